@@ -6,9 +6,14 @@
 
 A "step" = forward + backward + optimizer (+ gradient all-reduce when N > 1) of ResNet-50 → ArcFace(10 000 ids) on a
 synthetic 224x224x3 batch of 256 images per GPU that is already resident in HBM (BASELINE.json configs[1] / [2]).
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events around every kernel launch of extra,
-instrumented steps after the timed region; `cpu_baseline` times the oracle restatement of the reference path
-(PyTorch-CPU fp32) on the host cores (rank 0, N = 1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (`value`,
+`ms_per_step`); `roofline`, `cpu_baseline`, `extra` and `host_enqueue_ms_empty_queue` are null in it.  With --full it goes on
+after the timed region: `roofline` is measured live with HIP events around every kernel launch of extra, instrumented steps;
+`cpu_baseline` times the oracle restatement of the reference path (PyTorch-CPU fp32) on the host cores (rank 0, N = 1 only);
+`extra` holds the other BASELINE configs (Swin-T, the 10k x 1M match, the eval embedder, fp32, augmentation, the DDP path).
+
+  python bench.py --full                                 (the complete record; --detail FILE needs it)
+  python bench.py --dump-outputs DIR                     (the last timed step's outputs as DIR/*.npy, see dump_outputs)
 """
 import argparse
 import json
@@ -416,6 +421,33 @@ def augment_extra(device):
     return res
 
 
+DUMP_SAMPLE = 1 << 22     # elements kept of an output larger than this (a fixed, seeded sample)
+
+
+def dump_outputs(out, ml, outdir):
+    """What the caller of the timed path holds after the last timed step, as float32 DIR/<name>.npy: `loss`, `emb` (B x 512) and
+    `logits` (B x classes) of the step's forward, and the parameters the optimizer step wrote (`params`) and the gradients the
+    backward left (`grads`), both over all parameters of the model in named_parameters() order.  An array of more than
+    DUMP_SAMPLE elements is written as the flat elements at DUMP_SAMPLE sorted indices drawn without replacement by
+    numpy.random.default_rng(0), so the files depend on the arguments only and stay under 64 MB in all (44 MB at the defaults)."""
+    os.makedirs(outdir, exist_ok=True)
+
+    def save(name, t):
+        t = t.detach().float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.flatten()[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy())
+
+    save("loss", out["loss"].reshape(1))
+    save("emb", out["emb"])
+    if out.get("logits") is not None:
+        save("logits", out["logits"])
+    params = [p for _, p in ml.named_parameters()]
+    save("params", torch.cat([p.detach().float().flatten() for p in params]))
+    save("grads", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().flatten() for p in params]))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher around it: re-execute this command line as N ranks (one per GPU) under
     torch.distributed.run on 127.0.0.1 with a free port; rank 0's JSON line is this process's only stdout line."""
@@ -490,10 +522,19 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the Swin-T / match / eval / fp32 measurements after the headline")
-    ap.add_argument("--detail", default=None, help="write per-launch timings grouped by geometry to this JSON file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline, the CPU baselines and the other configs (the --no-* switches "
+                         "trim this); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--detail", default=None, help="write per-launch timings grouped by geometry to this JSON file (needs --full)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="no GPU work: every rank joins a gloo group, sums the rank ids and rank 0 prints one JSON line (CPU test of the --gpus N launcher path)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.detail and not (args.full and not args.no_roofline):
+        ap.error("--detail comes from the instrumented steps of --full (without --no-roofline)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -533,10 +574,10 @@ def main():
         if ddp is not None:
             ddp.finish_backward()
         opt.step()
-        return out["loss"]
+        return out
 
     for _ in range(args.warmup):
-        loss = step()
+        step()
 
     def fence():
         if dist is not None:
@@ -546,7 +587,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        out = step()
     host_ms = (time.perf_counter() - t0) / args.steps * 1e3   # host time to ENQUEUE a step (GPU-bound if << ms_per_step)
     fence()
     elapsed = time.perf_counter() - t0
@@ -554,23 +595,28 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
-    final_loss = float(loss.item())
-    # host time to enqueue ONE step into an EMPTY queue (no back-pressure from the GPU): what the host side really costs
-    host_free = []
-    for _ in range(3):
+    final_loss = float(out["loss"].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, ml, args.dump_outputs)   # before any further step changes the parameters
+    del out
+    host_free_ms = None
+    if args.full:
+        # host time to enqueue ONE step into an EMPTY queue (no back-pressure from the GPU): what the host side really costs
+        host_free = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            host_free.append((time.perf_counter() - t1) * 1e3)
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        host_free.append((time.perf_counter() - t1) * 1e3)
-    torch.cuda.synchronize()
-    host_free_ms = min(host_free)
+        host_free_ms = round(min(host_free), 3)
     ms = elapsed / args.steps * 1e3
     value = args.batch * world * args.steps / elapsed
 
     roof = None
     tr = None
     nprof = 3
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # EVERY rank runs the instrumented steps (they contain the gradient all-reduces); only rank 0 reports them
         from pets_face_recognition_amd._hip import set_tracer, EventTracer
         tr = EventTracer()
@@ -707,17 +753,17 @@ def main():
         del ml, opt, ddp
         ml = opt = None
         torch.cuda.empty_cache()
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             ms_leg = match_sharded_leg(device, rank, world, dist)
             if rank == 0 and world > 1:
                 extra = {"match_sharded": ms_leg}
-    if rank == 0 and world == 1 and not args.no_extras and args.arch == "resnet50" and args.dtype == "bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.arch == "resnet50" and args.dtype == "bf16":
         del ml, opt
         torch.cuda.empty_cache()
         extra = extras(args, device)
         if ms_leg is not None:
             extra["match_sharded"] = ms_leg
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_thread_sweep(args)
         if cpu is not None and args.arch == "resnet50" and not args.no_extras:
             try:
@@ -728,7 +774,7 @@ def main():
     if rank == 0:
         line = {"metric": f"FE train images/sec @224^2 bs={args.batch}/GPU", "value": round(value, 1), "unit": "images/sec",
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "host_enqueue_ms_per_step": round(host_ms, 3),
-                "host_enqueue_ms_empty_queue": round(host_free_ms, 3),
+                "host_enqueue_ms_empty_queue": host_free_ms,
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
                 "config": {"workload": f"{args.arch} FE + ArcFace(s=64,m=0.5) + CE, {args.classes} ids, 224x224x3, "
                                        f"fwd+bwd+SGD(momentum 0.9, param groups of the reference recipe)",

@@ -2,7 +2,7 @@
 # usage: ab_env.sh VAR v1 v2 ...   -> bench ms/step + entry-point times per value
 VAR=$1; shift
 for v in "$@"; do
-  env $VAR=$v timeout 200 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python -c "
+  env $VAR=$v timeout 200 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,5 +1,6 @@
 """The CPU oracle (oracle/) against the golden vectors generated from the reference's own modules
 (oracle/make_golden.py) — and the product's CPU (torch) execution path against the same vectors."""
+import math
 import os
 
 import numpy as np
@@ -19,6 +20,25 @@ def _arc_cases():
                 yield G, key, arc, easy, gamma
 
 
+def _logits_close(lo, G, key, arc, easy, rtol=1e-6, atol=1e-5):
+    """torch.allclose(lo, golden, rtol, atol), with the bound of each label entry scaled by how much the margin function amplifies
+    a change of the cosine there (|d shifted / d cos|, never below 1).  Near cos = 1 ArcFace's cos(θ + m) has slope
+    cos m + sin m · cos θ / sin θ (≈ 56 at cos θ = 0.99996), so the one-ulp spread of the cosine GEMM between BLAS code paths
+    (summation order; e.g. MKL on non-Intel hosts) becomes tens of ulps of that logit.  Every other entry keeps the plain bound."""
+    gold = torch.tensor(G[key + "_logits"])
+    tol = atol + rtol * gold.abs()
+    if arc:
+        m = float(G[key + "_m"])
+        x, w = torch.tensor(G[key + "_x"]).double(), torch.tensor(G[key + "_w"]).double()
+        rows = torch.arange(x.shape[0])
+        c = (torch.nn.functional.normalize(x, dim=1) @ torch.nn.functional.normalize(w, dim=1).t())[rows, torch.tensor(G[key + "_label"]).long()]
+        on_margin = c > 0 if easy else c > math.cos(math.pi - m)
+        slope = math.cos(m) + math.sin(m) * c / (1.0 - c * c).clamp_min(1e-30).sqrt()
+        scale = torch.where(on_margin, slope.abs(), torch.ones_like(c)).clamp_min(1.0).float()
+        tol[rows, torch.tensor(G[key + "_label"]).long()] *= scale
+    return bool(((lo.detach() - gold).abs() <= tol).all())
+
+
 def test_oracle_arcface_matches_reference_vectors():
     from oracle import arcface_ref
     n = 0
@@ -30,7 +50,7 @@ def test_oracle_arcface_matches_reference_vectors():
         lo = arcface_ref.arc_margin_logits(x, w, y, s, m, easy) if arc else arcface_ref.add_margin_logits(x, w, y, s, m)
         loss = arcface_ref.focal_loss(lo, y, gamma)
         loss.backward()
-        assert torch.allclose(lo, torch.tensor(G[key + "_logits"]), rtol=1e-6, atol=1e-5), key
+        assert _logits_close(lo, G, key, arc, easy), key
         assert abs(loss.item() - float(G[key + "_loss"])) < 1e-5
         assert torch.allclose(x.grad, torch.tensor(G[key + "_dx"]), rtol=1e-4, atol=1e-6)
         assert torch.allclose(w.grad, torch.tensor(G[key + "_dw"]), rtol=1e-4, atol=1e-6)
@@ -49,7 +69,7 @@ def test_product_cpu_path_losses_match_reference_vectors():
         x = torch.tensor(G[key + "_x"]).requires_grad_(True)
         r = wrap(x, torch.tensor(G[key + "_label"]))
         r["loss"].backward()
-        assert torch.allclose(r["logits"], torch.tensor(G[key + "_logits"]), rtol=1e-6, atol=1e-5), key
+        assert _logits_close(r["logits"], G, key, arc, easy), key
         assert abs(r["loss"].item() - float(G[key + "_loss"])) < 1e-5
         assert torch.allclose(x.grad, torch.tensor(G[key + "_dx"]), rtol=1e-4, atol=1e-6)
         assert set(r.keys()) == {"loss", "emb", "logits"}

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 # bench.py takes its per-launch HIP-event timings (a tracer forces serial execution), so the per-kernel averages of the
 # two agree; with the side stream on, concurrently running kernels stretch each other's durations.
 export PFR_SIDE_STREAM=0
-CMD="python $PWD/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-extras"
+CMD="python $PWD/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-extras"
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o stats -- $CMD > $OUT/${TAG}_prof_run.log 2>&1 )
 f=$(find $OUT/prof_$TAG -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp "$f" $OUT/${TAG}_kernel_stats_bench_resnet50_bs256_bf16.csv
@@ -27,10 +27,10 @@ SQSET="GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ
 python tools/pmc_top5.py $OUT/pmc_${TAG}_SQ 5 > $OUT/${TAG}_pmc_top5.txt 2>&1
 rm -rf $OUT/pmc_${TAG}_SQ
 # per-geometry table of the conv launches against max(MFMA, HBM) bounds (serialised launches, HIP events)
-python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --detail $OUT/${TAG}_detail.json > /dev/null 2>&1
+python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --detail $OUT/${TAG}_detail.json > /dev/null 2>&1
 python tools/layer_roofline.py $OUT/${TAG}_detail.json $OUT/${TAG}_layer_roofline.md > /dev/null
 # Swin-T bs 128 (BASELINE config 4): kernel stats + HBM traffic of its conv/linear/attention family
-SCMD="python $PWD/bench.py --arch swin_t --batch 128 --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-extras"
+SCMD="python $PWD/bench.py --full --arch swin_t --batch 128 --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-extras"
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_swin -o stats -- $SCMD > $OUT/${TAG}_prof_swin_run.log 2>&1 )
 f=$(find $OUT/prof_${TAG}_swin -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp "$f" $OUT/${TAG}_kernel_stats_bench_swin_t_bs128_bf16.csv
@@ -48,7 +48,7 @@ f=$(find $OUT/prof_${TAG}_match -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp "$f" $OUT/${TAG}_kernel_stats_match_10kx1M.csv
 rm -rf $OUT/prof_${TAG}_swin $OUT/prof_${TAG}_match $OUT/pmc_${TAG}_swin_FETCH_SIZE $OUT/pmc_${TAG}_swin_WRITE_SIZE
 unset PFR_SIDE_STREAM
-python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench_default.json
-python bench.py --arch swin_t --batch 128 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/${TAG}_bench_swin_t_bs128.json
+python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench_default.json
+python bench.py --full --arch swin_t --batch 128 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/${TAG}_bench_swin_t_bs128.json
 rm -rf $OUT/prof_$TAG $OUT/pmc_${TAG}_FETCH_SIZE $OUT/pmc_${TAG}_WRITE_SIZE
 ls -la $OUT | tail -12

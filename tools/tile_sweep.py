@@ -1,6 +1,6 @@
 """Tile-choice sweep for the conv / GEMM launches of a train step.
-   1. python bench.py --detail gpurun_out/detail.json ...      (lists the distinct launch geometries of a step)
-   2. python tools/tile_sweep.py gpurun_out/detail.json       (re-runs itself once per forced tile: PFR_TUNING=igemm_tile=<id>)
+   1. python bench.py --full --detail detail.json ...         (lists the distinct launch geometries of a step)
+   2. python tools/tile_sweep.py detail.json                 (re-runs itself once per forced tile: PFR_TUNING=igemm_tile=<id>)
 Prints, per geometry, the cold time of every tile variant and of the built-in heuristic."""
 import sys, os, re, json, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
