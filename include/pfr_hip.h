@@ -10,7 +10,7 @@
  * Conventions
  *   - every pointer is a DEVICE pointer owned by the caller (the library never allocates, frees or retains);
  *   - tensors are NHWC ("channels last"), dense, channel count a multiple of 16 bytes / sizeof(element);
- *   - dtype: PFR_F32 = 0 (exact-f32 MFMA, the parity path), PFR_BF16 = 1 (bf16 in, f32 accumulate);
+ *   - dtype: PFR_F32 = 0 (exact-f32 MFMA, the parity path), PFR_BF16 = 1 (bf16 in, f32 accumulate), PFR_I8 = 2 (match only);
  *   - `stream` is a hipStream_t (pass torch.cuda.current_stream().cuda_stream); all calls are asynchronous;
  *   - workspaces are supplied by the caller; their sizes come from the *_splits / *_blocks / *_mtile queries;
  *   - return value: 0 = ok, <0 = error (PFR_ERR_*), message via pfr_last_error() (thread-local);
@@ -27,6 +27,7 @@ extern "C" {
 
 #define PFR_F32 0
 #define PFR_BF16 1
+#define PFR_I8 2   /* int8 selection operand of the gallery match (pfr_quantize_rows_i8), int32 accumulate */
 #define PFR_OK 0
 #define PFR_ERR_ARG (-1)
 #define PFR_ERR_HIP (-2)
@@ -361,6 +362,26 @@ int pfr_topk_update(const float* scores, int rows, int ld, int n, int col0, int 
 int pfr_match_scores_filter(const void* q, const void* g, int dtype, int Q, int n, int D, int col0, int K, void* state,
                             void* cand, int cap, int exclude_self, pfr_stream_t stream);
 int pfr_topk_merge(const void* cand, int cap, int rows, int K, void* state, pfr_stream_t stream);
+/* ---- int8 selection (match.cosine_topk(compute_dtype=torch.int8)): per-row scalar-quantised operands, exact int32 accumulation on
+ * v_mfma_i32_32x32x32_i8, fp32 selection scores that feed the same running lists, filter, re-scoring and certificate as bf16.
+ *   Quantiser, per row x[0..D):  x̂ = x · inv with inv = 1 / max(|x|_2, eps) (the arithmetic of pfr_l2norm_dual), or x̂ = x when
+ *     normalize == 0;  m = max_i |x̂_i|;  r = 127.0f / m;  q_i = (int8) rintf(x̂_i · r) (round half to even);  s = m / 127.0f.
+ *     When r is +inf (m == 0, or m so small that the quotient overflows) the row is all zero and s = 0.  Columns D .. ldq-1 are 0.
+ *   Selection score of query row a and gallery row b:  score = ((float) acc · s_a) · s_b  with acc = Σ_i q_a,i · q_b,i accumulated
+ *     exactly in int32 (the conversion to float rounds to nearest even; exact for Dp <= 1040), the two fp32 products in this order.
+ *     pfr_match_scores_i8 and the filter epilogue of pfr_match_scores_filter_i8 compute it with the same operations: the same bits.
+ * pfr_quantize_rows_i8: x [rows][D] fp32 (D % 4 == 0, D <= 2048) -> q [rows][ldq] int8 (ldq >= D, ldq % 4 == 0; the match needs
+ *   ldq = Dp, a multiple of 128), scale [rows] fp32, and when non-NULL xn_f32 [rows][D] = x̂ and inv_norm [rows] = inv (normalize only). */
+int pfr_quantize_rows_i8(const float* x, void* q, int ldq, float* scale, float* xn_f32, float* inv_norm, int rows, int D, int normalize,
+                         float eps, pfr_stream_t stream);
+/* selection scores of one gallery chunk: out [Q][ld] fp32 (n valid columns) = score(q row, g row) for q [Q][Dp], g [n][Dp] int8 rows of
+ * pfr_quantize_rows_i8 with their scales q_scale [Q], g_scale [n] (g and g_scale point at the chunk's first row).  Dp % 128 == 0, <= 2048. */
+int pfr_match_scores_i8(const void* q, const float* q_scale, const void* g, const float* g_scale, int Q, int n, int Dp, float* out, int ld,
+                        pfr_stream_t stream);
+/* pfr_match_scores_filter on the int8 operands above: a selection score is appended to query r's candidate list iff its key beats r's
+ * current K-th best (exact: the comparison is on the score as defined, not on a bound of it). */
+int pfr_match_scores_filter_i8(const void* q, const float* q_scale, const void* g, const float* g_scale, int Q, int n, int Dp, int col0,
+                               int K, void* state, void* cand, int cap, int exclude_self, pfr_stream_t stream);
 int pfr_topk_flags(const void* state, int rows, int K, int* out_host, pfr_stream_t stream);
 int pfr_topk_finish(const void* state, int rows, int K, float* out_scores, int* out_idx, pfr_stream_t stream);
 /* exact fp32 re-scoring of KC candidates per query, keeps the best K.  q: L2-normalised fp32 rows; g: L2-normalised fp32 rows (g_scale

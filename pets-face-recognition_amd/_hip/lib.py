@@ -8,7 +8,7 @@ import ctypes
 import os
 import re
 
-PFR_F32, PFR_BF16 = 0, 1
+PFR_F32, PFR_BF16, PFR_I8 = 0, 1, 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _PKG = os.path.dirname(_HERE)
@@ -172,10 +172,12 @@ def dtype_id(torch_dtype_):
         return PFR_F32
     if torch_dtype_ == torch.bfloat16:
         return PFR_BF16
+    if torch_dtype_ == torch.int8:
+        return PFR_I8
     raise PfrError(f"unsupported dtype {torch_dtype_}")
 
 
 def torch_dtype(dtype_id_):
     import torch
 
-    return {PFR_F32: torch.float32, PFR_BF16: torch.bfloat16}[dtype_id_]
+    return {PFR_F32: torch.float32, PFR_BF16: torch.bfloat16, PFR_I8: torch.int8}[dtype_id_]

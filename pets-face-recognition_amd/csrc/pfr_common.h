@@ -13,11 +13,14 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+typedef int32_t i32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // dtype enum of the C-ABI (include/pfr_hip.h)
 #define PFR_F32 0
 #define PFR_BF16 1
+#define PFR_I8 2
 
 // error codes of the C-ABI
 #define PFR_OK 0
@@ -128,6 +131,10 @@ template <> struct DT<float> {
 template <> struct DT<bf16_t> {
   static constexpr int KPACK = 8;
   static constexpr int ID = PFR_BF16;
+};
+template <> struct DT<int8_t> {   // the match's 8-bit selection operand (pfr_quantize_rows_i8); int32 accumulators
+  static constexpr int KPACK = 16;
+  static constexpr int ID = PFR_I8;
 };
 
 __device__ __forceinline__ float to_f32(float v) { return v; }

@@ -108,6 +108,72 @@ extern "C" int pfr_l2norm_dual(const float* x, void* xn_bf16, float* xn_f32, flo
   return PFR_OK;
 }
 
+// int8 selection operand of the gallery match (the quantiser's definition: include/pfr_hip.h at pfr_quantize_rows_i8).  One pass per row
+// as l2norm_dual (float4 loads kept in registers, the same norm arithmetic): x̂ = x · inv (normalize) or x, then m = max |x̂_i| (a wave
+// maximum: exact), q_i = rint(x̂_i · (127 / m)), s = m / 127.  Writes the int8 row with leading dimension ldq (columns D .. ldq zero), the
+// scale, and optionally the fp32 row x̂ and the inverse norm.
+template <int NK>
+__global__ __launch_bounds__(256) void quantize_rows_i8_kernel(const float* __restrict__ x, int8_t* __restrict__ q, int ldq, float* __restrict__ scale,
+                                                               float* __restrict__ xf, float* __restrict__ inv_norm, int rows, int D, int normalize,
+                                                               float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const f32x4* xr = reinterpret_cast<const f32x4*>(x + (size_t)row * D);
+  const int n4 = D >> 2;
+  f32x4 v[NK];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) v[k] = xr[min(lane + 64 * k, n4 - 1)];
+  __builtin_amdgcn_sched_barrier(0);
+  float ss = 0.f;
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    if (lane + 64 * k >= n4) v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ss = fmaf(v[k][e], v[k][e], ss);
+  }
+  if (normalize) {
+    ss = wave_sum(ss);
+    const float inv = 1.f / fmaxf(sqrtf(ss), eps);
+    if (lane == 0 && inv_norm) inv_norm[row] = inv;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) v[k] = v[k] * inv;
+  }
+  float m = 0.f;
+#pragma unroll
+  for (int k = 0; k < NK; ++k)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) m = fmaxf(m, fabsf(v[k][e]));
+  m = wave_max(m);
+  const float r = 127.f / m;
+  const bool live = r < INFINITY;          // m == 0 (or so small that 127 / m overflows): an all-zero row with scale 0
+  const float rq = live ? r : 0.f;
+  if (lane == 0) scale[row] = live ? m / 127.f : 0.f;
+  uint32_t* qr = reinterpret_cast<uint32_t*>(q + (size_t)row * ldq);
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    const int i = lane + 64 * k;
+    if (i < n4) {
+      if (xf) reinterpret_cast<f32x4*>(xf + (size_t)row * D)[i] = v[k];
+      uint32_t w = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w |= (uint32_t)(uint8_t)(int8_t)(int)rintf(v[k][e] * rq) << (8 * e);
+      qr[i] = w;
+    }
+  }
+  for (int i = n4 + lane; i < (ldq >> 2); i += 64) qr[i] = 0u;
+}
+extern "C" int pfr_quantize_rows_i8(const float* x, void* q, int ldq, float* scale, float* xn_f32, float* inv_norm, int rows, int D, int normalize,
+                                    float eps, hipStream_t st) {
+  PFR_CHECK_ARG(x && q && scale && rows > 0, "pfr_quantize_rows_i8: null pointer");
+  PFR_CHECK_ARG(D > 0 && D % 4 == 0 && D <= 2048 && ldq >= D && ldq % 4 == 0,
+                "pfr_quantize_rows_i8: D must be a multiple of 4 and <= 2048, ldq >= D a multiple of 4");
+  if (D <= 512) hipLaunchKernelGGL(quantize_rows_i8_kernel<2>, dim3((rows + 3) / 4), dim3(256), 0, st, x, (int8_t*)q, ldq, scale, xn_f32, inv_norm, rows, D, normalize, eps);
+  else hipLaunchKernelGGL(quantize_rows_i8_kernel<8>, dim3((rows + 3) / 4), dim3(256), 0, st, x, (int8_t*)q, ldq, scale, xn_f32, inv_norm, rows, D, normalize, eps);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
 // dx = inv_norm · (dxn − xn · (xn·dxn)) ; xn is the normalised row recomputed in fp32 from x and inv_norm
 template <typename TI, typename TOo>
 __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const TI* __restrict__ x, const float* __restrict__ inv_norm,

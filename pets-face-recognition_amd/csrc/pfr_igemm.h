@@ -29,6 +29,10 @@ struct IgemmParams {
   int res_sub;                     // streaming join only: `residual` is compact [N][OH/2][OW/2][Cout], added at even (oh, ow)
   const unsigned char* res_mask;   // optional bit mask of `residual` ([M][ldy / KPACK] bytes, pfr_bn_act_mask): masked-out elements add 0
   int cap, col0, self_excl;   // act 4: list capacity, gallery index of column 0, skip column == row (all-vs-all evaluation)
+  // int8 match operands (T = int8_t, pfr_match_scores_i8 / pfr_match_scores_filter_i8): per-row scales of the query rows [M] and of the
+  // gallery rows [Cout]; the epilogues turn the int32 accumulator of (m, co) into the selection score ((float) acc * qscale[m]) * gscale[co]
+  const float* qscale = nullptr;
+  const float* gscale = nullptr;
   // act 4, persistent launch: L2-blocked tile order.  fo_qg > 0: the workgroups of one XCD (block b runs on XCD b % 8 — speed only) own a
   // contiguous range of gallery (column) tiles and walk it in super-steps of fo_qg query tiles x fo_gg gallery tiles (fo_qg * fo_gg =
   // workgroups per XCD), query group outermost: what an XCD works on at any time is a few MB of operands that stay in its L2, instead

@@ -64,7 +64,12 @@ __global__ __launch_bounds__(NW * 64, (KCH_ == 4 && NW == 4 && NST_ == 2 && size
   // FILT (top-K filter epilogue, act 4): scores are compared straight from the accumulators — no transpose buffer
   // FILT: + two winner queues of one entry per thread (u64 key|~column and the query row) and their counters: see "deferred append" below
   constexpr int FQCAP = NW * 64, FQOFF = NST * STAGE, FQBYTES = FILT ? 2 * FQCAP * 12 + 16 : 0;
-  constexpr int SMEM = FILT ? NST * STAGE + FQBYTES : ((NST * STAGE + PROB > EPI + RED) ? NST * STAGE + PROB : EPI + RED);
+  // int8 (I8): int32 accumulators, scaled into selection scores by the epilogue (IgemmParams::qscale / gscale); FILT + I8: + two staging
+  // buffers of the tile's BP gallery scales (tile t fills buffer t & 1 while the slowest wave may still read t - 1's)
+  constexpr bool I8 = sizeof(T) == 1;
+  static_assert(!I8 || (sizeof(TO) == 4 && !PRO && !BNB && !EPRE && NT >= BP), "int8 tiles: fp32 scores, no fused pre/post ops");
+  constexpr int GSOFF = FQOFF + FQBYTES, GSBYTES = (FILT && I8) ? 2 * BP * 4 : 0;
+  constexpr int SMEM = FILT ? NST * STAGE + FQBYTES + GSBYTES : ((NST * STAGE + PROB > EPI + RED) ? NST * STAGE + PROB : EPI + RED);
   static_assert(SMEM <= 160 * 1024, "tile does not fit the 160 KiB LDS");
   __shared__ __attribute__((aligned(16))) char smem[SMEM];
 
@@ -407,6 +412,24 @@ __global__ __launch_bounds__(NW * 64, (KCH_ == 4 && NW == 4 && NST_ == 2 && size
       tks[j] = m < p.M ? thrk[m] : 0xFFFFFFFFu;
     }
   }
+  // I8: the scales of the selection score, requested here as well.  tqs[j]: the query row this lane owns in accumulator column block j (the
+  // rows of tks).  tgs: FILT — the gallery scale of column n0 + tid (staged through LDS before the first barrier: a lane's 16 x TP columns
+  // would hold too many registers across the k-loop); tile kernel — the four columns of this thread's phase-2 chunk.
+  float tqs[I8 ? TQ : 1], tgs[I8 ? (FILT ? 1 : 16 / (int)sizeof(TO)) : 1];
+  if constexpr (I8) {
+#pragma unroll
+    for (int j = 0; j < TQ; ++j) {
+      const int m = m0 + wq * (BQ / WQ) + j * 32 + (lane & 31);
+      tqs[j] = m < p.M ? p.qscale[m] : 0.f;
+    }
+    if constexpr (FILT) {
+      tgs[0] = (tid < BP && n0 + tid < p.Cout) ? p.gscale[n0 + tid] : 0.f;
+    } else {
+      const int co = n0 + (tid % (BP * (int)sizeof(TO) / 16)) * (16 / (int)sizeof(TO));
+#pragma unroll
+      for (int e = 0; e < 16 / (int)sizeof(TO); ++e) tgs[e] = co + e < p.Cout ? p.gscale[co + e] : 0.f;
+    }
+  }
 
   // ---- NST-slot ring with counted waits: the DMA of k-steps kt+2 … kt+NST-1 stays in flight across the barrier that
   //      publishes kt+1 (raw s_barrier: no implicit vmcnt(0) drain); NST = 2 is the classic double buffer.
@@ -424,6 +447,9 @@ __global__ __launch_bounds__(NW * 64, (KCH_ == 4 && NW == 4 && NST_ == 2 && size
   if constexpr (PRO) {
     __syncthreads();  // coefficients visible
     if (npre > 1) fixup(0, okA, cA); else fixup(0, okB, cB);
+  }
+  if constexpr (FILT && I8) {   // (published by the barrier below; the epilogue of this tile reads buffer ft & 1 = fb)
+    if (tid < BP) reinterpret_cast<float*>(smem + GSOFF)[(ft & 1) * BP + tid] = tgs[0];
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -503,6 +529,22 @@ __global__ __launch_bounds__(NW * 64, (KCH_ == 4 && NW == 4 && NST_ == 2 && size
           __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, (__attribute__((address_space(3))) void*)(smem + (BP + (j * NW + wave) * RPI) * ROWB), 16, (int)off, 0, 0, 0);
         }
       }
+    }
+    if constexpr (I8) {
+      // int32 accumulators -> selection scores ((float) acc * q_scale) * g_scale, in the order of the definition (include/pfr_hip.h) — the
+      // same arithmetic as pfr_match_scores_i8, so both give the same bits.  The 16 columns of block i of this lane are 4 runs of 4 adjacent
+      // ones (acc_row): one LDS read of 16 bytes per run, consumed at once (the 256x256 tile has no registers to hold more of them).
+      const float* gsl = reinterpret_cast<const float*>(smem + GSOFF) + fb * BP + wp * (BP / WP) + 4 * (lane >> 5);
+#pragma unroll
+      for (int i = 0; i < TP; ++i)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const f32x4 gs4 = *reinterpret_cast<const f32x4*>(gsl + i * 32 + 8 * g);
+#pragma unroll
+          for (int j = 0; j < TQ; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = ((float)__float_as_int(acc[i][j][4 * g + e]) * tqs[j]) * gs4[e];
+        }
     }
     // Fast path (round 5; the common case of every fused chunk): the tile's columns all exist, nothing is excluded and every threshold
     // of this wave is the key of a POSITIVE score — for those the float order IS the key order, so the exact test is ONE compare per score
@@ -591,7 +633,12 @@ __global__ __launch_bounds__(NW * 64, (KCH_ == 4 && NW == 4 && NST_ == 2 && size
       for (int qd = 0; qd < 4; ++qd) {
         const int co = wp * (BP / WP) + i * 32 + 8 * qd + 4 * (lane >> 5);
         char* dst = smem + mrow * OROWB + co * (int)sizeof(TO);
-        if constexpr (sizeof(TO) == 4) {
+        if constexpr (I8) {   // first factor of the selection score; the gallery scale follows in phase 2
+          f32x4 v;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = (float)__float_as_int(acc[i][j][4 * qd + e]) * tqs[j];
+          *reinterpret_cast<f32x4*>(dst) = v;
+        } else if constexpr (sizeof(TO) == 4) {
           f32x4 v = {acc[i][j][4 * qd], acc[i][j][4 * qd + 1], acc[i][j][4 * qd + 2], acc[i][j][4 * qd + 3]};
           *reinterpret_cast<f32x4*>(dst) = v;
         } else {
@@ -694,6 +741,11 @@ __global__ __launch_bounds__(NW * 64, (KCH_ == 4 && NW == 4 && NST_ == 2 && size
     u32x4 v = *reinterpret_cast<const u32x4*>(smem + rr * OROWB + oc * 16);
     float f[KPO];
     Chunk<TO>::unpack(v, f);
+    if constexpr (I8) {
+#pragma unroll
+      for (int e = 0; e < KPO; ++e) f[e] *= tgs[e];
+      v = Chunk<TO>::pack(f);
+    }
     char* dst = yb + ((size_t)m * p.ldy + co) * sizeof(TO);
     const bool post = p.bias || p.accumulate || p.out_relu || p.residual || p.act;
     if (post) {
@@ -1382,4 +1434,63 @@ extern "C" int pfr_match_scores_filter(const void* q, const void* g, int dtype, 
     return launch_filter_k<bf16_t, 128, 128, 8, 4, 2>(p, stream);
   }
   return launch_filter_k<float, 128, 128, 8, 4, 2>(p, stream);
+}
+
+// ---- int8 selection of the gallery match (selection score: include/pfr_hip.h).  q [Q][Dp], g [n][Dp] int8 rows of pfr_quantize_rows_i8,
+// q_scale [Q], g_scale [n] (g and g_scale both point at the chunk's first gallery row).  Same tile kernel, same LDS layout and DMA as bf16:
+// a 128-byte k-step holds 128 int8 k-values (one v_mfma_i32_32x32x32_i8 per 16-byte half instead of one bf16 MFMA), so a 512-byte row is
+// 4 k-steps where a bf16 row is 8.
+static IgemmParams match_i8_params(const void* q, const float* q_scale, const void* g, const float* g_scale, int Q, int n, int Dp) {
+  IgemmParams p;
+  p.x = q; p.w = g; p.y = nullptr; p.y2 = nullptr; p.ccnt = nullptr;
+  p.N = Q; p.H = 1; p.W = 1; p.C = Dp;
+  p.R = 1; p.S = 1; p.OH = 1; p.OW = 1; p.ostride = 1; p.pad = 0; p.idil_log2 = 0;
+  p.Cout = n; p.ldy = n;
+  p.M = Q; p.K = Dp;
+  p.stats_part = nullptr; p.bias = nullptr; p.residual = nullptr; p.accumulate = 0; p.out_relu = 0;
+  p.pro_scale = nullptr; p.pro_shift = nullptr; p.pro_relu = 0;
+  p.act = 0; p.cap = 0; p.col0 = 0; p.self_excl = 0; p.res_mask = nullptr; p.res_sub = 0;
+  p.bnb_mask = nullptr;
+  for (int i = 0; i < 2; ++i) { p.bnb_x[i] = nullptr; p.bnb_coef[i] = nullptr; p.bnb_part[i] = nullptr; }
+  p.div_ohow = make_fastdiv(1u);
+  p.div_ow = make_fastdiv(1u);
+  p.qscale = q_scale; p.gscale = g_scale;
+#ifdef PFR_IGEMM_TRACE
+  p.trace = g_igemm_trace;
+  p.dbg = g_igemm_dbg;
+#endif
+  return p;
+}
+
+extern "C" int pfr_match_scores_i8(const void* q, const float* q_scale, const void* g, const float* g_scale, int Q, int n, int Dp,
+                                   float* out, int ld, hipStream_t stream) {
+  PFR_CHECK_ARG(q && q_scale && g && g_scale && out, "pfr_match_scores_i8: null pointer");
+  PFR_CHECK_ARG(Q > 0 && n > 0 && Dp > 0 && Dp % 128 == 0 && Dp <= 2048 && ld >= n && ld % 4 == 0,
+                "pfr_match_scores_i8: bad geometry (Dp %% 128 == 0, <= 2048; ld >= n, ld %% 4 == 0)");
+  IgemmParams p = match_i8_params(q, q_scale, g, g_scale, Q, n, Dp);
+  p.y = out; p.ldy = ld;
+  // one 128x128 tile per workgroup (the materialised chunk is the schedule's first segment only; the 256x256 tile's fp32 transpose
+  // buffer would not fit the LDS)
+  p.pclass = 0; p.mclass = 0; p.tpc = 1;
+  p.div_chw = make_fastdiv(1u); p.div_cw = make_fastdiv(1u);
+  p.tilesM = (Q + 127) / 128;
+  p.tilesN = (n + 127) / 128;
+  p.krot = 0;
+  p.dma_sched = pfr_knob(KNOB_IGEMM_DMA);
+  hipLaunchKernelGGL((igemm_kernel<int8_t, float, 128, 128, false, true, 8, 4, 2, 2>), dim3((unsigned)(p.tilesM * p.tilesN)), dim3(256), 0,
+                     stream, p);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+extern "C" int pfr_match_scores_filter_i8(const void* q, const float* q_scale, const void* g, const float* g_scale, int Q, int n, int Dp,
+                                          int col0, int K, void* state, void* cand, int cap, int exclude_self, hipStream_t stream) {
+  PFR_CHECK_ARG(q && q_scale && g && g_scale && state && cand, "pfr_match_scores_filter_i8: null pointer");
+  PFR_CHECK_ARG(Q > 0 && n > 0 && Dp > 0 && Dp % 128 == 0 && Dp <= 2048 && K >= 1 && K <= 512 && cap >= 1,
+                "pfr_match_scores_filter_i8: bad geometry (Dp %% 128 == 0, <= 2048; 1 <= K <= 512)");
+  const TopkState t = topk_state(state, Q, K);
+  IgemmParams p = match_i8_params(q, q_scale, g, g_scale, Q, n, Dp);
+  p.act = 4; p.y = cand; p.y2 = t.thrk; p.ccnt = t.ccnt; p.cap = cap; p.col0 = col0; p.self_excl = exclude_self;
+  if ((long)((Q + 255) / 256) * ((n + 255) / 256) >= 160) return launch_filter_k<int8_t, 256, 256, 8, 8, 2>(p, stream);
+  return launch_filter_k<int8_t, 128, 128, 8, 4, 2>(p, stream);
 }

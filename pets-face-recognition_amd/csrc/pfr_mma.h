@@ -1,11 +1,12 @@
 // pfr_mma.h — the MFMA tile engine shared by the implicit-GEMM conv kernels (fwd / dgrad / wgrad / plain GEMM).
 //
-// Geometry (identical in BYTES for both dtypes):
+// Geometry (identical in BYTES for every dtype):
 //   * an LDS operand tile is ROWS x 64 B of k-values (32 bf16 or 16 f32) per k-step, row stride 80 B
 //     (64 + 16 pad → ds_read_b128 by the 16-lane groups of gfx950 is bank-conflict free);
 //   * a k-step holds two "k-groups" of 32 B per row; a k-group feeds ONE v_mfma_f32_32x32x16_bf16
 //     (lane = row, lane>>5 selects the 16-byte half) or FOUR v_mfma_f32_32x32x2_f32 (element j of both
-//     operands' 16-byte chunk is k-slot {j, 4+j}: any k-permutation is legal as long as A and B agree);
+//     operands' 16-byte chunk is k-slot {j, 4+j}: any k-permutation is legal as long as A and B agree), or ONE
+//     v_mfma_i32_32x32x32_i8 (int8: 16 k-values per 16-byte half, int32 accumulators bit-cast into the f32x16 registers);
 //   * 256 threads = 4 waves in a 2x2 grid; wave (wp, wq) owns P-rows [wp*BP/2, +BP/2) x Q-rows [wq*BQ/2, +BQ/2)
 //     as (BP/64) x (BQ/64) accumulators of 32x32.  The P operand is the MFMA "A" (accumulator ROW index),
 //     the Q operand the MFMA "B" (accumulator COLUMN index = lane & 31).
@@ -18,6 +19,14 @@
 template <typename T> struct KStep;  // elements per k-step
 template <> struct KStep<float> { static constexpr int BK = 16; };
 template <> struct KStep<bf16_t> { static constexpr int BK = 32; };
+template <> struct KStep<int8_t> { static constexpr int BK = 64; };
+
+// one k-group of int8 fragments: v_mfma_i32_32x32x32_i8 reads the same 16 bytes per lane as the bf16 form (16 k-values instead of 8) and
+// accumulates exactly in int32; the f32x16 accumulator registers carry the int32 bits (zero-initialised bits are the int 0 as well)
+__device__ __forceinline__ f32x16 mfma_i8(u32x4 a, u32x4 b, f32x16 c) {
+  return __builtin_bit_cast(f32x16, __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b),
+                                                                          __builtin_bit_cast(i32x16, c), 0, 0, 0));
+}
 
 template <typename T, int TP, int TQ>
 __device__ __forceinline__ void mma_kstep(const char* ldsP, const char* ldsQ, int lane, f32x16 (&acc)[TP][TQ]) {
@@ -39,6 +48,11 @@ __device__ __forceinline__ void mma_kstep(const char* ldsP, const char* ldsQ, in
         for (int j = 0; j < TQ; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fp[i]),
                                                                __builtin_bit_cast(bf16x8, fq[j]), acc[i][j], 0, 0, 0);
+    } else if constexpr (sizeof(T) == 1) {
+#pragma unroll
+      for (int i = 0; i < TP; ++i)
+#pragma unroll
+        for (int j = 0; j < TQ; ++j) acc[i][j] = mfma_i8(fp[i], fq[j], acc[i][j]);
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
@@ -128,6 +142,11 @@ __device__ __forceinline__ void mma_kstep_sw(const char* ldsP, const char* ldsQ,
         for (int j = 0; j < TQ; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fp[b][i]),
                                                                __builtin_bit_cast(bf16x8, fq[b][j]), acc[i][j], 0, 0, 0);
+    } else if constexpr (sizeof(T) == 1) {
+#pragma unroll
+      for (int i = 0; i < TP; ++i)
+#pragma unroll
+        for (int j = 0; j < TQ; ++j) acc[i][j] = mfma_i8(fp[b][i], fq[b][j], acc[i][j]);
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e)

@@ -24,12 +24,15 @@ class PreparedGallery:
     gallery answers query batch after query batch): the bf16 GEMM operand and, for the exact re-scoring, the fp32 copy.  Reuse is
     EXPLICIT — the caller builds the handle with `prepare_gallery(g)` and passes it to `cosine_topk` in place of `g`; nothing is keyed
     on tensor identity or version counters (writes through raw pointers — every kernel of this library — are invisible to them), so a
-    gallery buffer that was refilled needs a new handle.  1 M x 512: 1 GB (bf16) + 2 GB (fp32)."""
+    gallery buffer that was refilled needs a new handle.  1 M x 512: 1 GB (bf16) + 2 GB (fp32).
+    int8 (`compute_dtype=torch.int8`): `gn` holds the int8 rows [G, Dp] of `quantize_rows` (Dp = D rounded up to 128) and `qscale` their
+    fp32 scales [G]; 1 M x 512: 0.5 GB + 4 MB (+ 2 GB fp32 with rescore)."""
 
-    def __init__(self, gn, gn32, compute_dtype, rescore, normalized):
+    def __init__(self, gn, gn32, compute_dtype, rescore, normalized, qscale=None, dim=None):
         self.gn, self.gn32, self.gscale = gn, gn32, None
+        self.qscale = qscale        # int8 only: per-row scales of the int8 rows (gscale means the inverse norms of borrowed raw rows)
         self.compute_dtype, self.rescore, self.normalized = compute_dtype, rescore, normalized
-        self.shape, self.device = tuple(gn.shape), gn.device
+        self.shape, self.device = (gn.shape[0], gn.shape[1] if dim is None else dim), gn.device
 
     def __len__(self):
         return self.shape[0]
@@ -60,6 +63,49 @@ def _prep_rows(x32, T, rescore, normalize, borrow=False):
     return (x32 if T == torch.float32 else ops.cast(x32, T)), x32
 
 
+def quantize_rows(x, normalize=True, return_rows=False):
+    """The int8 operand of the match: per row x̂ = x / max(|x|, 1e-12) (or x itself with normalize=False), m = max |x̂_i|,
+    q_i = round_half_even(x̂_i · (127 / m)), scale = m / 127 (an all-zero row with scale 0 when 127 / m is +inf); the exact definition is
+    at pfr_quantize_rows_i8 in include/pfr_hip.h.  x [rows, D] on the device (D % 4 == 0, D <= 2048).
+    → (int8 [rows, Dp] with Dp = D rounded up to a multiple of 128, zero padded; fp32 scale [rows]) [+ the fp32 rows x̂ [rows, D]]."""
+    if not x.is_cuda:
+        raise PfrError("quantize_rows: the int8 operand is made on the device (gfx950)")
+    x32 = x.float().contiguous()
+    rows, D = x32.shape
+    if D % 4 or D > 2048:
+        raise PfrError(f"quantize_rows: D={D} must be a multiple of 4 and <= 2048")
+    Dp = (D + 127) // 128 * 128
+    q8 = torch.empty((rows, Dp), dtype=torch.int8, device=x.device)
+    sc = torch.empty(rows, dtype=torch.float32, device=x.device)
+    xf = torch.empty((rows, D), dtype=torch.float32, device=x.device) if return_rows else None
+    if rows:
+        lib.pfr_quantize_rows_i8(x32.data_ptr(), q8.data_ptr(), Dp, sc.data_ptr(), 0 if xf is None else xf.data_ptr(), 0, rows, D,
+                                 int(bool(normalize)), 1e-12, _stream())
+    return (q8, sc, xf) if return_rows else (q8, sc)
+
+
+def _prep_rows_i8(x32, rescore, normalize, borrow=False):
+    """int8 counterpart of _prep_rows: → ((int8 rows, scales), fp32 rows for the re-scoring or None[, inverse norms of borrowed raw rows])"""
+    rows, D = x32.shape
+    if D % 4 or D > 2048:
+        raise PfrError(f"cosine_topk(int8): D={D} must be a multiple of 4 and <= 2048")
+    Dp = (D + 127) // 128 * 128
+    q8 = torch.empty((rows, Dp), dtype=torch.int8, device=x32.device)
+    sc = torch.empty(rows, dtype=torch.float32, device=x32.device)
+    xf = inv = None
+    if rescore and borrow and normalize:     # the re-scoring reads the caller's raw rows times their inverse norms (as bf16 does)
+        inv = torch.empty(rows, dtype=torch.float32, device=x32.device)
+    elif rescore and normalize:
+        xf = torch.empty((rows, D), dtype=torch.float32, device=x32.device)
+    lib.pfr_quantize_rows_i8(x32.data_ptr(), q8.data_ptr(), Dp, sc.data_ptr(), 0 if xf is None else xf.data_ptr(),
+                             0 if inv is None else inv.data_ptr(), rows, D, int(bool(normalize)), 1e-12, _stream())
+    if rescore and not normalize:
+        xf = x32                              # rows are used as given (the scores are defined on them)
+    if inv is not None:
+        xf = x32
+    return ((q8, sc), xf, inv) if borrow else ((q8, sc), xf)
+
+
 def prepare_gallery(g, compute_dtype=torch.bfloat16, rescore=None, normalize=True):
     """Normalise a gallery once for many `cosine_topk(q, handle, k)` calls (same compute_dtype / rescore / normalize as those calls)."""
     if not g.is_cuda:
@@ -67,9 +113,18 @@ def prepare_gallery(g, compute_dtype=torch.bfloat16, rescore=None, normalize=Tru
     T = compute_dtype
     if rescore is None:
         rescore = T != torch.float32
+    if T == torch.int8:
+        g32 = g.float().contiguous()
+        (g8, gs), gn32 = _prep_rows_i8(g32, rescore, normalize)
+        if gn32 is not None and gn32.data_ptr() == g32.data_ptr() and g32.data_ptr() == g.data_ptr():
+            gn32 = gn32.clone()     # (normalize=False: the handle owns its rows, the caller may refill the buffer)
+        return PreparedGallery(g8, gn32, T, bool(rescore), bool(normalize), qscale=gs, dim=g.shape[1])
     gn, gn32 = _prep_rows(g.float().contiguous(), T, rescore, normalize)
     return PreparedGallery(gn, gn32, T, bool(rescore), bool(normalize))
 
+
+#: default candidate slack of the certified int8 selection (compute_dtype=torch.int8), measured on the GPU: profiles/match_int8.txt
+_I8_SLACK = 128
 
 #: what the last certified `cosine_topk` call on this process did: queries, candidates per query, the largest selection-score error measured,
 #: queries re-matched with a wider candidate list, queries re-matched exactly in fp32
@@ -91,7 +146,12 @@ def cosine_topk(q, g, k, compute_dtype=torch.bfloat16, chunk=131072, exclude_sel
     the same data); a query whose gap is below twice the largest error seen is matched again with a four times wider slack, and in fp32
     (exactly the reference's arithmetic) if it fails again.  With the check the default slack is max(28, k / 4) instead of max(28, 1.5 k):
     1.5 ms less at 10 k x 1 M x 512 (13.5 instead of 15.0 ms on the box that measured it), same results; `last_match_stats` records what the
-    check did."""
+    check did.
+    compute_dtype=torch.int8: the selection runs on per-row scalar-quantised rows (`quantize_rows`) on the int8 MFMA; the selection score is
+    ((float) Σ q_a,i q_b,i · s_a) · s_b (include/pfr_hip.h).  rescore and certify default to True and give the same exact top-k as bf16; the
+    int8 selection error is about 4x the bf16 one, so the default slack is wider: max(_I8_SLACK, k / 4).  The lists hold at most 512 entries:
+    from k = 512 - _I8_SLACK on the slack shrinks, at k = 512 there is none and every query that is not certified is re-matched in fp32.
+    rescore=False returns the top-k by the selection score itself (approximate; a 1 M x 512 handle then holds 0.5 GB + 4 MB)."""
     prepared = g if isinstance(g, PreparedGallery) else None
     if not q.is_cuda:
         if prepared is not None:
@@ -113,13 +173,21 @@ def cosine_topk(q, g, k, compute_dtype=torch.bfloat16, chunk=131072, exclude_sel
         # the running lists of the top-K kernels hold at most 512 entries per query (pfr_match.hip); silently returning
         # fewer columns, or re-scoring past the candidate list, would be wrong answers
         raise PfrError(f"cosine_topk: k={k} exceeds the 512-entry running list of the gfx950 top-K kernels")
+    i8 = T == torch.int8
     if slack is None:
-        slack = max(28, (k + 3) // 4) if certify else max(28, k // 2 + k)
+        if i8:
+            slack = max(_I8_SLACK, (k + 3) // 4) if certify else max(_I8_SLACK, 2 * k)
+        else:
+            slack = max(28, (k + 3) // 4) if certify else max(28, k // 2 + k)
     kc = max(k, min(512, k + slack)) if rescore else k
     q32 = q.float().contiguous()
-    qn, qn32 = _prep_rows(q32, T, rescore, normalize)
+    qn, qn32 = _prep_rows_i8(q32, rescore, normalize) if i8 else _prep_rows(q32, T, rescore, normalize)
     if prepared is not None:
         gn, gn32, gscale = prepared.gn, prepared.gn32, None      # (a handle owns a normalised copy: the caller may refill its buffer)
+        if i8:
+            gn = (gn, prepared.qscale)
+    elif i8:
+        gn, gn32, gscale = _prep_rows_i8(g.float().contiguous(), rescore, normalize, borrow=True)
     else:
         gn, gn32, gscale = _prep_rows(g.float().contiguous(), T, rescore, normalize, borrow=True)
     sched = dict(chunk=chunk, exclude_self=exclude_self, fused_filter=fused_filter, merge_every=merge_every, seed_cols=seed_cols)
@@ -138,7 +206,8 @@ def cosine_topk(q, g, k, compute_dtype=torch.bfloat16, chunk=131072, exclude_sel
             # (with exclude_self the fused filter identifies "self" by row == column: the whole set is matched again, not a subset)
             rows = None if exclude_self else bad
             stats["widened"] = Q if rows is None else int(rows.numel())
-            s2, i2, c2 = _topk_pass(qn if rows is None else qn[rows], qn32 if rows is None else qn32[rows], gn, gn32, gscale, k, kc2, T, True, **sched)
+            s2, i2, c2 = _topk_pass(qn if rows is None else _take_rows(qn, rows), qn32 if rows is None else qn32[rows], gn, gn32, gscale, k, kc2,
+                                    T, True, **sched)
             eps = torch.maximum(eps, c2[:, 0].max())
             still = c2[:, 1] < _CERT_SAFETY * eps
             if rows is None:
@@ -166,10 +235,17 @@ def cosine_topk(q, g, k, compute_dtype=torch.bfloat16, chunk=131072, exclude_sel
     return sc, idx
 
 
+def _take_rows(qn, rows):
+    return (qn[0][rows], qn[1][rows]) if isinstance(qn, tuple) else qn[rows]
+
+
 def _topk_pass(qn, qn32, gn, gn32, gscale, k, kc, T, certify, chunk=131072, exclude_self=False, fused_filter=True, merge_every=2,
                seed_cols="auto"):
     """One pass of prepared query rows over the prepared gallery: running top-kc lists per query (selection scores in T), then — with
-    qn32 / gn32 — the exact fp32 re-scoring that keeps k.  → (scores [Q,k], idx [Q,k], certificate [Q,2] or None)."""
+    qn32 / gn32 — the exact fp32 re-scoring that keeps k.  → (scores [Q,k], idx [Q,k], certificate [Q,2] or None).
+    int8 (T = torch.int8): qn and gn are (int8 rows [*, Dp], scales) pairs of quantize_rows; qn32 / gn32 keep the original D."""
+    i8 = T == torch.int8
+    (qn, qs8), (gn, gs8) = (qn, gn) if i8 else ((qn, None), (gn, None))
     Q, D = qn.shape
     G = gn.shape[0]
     rescore = qn32 is not None
@@ -179,7 +255,7 @@ def _topk_pass(qn, qn32, gn, gn32, gscale, k, kc, T, certify, chunk=131072, excl
     # Chunks after the first (every running list is full by then) use the GEMM with the top-K filter in its epilogue: the
     # fp32 score chunk is never written.  A candidate-list overflow (adversarially ordered gallery) is flagged on the
     # device and the whole match is redone on the unfused path.
-    fused = fused_filter and G > chunk and chunk >= kc + 1 and D % (64 if T == torch.bfloat16 else 32) == 0
+    fused = fused_filter and G > chunk and chunk >= kc + 1 and (i8 or D % (64 if T == torch.bfloat16 else 32) == 0)
     cap = 1536
     cand = torch.empty((Q, cap), dtype=torch.int64, device=qn.device) if fused else None
     sbuf = None
@@ -216,14 +292,21 @@ def _topk_pass(qn, qn32, gn, gn32, gscale, k, kc, T, certify, chunk=131072, excl
         pending = 0
         for si, (c0, n, seg_fused) in enumerate(segs):
             if seg_fused:
-                lib.pfr_match_scores_filter(qn.data_ptr(), gn[c0:c0 + n].data_ptr(), dtype_id(T), Q, n, D, c0, kc, state.data_ptr(),
-                                            cand.data_ptr(), cap, int(exclude_self), _stream())
+                if i8:
+                    lib.pfr_match_scores_filter_i8(qn.data_ptr(), qs8.data_ptr(), gn[c0].data_ptr(), gs8[c0].data_ptr(), Q, n, D, c0, kc,
+                                                   state.data_ptr(), cand.data_ptr(), cap, int(exclude_self), _stream())
+                else:
+                    lib.pfr_match_scores_filter(qn.data_ptr(), gn[c0:c0 + n].data_ptr(), dtype_id(T), Q, n, D, c0, kc, state.data_ptr(),
+                                                cand.data_ptr(), cap, int(exclude_self), _stream())
                 pending += 1
                 if pending >= merge_every or si + 1 == len(segs) or (seed_cols and c0 < 4 * chunk):
                     lib.pfr_topk_merge(cand.data_ptr(), cap, Q, kc, state.data_ptr(), _stream())
                     pending = 0
                 continue
-            ops.conv2d_fwd(qn.view(Q, 1, 1, D), gn[c0:c0 + n].view(n, 1, 1, D), out=sbuf)
+            if i8:
+                lib.pfr_match_scores_i8(qn.data_ptr(), qs8.data_ptr(), gn[c0].data_ptr(), gs8[c0].data_ptr(), Q, n, D, sbuf.data_ptr(), ld, _stream())
+            else:
+                ops.conv2d_fwd(qn.view(Q, 1, 1, D), gn[c0:c0 + n].view(n, 1, 1, D), out=sbuf)
             lib.pfr_topk_update(sbuf.data_ptr(), Q, ld, n, c0, kc, state.data_ptr(), 0 if self_idx is None else self_idx.data_ptr(),
                                 _stream())
         if not fused:
@@ -240,12 +323,13 @@ def _topk_pass(qn, qn32, gn, gn32, gscale, k, kc, T, certify, chunk=131072, excl
         sc2 = torch.empty((Q, k), dtype=torch.float32, device=qn.device)
         idx2 = torch.empty((Q, k), dtype=torch.int32, device=qn.device)
         gs = 0 if gscale is None else gscale.data_ptr()
+        D32 = qn32.shape[1]
         if certify:
             cert = torch.empty((Q, 2), dtype=torch.float32, device=qn.device)
-            lib.pfr_topk_rescore_cert(qn32.data_ptr(), gn32.data_ptr(), gs, Q, D, idx.data_ptr(), sc.data_ptr(), kc, k,
+            lib.pfr_topk_rescore_cert(qn32.data_ptr(), gn32.data_ptr(), gs, Q, D32, idx.data_ptr(), sc.data_ptr(), kc, k,
                                       sc2.data_ptr(), idx2.data_ptr(), cert.data_ptr(), _stream())
             return sc2, idx2, cert
-        lib.pfr_topk_rescore(qn32.data_ptr(), gn32.data_ptr(), gs, Q, D, idx.data_ptr(), kc, k, sc2.data_ptr(), idx2.data_ptr(), _stream())
+        lib.pfr_topk_rescore(qn32.data_ptr(), gn32.data_ptr(), gs, Q, D32, idx.data_ptr(), kc, k, sc2.data_ptr(), idx2.data_ptr(), _stream())
         return sc2, idx2, None
     return sc[:, :k].contiguous(), idx[:, :k].contiguous(), None
 
