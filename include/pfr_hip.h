@@ -309,6 +309,26 @@ int pfr_sgd_step(float* p, const float* g, float* mom, void* shadow, int shadow_
                  float weight_decay, float grad_scale, int first_step, pfr_stream_t stream);
 int pfr_adamw_step(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, size_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, pfr_stream_t stream);
+/* the same steps with gradient clipping folded in: g' = clamp(g * grad_scale * (*clip_coef), ±clip_value).  clip_coef is a device
+ * fp32 scalar (pfr_grad_norm's coefficient: torch.nn.utils.clip_grad_norm_'s `grads.mul_(clip_coef_clamped)`) or NULL = 1;
+ * clip_value > 0 replaces torch.nn.utils.clip_grad_value_'s `grads.clamp_(-clip_value, clip_value)`, 0 = no clamp.
+ * The gradient buffer is only read. */
+int pfr_sgd_step_clip(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
+                      float weight_decay, float grad_scale, int first_step, const float* clip_coef, float clip_value,
+                      pfr_stream_t stream);
+int pfr_adamw_step_clip(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, size_t n, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                        const float* clip_coef, float clip_value, pfr_stream_t stream);
+/* gradient norm over nseg dense fp32 segments (one per parameter), replacing torch.nn.utils.clip_grad_norm_'s
+ * `torch._foreach_norm(grads, p)` + `vector_norm(stack(norms), p)` + clip coefficient, and PL's per-parameter grad_norm().
+ * segs: device table [nseg] of {const float* ptr; int64 n; int64 first_chunk; int64 chunks} with chunks = ceil(n / chunk_elems),
+ * chunk_elems = pfr_grad_norm_chunk_elems(), first chunks consecutive; chunk_seg: device int32 [nchunks] = segment of each chunk.
+ * norm_p > 0: 1, 2, INFINITY, or any other p ((sum |x|^p)^(1/p), torch.linalg.vector_norm's ord).  ws: fp64 workspace
+ * [nchunks + nseg].  out fp32 [nseg + 2]: the segment norms, the total over them, then min(1, max_norm / (total + 1e-6)).
+ * Two launches, no atomics: bitwise reproducible; NaN / inf propagate as in torch. */
+int pfr_grad_norm_chunk_elems(void);
+int pfr_grad_norm(const void* segs, const int* chunk_seg, int nseg, long nchunks, float norm_p, float max_norm, double* ws,
+                  float* out, pfr_stream_t stream);
 
 /* ---- Swin-T feature extractor (models/swin.py:8-241): LayerNorm (29,215), exact GELU (39-43), fused shifted-window
  * attention (101-135).  Linear layers and the Unfold+Linear patch merging (a stride-f conv) use pfr_conv2d_*. */

@@ -305,3 +305,27 @@ def adamw_step(p, g, m, v, shadow, lr, beta1, beta2, eps, weight_decay, step, gr
     lib.pfr_adamw_step(_p(p), _p(g), _p(m), _p(v), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),
                        float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step), float(grad_scale),
                        _stream())
+
+
+def sgd_step_clip(p, g, mom, shadow, lr, momentum, weight_decay, clip_coef, clip_value, grad_scale=1.0, first_step=False):
+    """sgd_step on clamp(g * grad_scale * clip_coef, ±clip_value): clip_coef a 1-element fp32 CUDA tensor or None, clip_value 0 = no clamp"""
+    lib.pfr_sgd_step_clip(_p(p), _p(g), _p(mom), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),
+                          float(lr), float(momentum), float(weight_decay), float(grad_scale), int(first_step), _p(clip_coef),
+                          float(clip_value), _stream())
+
+
+def adamw_step_clip(p, g, m, v, shadow, lr, beta1, beta2, eps, weight_decay, step, clip_coef, clip_value, grad_scale=1.0):
+    lib.pfr_adamw_step_clip(_p(p), _p(g), _p(m), _p(v), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype),
+                            p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+                            float(grad_scale), _p(clip_coef), float(clip_value), _stream())
+
+
+def grad_norm(segs, chunk_seg, nseg, nchunks, norm_p, max_norm, ws, out):
+    """pfr_grad_norm: segs / chunk_seg = the device tables of optim.fused.SegmentNorm, norm_p > 0 (math.inf: max norm),
+    ws fp64 [nchunks + nseg], out fp32 [nseg + 2] (segment norms, total, clip coefficient)"""
+    assert ws.dtype == torch.float64 and ws.numel() >= nchunks + nseg and out.dtype == torch.float32 and out.numel() >= nseg + 2
+    lib.pfr_grad_norm(_p(segs), _p(chunk_seg), int(nseg), int(nchunks), float(norm_p), float(max_norm), _p(ws), _p(out), _stream())
+
+
+def grad_norm_chunk_elems():
+    return lib.pfr_grad_norm_chunk_elems()

@@ -31,7 +31,7 @@ def _live(key, default):
 
 def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs, device, n_epochs=1, seed=0,
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
-         noise_bank=0, limit_val_batches=None):
+         noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None):
     torch.manual_seed(seed)
     dataset = SyntheticRecDataset(n_train_ids + n_val_ids, photos, image_size, seed=seed, noise=noise, raw_uint8=device_augment,
                                   noise_bank=noise_bank)
@@ -103,6 +103,13 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         ns['device_train_augmentation'] = DeviceAugmentation((image_size - 4, image_size - 4), (image_size, image_size), 0.1, 0.3,
                                                              5.0, torch.Generator().manual_seed(seed + _rank()))
         ns['device_val_augmentation'] = val_augmentation()
+    # the reference's commented-out `gradient_clip_val=1, gradient_clip_algorithm='norm'` trainer_kwargs (fe_dogs_config.py:146-147):
+    # passed on only when set, so that the other configs build exactly the trainer they did
+    clip_kwargs = {}
+    if gradient_clip_val is not None:
+        clip_kwargs['gradient_clip_val'] = gradient_clip_val
+    if gradient_clip_algorithm is not None:
+        clip_kwargs['gradient_clip_algorithm'] = gradient_clip_algorithm
     output = Path('results')
     output.mkdir(exist_ok=True)
     ns.update(dict(
@@ -110,7 +117,8 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         thrs=np.linspace(0.5, 0.99, 6), far_thr=[0.1, 0.05, 0.03, 0.01, 0.005, 0.001], k=[5, 10, 100],
         pair_generator=pair_generator, similarity_f=similarity_f, model=model, loss=loss, optimizer=optimizer,
         train_dataloader=train_dataloader, val_dataloader=val_dataloader,
-        trainer_kwargs=dict(benchmark=True, limit_train_batches=limit_train_batches, limit_val_batches=limit_val_batches),
+        trainer_kwargs=dict(benchmark=True, limit_train_batches=limit_train_batches, limit_val_batches=limit_val_batches,
+                            **clip_kwargs),
         output=output, experiment_name='Synthetic', run_name=f'{arch} synthetic',
         device=device, distributed_train=not isinstance(device, str),
         world_size=len(device) if not isinstance(device, str) else None))

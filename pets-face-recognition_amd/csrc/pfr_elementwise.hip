@@ -1647,13 +1647,190 @@ extern "C" int pfr_colsum_final_batch(const void* descs, int n, int max_C, hipSt
 }
 
 // ------------------------------------------------------------------------------------------------
+// gradient norm over a list of dense fp32 segments, one per parameter (torch.nn.utils.clip_grad_norm_, PL's grad_norm).
+// Launch 1: one workgroup per fixed chunk of GN_CHUNK elements of one segment, one fp64 partial per chunk (plain store).
+// Launch 2: one workgroup sums every segment's partials in chunk order, then writes the segment norms, the total over them
+// and the clip coefficient.  Stream order is the only synchronisation (no atomics, no arrival counter): bitwise reproducible.
+// fp64 from the first product on: a 31 M-element sum stays far inside 1e-6 of an exact one.  NaN / inf are not masked.
+struct GradNormSeg {
+  const float* p;       // first element of the segment (any 4-byte alignment)
+  long long n;          // elements
+  long long chunk0;     // index of its first chunk in the partial array
+  long long nchunk;     // ceil(n / GN_CHUNK)
+};
+constexpr int GN_THREADS = 256;
+constexpr int GN_VEC = 16;                               // f32x4 loads per lane per chunk, all in flight together
+constexpr int GN_CHUNK = GN_THREADS * 4 * GN_VEC;        // 16 384 elements = 64 KiB per workgroup
+constexpr int GN_FIN_THREADS = 1024;
+constexpr int GN_TILE = 4096;                            // partials per LDS tile of the finalize (32 KiB)
+
+// P = 2: sum of squares, P = 1: sum of magnitudes, P = 0: max magnitude, P = 3: sum of |x|^pw for any other pw > 0
+// (torch's general vector norm (sum |x|^p)^(1/p))
+template <int P>
+__device__ __forceinline__ double gn_term(float x, double pw) {
+  const double a = fabs((double)x);
+  if constexpr (P == 3) return pow(a, pw);
+  else return P == 2 ? a * a : a;
+}
+template <int P>
+__device__ __forceinline__ double gn_comb(double a, double b) {
+  if constexpr (P == 0) return (b > a || b != b) ? b : a;   // max that keeps a NaN (fmax would drop it)
+  else return a + b;
+}
+template <int P>
+__device__ __forceinline__ double gn_root(double v, double pw) {
+  if constexpr (P == 2) return sqrt(v);
+  else if constexpr (P == 3) return pow(v, 1.0 / pw);
+  else return v;
+}
+template <int P>
+__device__ __forceinline__ double gn_wave(double v) {   // fixed butterfly: every lane's order is fixed
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = gn_comb<P>(v, __shfl_xor(v, o));
+  return v;
+}
+
+template <int P>
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_chunk_kernel(const GradNormSeg* __restrict__ segs,
+                                                                     const int* __restrict__ chunk_seg,
+                                                                     double* __restrict__ partial, double pw) {
+  const int chunk = blockIdx.x, t = threadIdx.x;
+  const GradNormSeg s = segs[chunk_seg[chunk]];
+  const long long lo = (long long)(chunk - s.chunk0) * GN_CHUNK;
+  const int len = (int)min((long long)GN_CHUNK, s.n - lo);
+  const float* x = s.p + lo;
+  double acc = 0.0;
+  if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+    const int nv = len >> 2;
+    if (nv > 0) {
+      const f32x4* xv = reinterpret_cast<const f32x4*>(x);
+      f32x4 q[GN_VEC];
+#pragma unroll
+      for (int k = 0; k < GN_VEC; ++k) q[k] = xv[min(t + k * GN_THREADS, nv - 1)];   // clamped: all loads issued at once
+#pragma unroll
+      for (int k = 0; k < GN_VEC; ++k)
+        if (t + k * GN_THREADS < nv)
+          acc = gn_comb<P>(acc, gn_comb<P>(gn_comb<P>(gn_term<P>(q[k][0], pw), gn_term<P>(q[k][1], pw)),
+                                           gn_comb<P>(gn_term<P>(q[k][2], pw), gn_term<P>(q[k][3], pw))));
+    }
+    if (t < (len & 3)) acc = gn_comb<P>(acc, gn_term<P>(x[4 * nv + t], pw));
+  } else {   // a start that is not 16-byte aligned: coalesced 4-byte loads
+    for (int i = t; i < len; i += GN_THREADS) acc = gn_comb<P>(acc, gn_term<P>(x[i], pw));
+  }
+  acc = gn_wave<P>(acc);
+  __shared__ double w[GN_THREADS / 64];
+  if ((t & 63) == 0) w[t >> 6] = acc;
+  __syncthreads();
+  if (t == 0) partial[chunk] = gn_comb<P>(gn_comb<P>(w[0], w[1]), gn_comb<P>(w[2], w[3]));
+}
+
+template <int P>
+__global__ __launch_bounds__(GN_FIN_THREADS) void grad_norm_final_kernel(const GradNormSeg* __restrict__ segs,
+                                                                         const int* __restrict__ chunk_seg, int nseg,
+                                                                         long long nchunks, float max_norm, double pw,
+                                                                         const double* __restrict__ partial,
+                                                                         double* __restrict__ segacc, float* __restrict__ out) {
+  constexpr int NW = GN_FIN_THREADS / 64;
+  __shared__ double tile[GN_TILE];
+  __shared__ double red[NW];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  // the partials in tiles of GN_TILE chunks, one wave per segment.  A wave fetches the chunk ranges of its next 64 segments
+  // together (one load per lane, handed out by shuffles), so its walk over the segments waits on no global load.  A segment's
+  // first tile stores its sum, a later tile (a segment that spans tiles) adds to it: tile order, fixed.
+  for (long long c0 = 0; c0 < nchunks; c0 += GN_TILE) {
+    const int nt = (int)min((long long)GN_TILE, nchunks - c0);
+    for (int i = t; i < nt; i += GN_FIN_THREADS) tile[i] = partial[c0 + i];
+    __syncthreads();
+    const int s_lo = chunk_seg[c0], s_hi = chunk_seg[c0 + nt - 1];
+    for (int sb = s_lo + wv; sb <= s_hi; sb += NW * 64) {
+      const int sj = sb + NW * lane;
+      long long ca = 0, cn = 0;
+      if (sj <= s_hi) {
+        ca = segs[sj].chunk0;
+        cn = segs[sj].nchunk;
+      }
+      for (int j = 0; j < 64; ++j) {
+        const int s = sb + NW * j;
+        if (s > s_hi) break;   // (wave-uniform)
+        const long long d0 = __shfl(ca, j), dn = __shfl(cn, j);
+        const long long a = max(d0, c0), b = min(d0 + dn, c0 + nt);
+        double acc = 0.0;
+        for (long long i = a + lane; i < b; i += 64) acc = gn_comb<P>(acc, tile[i - c0]);
+        acc = gn_wave<P>(acc);
+        if (lane == 0) segacc[s] = d0 < c0 ? gn_comb<P>(segacc[s], acc) : acc;
+      }
+    }
+    __threadfence();
+    __syncthreads();
+  }
+  // fp32 segment norms (torch's per-tensor norms), then the total over them as torch stacks and norms them
+  double tot = 0.0;
+  for (int s = t; s < nseg; s += GN_FIN_THREADS) {
+    const double v = segs[s].nchunk > 0 ? segacc[s] : 0.0;   // (an empty segment has no chunk and no stored sum)
+    const float nf = (float)gn_root<P>(v, pw);
+    out[s] = nf;
+    tot = gn_comb<P>(tot, gn_term<P>(nf, pw));
+  }
+  tot = gn_wave<P>(tot);
+  if (lane == 0) red[wv] = tot;
+  __syncthreads();
+  if (t == 0) {
+    double a = 0.0;
+    for (int k = 0; k < NW; ++k) a = gn_comb<P>(a, red[k]);
+    const float total = (float)gn_root<P>(a, pw);
+    float coef = max_norm / (total + 1e-6f);
+    coef = coef > 1.f ? 1.f : coef;   // torch.clamp(max=1.0) keeps a NaN; an inf total gives 0
+    out[nseg] = total;
+    out[nseg + 1] = coef;
+  }
+}
+
+extern "C" int pfr_grad_norm_chunk_elems(void) { return GN_CHUNK; }
+
+template <int P>
+static void launch_grad_norm(const GradNormSeg* segs, const int* chunk_seg, int nseg, long nchunks, double pw, float max_norm,
+                             double* ws, float* out, hipStream_t st) {
+  if (nchunks > 0)
+    hipLaunchKernelGGL(grad_norm_chunk_kernel<P>, dim3((unsigned)nchunks), dim3(GN_THREADS), 0, st, segs, chunk_seg, ws, pw);
+  hipLaunchKernelGGL(grad_norm_final_kernel<P>, dim3(1), dim3(GN_FIN_THREADS), 0, st, segs, chunk_seg, nseg, (long long)nchunks,
+                     max_norm, pw, (const double*)ws, ws + nchunks, out);
+}
+extern "C" int pfr_grad_norm(const void* segs, const int* chunk_seg, int nseg, long nchunks, float norm_p, float max_norm,
+                             double* ws, float* out, hipStream_t st) {
+  PFR_CHECK_ARG(segs && ws && out && nseg > 0 && nchunks >= 0 && (nchunks == 0 || chunk_seg), "pfr_grad_norm: bad args");
+  PFR_CHECK_ARG(nchunks < (1L << 31), "pfr_grad_norm: too many chunks");
+  PFR_CHECK_ARG(norm_p > 0.f, "pfr_grad_norm: norm_p must be > 0 (inf for the max norm)");
+  const GradNormSeg* sg = (const GradNormSeg*)segs;
+  if (norm_p == 2.f) launch_grad_norm<2>(sg, chunk_seg, nseg, nchunks, 2.0, max_norm, ws, out, st);
+  else if (norm_p == 1.f) launch_grad_norm<1>(sg, chunk_seg, nseg, nchunks, 1.0, max_norm, ws, out, st);
+  else if (__builtin_isinf(norm_p)) launch_grad_norm<0>(sg, chunk_seg, nseg, nchunks, 0.0, max_norm, ws, out, st);
+  else launch_grad_norm<3>(sg, chunk_seg, nseg, nchunks, (double)norm_p, max_norm, ws, out, st);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // optimiser steps over flat fp32 master buffers (+ compute-dtype shadow copy of the parameters)
 // four parameters per thread (16-byte loads of p / g / momentum issued together, one 8- or 16-byte shadow store): the scalar version
 // made three dependent 4-byte round trips per parameter
-template <typename TS>
+// CLIP: the gradient is multiplied by *coef after gscale (clip_grad_norm_'s coefficient, NULL = 1) and clamped to ±clipv (clipv > 0:
+// clip_grad_value_); the CLIP = false instantiation is the plain step (pfr_sgd_step / pfr_adamw_step launch exactly that)
+template <bool CLIP>
+__device__ __forceinline__ float clip_grad(float gv, float c, float clipv) {
+  if constexpr (CLIP) {
+    gv *= c;
+    // comparisons, not fminf / fmaxf: a NaN gradient stays NaN as under torch.clamp
+    if (clipv > 0.f) gv = gv > clipv ? clipv : (gv < -clipv ? -clipv : gv);
+  }
+  return gv;
+}
+
+template <typename TS, bool CLIP = false>
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mom, TS* __restrict__ shadow,
-                           size_t n, float lr, float momentum, float wd, float gscale, int first) {
+                           size_t n, float lr, float momentum, float wd, float gscale, int first, const float* __restrict__ coef,
+                           float clipv) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const float c = CLIP && coef ? *coef : 1.f;
   const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(mom) |
                      reinterpret_cast<uintptr_t>(shadow)) & 15) == 0;
   const size_t n4 = vec ? n / 4 : 0;
@@ -1666,7 +1843,7 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
     f32x4 b;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float d = fmaf(wd, w[e], gr[e] * gscale);
+      const float d = fmaf(wd, w[e], clip_grad<CLIP>(gr[e] * gscale, c, clipv));
       b[e] = use_mom ? (first ? d : fmaf(momentum, m[e], d)) : d;
       w[e] = fmaf(-lr, b[e], w[e]);
     }
@@ -1685,7 +1862,7 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
   }
   for (size_t i = 4 * n4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float w = p[i];
-    float d = fmaf(wd, w, g[i] * gscale);
+    float d = fmaf(wd, w, clip_grad<CLIP>(g[i] * gscale, c, clipv));
     float b = d;
     if (momentum != 0.f) {
       b = first ? d : fmaf(momentum, mom[i], d);
@@ -1703,22 +1880,42 @@ extern "C" int pfr_sgd_step(float* p, const float* g, float* mom, void* shadow, 
   unsigned blocks = (unsigned)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   if (shadow && shadow_dtype == PFR_BF16)
-    hipLaunchKernelGGL(sgd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, p, g, mom, (bf16_t*)shadow, n, lr, momentum, weight_decay, grad_scale, first_step);
+    hipLaunchKernelGGL(sgd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, p, g, mom, (bf16_t*)shadow, n, lr, momentum, weight_decay, grad_scale, first_step,
+                       (const float*)nullptr, 0.f);
   else
-    hipLaunchKernelGGL(sgd_kernel<float>, dim3(blocks), dim3(256), 0, st, p, g, mom, (float*)shadow, n, lr, momentum, weight_decay, grad_scale, first_step);
+    hipLaunchKernelGGL(sgd_kernel<float>, dim3(blocks), dim3(256), 0, st, p, g, mom, (float*)shadow, n, lr, momentum, weight_decay, grad_scale, first_step,
+                       (const float*)nullptr, 0.f);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+extern "C" int pfr_sgd_step_clip(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr,
+                                 float momentum, float weight_decay, float grad_scale, int first_step, const float* clip_coef,
+                                 float clip_value, hipStream_t st) {
+  PFR_CHECK_ARG(p && g && (momentum == 0.f || mom), "pfr_sgd_step_clip: null pointer");
+  PFR_CHECK_ARG(clip_value >= 0.f, "pfr_sgd_step_clip: clip_value must be >= 0 (0 = no clamp)");
+  if (n == 0) return PFR_OK;
+  unsigned blocks = (unsigned)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  if (shadow && shadow_dtype == PFR_BF16)
+    hipLaunchKernelGGL((sgd_kernel<bf16_t, true>), dim3(blocks), dim3(256), 0, st, p, g, mom, (bf16_t*)shadow, n, lr, momentum, weight_decay, grad_scale,
+                       first_step, clip_coef, clip_value);
+  else
+    hipLaunchKernelGGL((sgd_kernel<float, true>), dim3(blocks), dim3(256), 0, st, p, g, mom, (float*)shadow, n, lr, momentum, weight_decay, grad_scale,
+                       first_step, clip_coef, clip_value);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }
 
-template <typename TS>
+template <typename TS, bool CLIP = false>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                              TS* __restrict__ shadow, size_t n, float lr, float b1, float b2, float eps, float wd,
-                             float bc1, float bc2, float gscale) {
+                             float bc1, float bc2, float gscale, const float* __restrict__ coef, float clipv) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const float c = CLIP && coef ? *coef : 1.f;
   for (; i < n; i += stride) {
     float w = p[i];
-    const float gr = g[i] * gscale;
+    const float gr = clip_grad<CLIP>(g[i] * gscale, c, clipv);
     w *= 1.f - lr * wd;
     const float mm = b1 * m[i] + (1.f - b1) * gr;
     const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
@@ -1739,9 +1936,29 @@ extern "C" int pfr_adamw_step(float* p, const float* g, float* m, float* v, void
   unsigned blocks = (unsigned)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   if (shadow && shadow_dtype == PFR_BF16)
-    hipLaunchKernelGGL(adamw_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, p, g, m, v, (bf16_t*)shadow, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale);
+    hipLaunchKernelGGL(adamw_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, p, g, m, v, (bf16_t*)shadow, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale,
+                       (const float*)nullptr, 0.f);
   else
-    hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(256), 0, st, p, g, m, v, (float*)shadow, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale);
+    hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(256), 0, st, p, g, m, v, (float*)shadow, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale,
+                       (const float*)nullptr, 0.f);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+extern "C" int pfr_adamw_step_clip(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, size_t n,
+                                   float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                   const float* clip_coef, float clip_value, hipStream_t st) {
+  PFR_CHECK_ARG(p && g && m && v && step >= 1, "pfr_adamw_step_clip: bad args");
+  PFR_CHECK_ARG(clip_value >= 0.f, "pfr_adamw_step_clip: clip_value must be >= 0 (0 = no clamp)");
+  if (n == 0) return PFR_OK;
+  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+  unsigned blocks = (unsigned)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  if (shadow && shadow_dtype == PFR_BF16)
+    hipLaunchKernelGGL((adamw_kernel<bf16_t, true>), dim3(blocks), dim3(256), 0, st, p, g, m, v, (bf16_t*)shadow, n, lr, beta1, beta2, eps, weight_decay, bc1,
+                       bc2, grad_scale, clip_coef, clip_value);
+  else
+    hipLaunchKernelGGL((adamw_kernel<float, true>), dim3(blocks), dim3(256), 0, st, p, g, m, v, (float*)shadow, n, lr, beta1, beta2, eps, weight_decay, bc1,
+                       bc2, grad_scale, clip_coef, clip_value);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }

@@ -9,6 +9,8 @@ step (loops/train_loop.py:13-38); evaluation outputs are handed over as List[dat
 (trainer.py:105,110,118); one checkpoint (bare state_dict, reference key names) per epoch plus a `.trainer` sidecar
 (epoch, global_step, optimizer_states, lr_schedulers — PL's checkpoint keys) that `resume_from_checkpoint=` /
 `fit(ckpt_path=)` restart from (trainer.py:111,399; a PL-format checkpoint holding the same keys is read too).
+`gradient_clip_val` / `gradient_clip_algorithm` / `track_grad_norm` as in PL 1.5 (trainer.py:73-74,87,481-505), in the order of
+its OptimizerLoop._track_and_norm_grad: backward -> gradient all-reduce -> track -> clip -> optimizer.step.
 
 Distributed = one process per GPU started by torchrun (RANK / LOCAL_RANK / WORLD_SIZE), RCCL all-reduce of the flat
 gradient buffer in buckets overlapped with backward (engine/ddp.py)."""
@@ -43,7 +45,24 @@ class Trainer:
     def __init__(self, gpus=0, default_root_dir=None, strategy=None, max_epochs=1, logger=False, enable_checkpointing=False,
                  callbacks=None, num_sanity_val_steps=0, limit_train_batches=None, limit_val_batches=None,
                  check_val_every_n_epoch=1, log_every_n_steps=50, benchmark=None, fast_dev_run=False, prefetch_batches=2,
-                 resume_from_checkpoint=None, resume_weights_only=False, **_ignored):
+                 resume_from_checkpoint=None, resume_weights_only=False, gradient_clip_val=None, gradient_clip_algorithm=None,
+                 track_grad_norm=-1, **_ignored):
+        # PL 1.5's checks (reference engine/trainer.py:481-505; its MisconfigurationException is a ValueError here)
+        if gradient_clip_val is not None and not isinstance(gradient_clip_val, (int, float)):
+            raise TypeError(f"`gradient_clip_val` should be an int or a float. Got {gradient_clip_val}.")
+        if gradient_clip_algorithm is not None:
+            if not isinstance(gradient_clip_algorithm, str):
+                raise TypeError(f"`gradient_clip_algorithm` should be a str. Got {gradient_clip_algorithm}.")
+            if gradient_clip_algorithm.lower() not in ('norm', 'value'):
+                raise ValueError(f"`gradient_clip_algorithm` {gradient_clip_algorithm} is invalid. Allowed algorithms: ['value', 'norm'].")
+        if track_grad_norm != -1 and not ((isinstance(track_grad_norm, (int, float)) or track_grad_norm == 'inf')
+                                          and float(track_grad_norm) > 0):
+            raise ValueError(f"`track_grad_norm` must be a positive number or 'inf' (infinity norm). Got {track_grad_norm}.")
+        self.gradient_clip_val = gradient_clip_val
+        self.gradient_clip_algorithm = 'norm' if gradient_clip_algorithm is None else gradient_clip_algorithm.lower()
+        self.track_grad_norm = float(track_grad_norm)
+        self.grad_norm_history = []   # the grad_norm dictionaries of the logging steps of the last fit()
+        self._track_norm = None       # optim.fused.SegmentNorm of the tracked gradients (CUDA)
         self.gpus, self.root, self.strategy = gpus, default_root_dir, strategy
         self.max_epochs = 1 if fast_dev_run else max_epochs
         self.logger = logger if logger else None
@@ -173,6 +192,7 @@ class Trainer:
                           else ([opt], []))
         optim = optims[0]
         history = []
+        gn_history = []
         first_epoch = 0
         ckpt_path = ckpt_path or self.resume_from_checkpoint
         if ckpt_path is not None:
@@ -201,6 +221,12 @@ class Trainer:
                 loss.backward()
                 if self.ddp is not None:
                     self.ddp.finish_backward()
+                if self.track_grad_norm > 0 and (self.global_step + 1) % self.log_every_n_steps == 0:
+                    norms = self._grad_norm_dict(controller)
+                    gn_history.append(norms)
+                    if norms and self.logger is not None and self.rank == 0 and hasattr(self.logger, 'log_metrics'):
+                        self.logger.log_metrics(norms, step=self.global_step)
+                self._clip_gradients(optim)
                 optim.step()
                 self.global_step += 1
                 if self.global_step % self.log_every_n_steps == 0 or bi == 0:
@@ -224,7 +250,50 @@ class Trainer:
             if self.enable_checkpointing and self.root is not None and self.rank == 0:
                 self._save_checkpoint(controller, optims, scheds, epoch)
         self.loss_history = history
+        self.grad_norm_history = gn_history
         return controller
+
+    # ------------------------------------------------------------------ gradient clipping / norm tracking
+    def _clip_gradients(self, optim):
+        """PL 1.5 clip_gradients over the optimizer's own parameters (PL's main_params(optimizer)); a value <= 0 / None: no clipping.
+        A fused optimizer folds the clip into its next step (device norm, no host sync); any other optimizer goes through
+        torch.nn.utils."""
+        clip_val = self.gradient_clip_val
+        if clip_val is None or float(clip_val) <= 0:
+            return
+        clip_val = float(clip_val)
+        from ..optim.fused import _FusedBase
+        if isinstance(optim, _FusedBase):
+            if self.gradient_clip_algorithm == 'value':
+                optim.clip_grad_value_(clip_val)
+            else:
+                optim.clip_grad_norm_(clip_val, 2.0)
+            return
+        params = [p for group in optim.param_groups for p in group['params']]
+        if self.gradient_clip_algorithm == 'value':
+            torch.nn.utils.clip_grad_value_(params, clip_val)
+        else:
+            torch.nn.utils.clip_grad_norm_(params, clip_val)
+
+    def _grad_norm_dict(self, controller):
+        """PL 1.5's grad_norm(lightning_module, track_grad_norm): {'grad_{p}_norm_{name}': norm} over the parameters with a gradient,
+        plus 'grad_{p}_norm_total', rounded to 4 digits.  CUDA gradients: one pfr_grad_norm call and one device-to-host copy
+        (PL syncs once per parameter)."""
+        p = self.track_grad_norm
+        named = [(n, q.grad) for n, q in controller.named_parameters() if q.grad is not None]
+        if not named:
+            return {}
+        if named[0][1].is_cuda:
+            from ..optim.fused import SegmentNorm
+            if self._track_norm is None:
+                self._track_norm = SegmentNorm()
+            vals = self._track_norm.compute([g for _, g in named], p, copy_other=True).cpu().tolist()
+            norms = {f'grad_{p}_norm_{n}': v for (n, _), v in zip(named, vals)}
+            norms[f'grad_{p}_norm_total'] = vals[len(named)]
+        else:
+            norms = {f'grad_{p}_norm_{n}': g.norm(p).item() for n, g in named}
+            norms[f'grad_{p}_norm_total'] = torch.tensor(list(norms.values())).norm(p).item()
+        return {k: round(v, 4) for k, v in norms.items()}
 
     def _run_eval(self, controller, device, kind):
         if self.ddp is not None:

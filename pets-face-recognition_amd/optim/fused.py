@@ -1,7 +1,13 @@
 """Flat-buffer fused optimizers with the torch.optim interface (param_groups / step / zero_grad / state_dict), so the
 config contract `optimizer(model_) -> ([optim], [sched])` (/root/reference/configs/dog_fe/fe_dogs_config.py:123-133,
 body_dog_fe.py:121-131) and torch LR schedulers keep working.  Parameters that live in an FEEngine flat buffer are
-updated with ONE kernel launch per contiguous range of a param group; any other CUDA parameter gets one launch."""
+updated with ONE kernel launch per contiguous range of a param group; any other CUDA parameter gets one launch.
+
+Gradient clipping (`clip_grad_norm_` / `clip_grad_value_`, torch.nn.utils' argument conventions) is folded into the next
+`step()`: the norm is reduced on the device (pfr_grad_norm) and the update kernels read its clip coefficient from device
+memory, so there is no host sync and no extra pass that rewrites the gradients.  The gradients themselves are NOT scaled in
+place; only the update uses the clipped values (PL steps right after clipping and zeroes the gradients before the next
+backward, so a trainer cannot tell the difference)."""
 import torch
 
 from .._hip import ops, PfrError
@@ -16,6 +22,38 @@ class _FusedBase(torch.optim.Optimizer):
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._runs = {}      # group index -> (signature, [run, ...])
+        self._clip_coef = None     # armed by clip_grad_norm_: 1-element device tensor, consumed by the next step()
+        self._clip_value = 0.0     # armed by clip_grad_value_ (0 = off), consumed by the next step()
+        self._norm = SegmentNorm()
+
+    def _grads(self):
+        return [p.grad for group in self.param_groups for p in group["params"] if p.grad is not None]
+
+    @torch.no_grad()
+    def clip_grad_norm_(self, max_norm, norm_type=2.0):
+        """torch.nn.utils.clip_grad_norm_ over every gradient of every param group: returns the total norm as a 0-d device tensor
+        (no host sync) and arms its clip coefficient min(1, max_norm / (total + 1e-6)) for the next step().  norm_type 1, 2 or
+        inf (any other p > 0 too).  The gradients are not modified; the next step() uses them scaled by the coefficient."""
+        grads = self._grads()
+        if not grads:
+            return torch.tensor(0.0)
+        out = self._norm.compute(grads, norm_type, max_norm)
+        self._clip_coef = out[len(grads) + 1:]
+        return out[len(grads)]
+
+    def clip_grad_value_(self, clip_value):
+        """torch.nn.utils.clip_grad_value_: the next step() uses every gradient clamped to [-clip_value, clip_value] (the
+        gradients themselves are not modified).  clip_value must be > 0."""
+        clip_value = float(clip_value)
+        if not clip_value > 0:
+            raise ValueError(f"clip_value must be > 0, got {clip_value}")
+        self._clip_value = clip_value
+
+    def _take_clip(self):
+        """-> (coefficient tensor or None, clamp value or 0.0) armed for this step, and disarms them"""
+        armed = (self._clip_coef, self._clip_value)
+        self._clip_coef, self._clip_value = None, 0.0
+        return armed
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -131,6 +169,62 @@ class _FusedBase(torch.optim.Optimizer):
         return (t.data_ptr(), n)
 
 
+def norm_order(norm_type):
+    """torch norm_type -> pfr_grad_norm's norm_p: any p > 0, math.inf for the max norm"""
+    p = float(norm_type)
+    if not p > 0:
+        raise PfrError(f"the device gradient norm needs norm_type > 0 (or inf), got {norm_type}")
+    return p
+
+
+class SegmentNorm:
+    """Norms of a list of dense fp32 CUDA gradients on the device: one pfr_grad_norm call (two launches), no host sync.  Each
+    gradient is one segment, so alignment padding between parameters of a flat buffer never enters.  The descriptor tables of
+    the last layout seen are kept and rebuilt when a gradient moves.  compute(..., copy_other=True) also takes gradients of
+    another dtype or a strided layout, as a contiguous fp32 copy (what the norm reads is the same values)."""
+
+    def __init__(self):
+        self._key = None
+
+    def _tables(self, grads):
+        key = tuple((g.data_ptr(), g.numel()) for g in grads)
+        if key == self._key:
+            return
+        dev = grads[0].device
+        ce = ops.grad_norm_chunk_elems()
+        rows, chunk_seg, c0 = [], [], 0
+        for i, g in enumerate(grads):
+            if g.dtype != torch.float32 or not g.is_cuda or g.device != dev:
+                raise PfrError("the device gradient norm needs fp32 CUDA gradients on one device")
+            span = _FusedBase._storage_span(g)
+            if span is None and g.numel() > 0:
+                raise PfrError("the device gradient norm needs gradients that are dense in memory")
+            n = g.numel()
+            nch = -(-n // ce)
+            rows.append((span[0] if n else 0, n, c0, nch))
+            chunk_seg += [i] * nch
+            c0 += nch
+        # (pinned + non_blocking: no host sync; the caching host allocator keeps the staging buffers alive until the copies ran)
+        self._segs = torch.tensor(rows, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        self._chunk_seg = torch.tensor(chunk_seg or [0], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        self._ws = torch.empty(c0 + len(grads), dtype=torch.float64, device=dev)
+        self._nchunks = c0
+        self._key = key
+
+    def compute(self, grads, norm_type=2.0, max_norm=1.0, copy_other=False):
+        """-> fp32 device tensor [len(grads) + 2]: every gradient's norm, the total norm (torch's norm of the stacked per-tensor
+        norms), then the clip coefficient min(1, max_norm / (total + 1e-6))"""
+        p = norm_order(norm_type)
+        if copy_other:
+            # (a copy is freed when this call returns; the caching allocator hands its memory only to work queued after the norm)
+            grads = [g if g.dtype == torch.float32 and _FusedBase._storage_span(g) is not None
+                     else g.detach().float().contiguous() for g in grads]
+        self._tables(grads)
+        out = torch.empty(len(grads) + 2, dtype=torch.float32, device=grads[0].device)
+        ops.grad_norm(self._segs, self._chunk_seg, len(grads), self._nchunks, p, max_norm, self._ws, out)
+        return out
+
+
 class FusedSGD(_FusedBase):
     _STATE_KEYS = ("momentum_buffer",)
 
@@ -142,11 +236,17 @@ class FusedSGD(_FusedBase):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        coef, clip_value = self._take_clip()
+        clip = coef is not None or clip_value > 0
         for gi, group in enumerate(self.param_groups):
             for r in self._group_runs(gi, group):
                 # a zero-initialised buffer makes torch's "first step: buf = d" the general rule buf = momentum*buf + d
                 buf = r["state"]["momentum_buffer"] if group["momentum"] != 0 else None
-                ops.sgd_step(r["pf"], r["gf"], buf, None, group["lr"], group["momentum"], group["weight_decay"], first_step=False)
+                if clip:
+                    ops.sgd_step_clip(r["pf"], r["gf"], buf, None, group["lr"], group["momentum"], group["weight_decay"], coef,
+                                      clip_value, first_step=False)
+                else:
+                    ops.sgd_step(r["pf"], r["gf"], buf, None, group["lr"], group["momentum"], group["weight_decay"], first_step=False)
         return loss
 
 
@@ -173,8 +273,15 @@ class FusedAdamW(_FusedBase):
     def step(self, closure=None):
         loss = closure() if closure is not None else None
         self._t += 1
+        coef, clip_value = self._take_clip()
+        clip = coef is not None or clip_value > 0
         for gi, group in enumerate(self.param_groups):
             for r in self._group_runs(gi, group):
-                ops.adamw_step(r["pf"], r["gf"], r["state"]["exp_avg"], r["state"]["exp_avg_sq"], None, group["lr"],
-                               group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"], self._t)
+                if clip:
+                    ops.adamw_step_clip(r["pf"], r["gf"], r["state"]["exp_avg"], r["state"]["exp_avg_sq"], None, group["lr"],
+                                        group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"], self._t, coef,
+                                        clip_value)
+                else:
+                    ops.adamw_step(r["pf"], r["gf"], r["state"]["exp_avg"], r["state"]["exp_avg_sq"], None, group["lr"],
+                                   group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"], self._t)
         return loss
