@@ -303,6 +303,27 @@ int pfr_margin_ce(const float* cosv, const int64_t* label, int B, int C, int ldc
 int pfr_margin_bwd(const float* cosv, const int64_t* label, int B, int C, int ldc, int mode, float s, float m,
                    const float* dlogits, void* dcos, int dcos_dtype, pfr_stream_t stream);
 int pfr_mean(const float* x, float* out, int n, pfr_stream_t stream);
+/* pfr_margin_ce with the rest of `loss_kwargs` (losses/__init__.py:28-33) in the same single row kernel; all options off = pfr_margin_ce.
+ *   alpha [C] fp32 or NULL: FocalLoss(alpha=True)'s `input = self.alpha * input` (losses/losses.py:23): the criterion runs on
+ *     z = alpha * l (row maximum taken over z); `logits` stay the margin output l; dcos carries d loss / d l = alpha * dz.
+ *   class_weight [C] fp32 or NULL, label_smoothing in [0, 1]: nn.CrossEntropyLoss(weight=, label_smoothing=) (F.cross_entropy):
+ *     loss_row = (1-e) w_t (lse - l_t) + (e/C) (W lse - sum_c w_c l_c), W = sum_c w_c.  Exclusive with alpha and with gamma != 0.
+ *   row_stats [B][4] fp32 or NULL: {lse, the row's gradient factor (focal f, or S = (1-e) w_t + (e/C) W), target margin logit l_t, w_t}:
+ *     what pfr_alpha_grad and pfr_loss_reduce read.
+ *   grad_scale_dev2: a second device scalar multiplied into the gradient scale (pfr_loss_reduce's 1 / denominator) or NULL. */
+int pfr_margin_ce_ex(const float* cosv, const int64_t* label, int B, int C, int ldc, int mode, float s, float m, float gamma,
+                     const float* alpha, const float* class_weight, float label_smoothing, float grad_scale,
+                     const float* grad_scale_dev, const float* grad_scale_dev2, float* logits, float* loss_rows, float* row_stats,
+                     void* dcos, int dcos_dtype, pfr_stream_t stream);
+/* gradient of FocalLoss's alpha (autograd of `self.alpha * input`, losses/losses.py:23): dalpha[c] = grad_scale * (*grad_scale_dev) *
+ * sum_i dz_ic * l_ic with dz recomputed from cos, alpha and pfr_margin_ce_ex's row_stats.  Column-wise, rows in a fixed order,
+ * no atomics: bitwise reproducible. */
+int pfr_alpha_grad(const float* cosv, const int64_t* label, const float* alpha, const float* row_stats, int B, int C, int ldc,
+                   float s, float grad_scale, const float* grad_scale_dev, float* dalpha, pfr_stream_t stream);
+/* the criterion's reduction (`.mean()` of losses/losses.py:28; F.cross_entropy's reduction): out_loss = sum(loss_rows) / d,
+ * out_inv_denom (or NULL) = 1 / d; reduction 0: d = n, 1 ('sum'): d = 1, 2 (weighted 'mean'): d = sum_i row_stats[i][3] = sum_i w_{t_i} */
+int pfr_loss_reduce(const float* loss_rows, const float* row_stats, int n, int reduction, float* out_loss, float* out_inv_denom,
+                    pfr_stream_t stream);
 
 /* ---- optimiser steps over flat fp32 master buffers (configs/dog_fe/fe_dogs_config.py:123-133; body_dog_fe.py:121-131) */
 int pfr_sgd_step(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,

@@ -295,6 +295,50 @@ def mean(x, out=None):
     return out
 
 
+def _chk_class_vector(v, C, device, name):
+    if v is not None and (v.dtype != torch.float32 or v.shape != (C,) or v.device != device or not v.is_contiguous()):
+        raise PfrError(f"{name}: expected a contiguous fp32 [{C}] tensor on {device}")
+
+
+def margin_ce_ex(cosv, label, C, mode, s, m, gamma=0.0, alpha=None, class_weight=None, label_smoothing=0.0, grad_scale=1.0,
+                 grad_scale_dev=None, grad_scale_dev2=None, want_logits=True, want_stats=True, dcos_dtype=None):
+    """margin_ce with the criterion options of pfr_margin_ce_ex -> (logits, loss_rows, row_stats [B, 4], dcos)"""
+    B, ldc = cosv.shape
+    assert cosv.dtype == torch.float32 and label.dtype == torch.int64
+    _chk_class_vector(alpha, C, cosv.device, "margin_ce_ex: alpha")
+    _chk_class_vector(class_weight, C, cosv.device, "margin_ce_ex: class_weight")
+    logits = torch.empty((B, C), dtype=torch.float32, device=cosv.device) if want_logits else None
+    loss_rows = torch.empty(B, dtype=torch.float32, device=cosv.device)
+    stats = torch.empty((B, 4), dtype=torch.float32, device=cosv.device) if want_stats else None
+    dcos = None if dcos_dtype is None else torch.zeros((B, ldc), dtype=dcos_dtype, device=cosv.device)
+    lib.pfr_margin_ce_ex(_p(cosv), _p(label), B, C, ldc, MARGIN_MODES[mode], float(s), float(m), float(gamma), _p(alpha), _p(class_weight),
+                         float(label_smoothing), float(grad_scale), _p(grad_scale_dev), _p(grad_scale_dev2), _p(logits), _p(loss_rows),
+                         _p(stats), _p(dcos), PFR_F32 if dcos is None else dtype_id(dcos.dtype), _stream())
+    return logits, loss_rows, stats, dcos
+
+
+def alpha_grad(cosv, label, alpha, row_stats, C, s, grad_scale=1.0, grad_scale_dev=None):
+    """d loss / d alpha [C] of the adaptive-alpha focal criterion from cos, alpha and margin_ce_ex's row statistics"""
+    B, ldc = cosv.shape
+    _chk_class_vector(alpha, C, cosv.device, "alpha_grad: alpha")
+    assert row_stats.shape == (B, 4) and row_stats.dtype == torch.float32 and row_stats.is_contiguous()
+    dalpha = torch.empty(C, dtype=torch.float32, device=cosv.device)
+    lib.pfr_alpha_grad(_p(cosv), _p(label), _p(alpha), _p(row_stats), B, C, ldc, float(s), float(grad_scale), _p(grad_scale_dev),
+                       _p(dalpha), _stream())
+    return dalpha
+
+
+LOSS_REDUCTIONS = {"mean": 0, "sum": 1, "weighted_mean": 2}
+
+
+def loss_reduce(loss_rows, row_stats, reduction):
+    """-> (loss, 1 / denominator), both device scalars"""
+    out = torch.empty((), dtype=torch.float32, device=loss_rows.device)
+    inv = torch.empty((), dtype=torch.float32, device=loss_rows.device)
+    lib.pfr_loss_reduce(_p(loss_rows), _p(row_stats), loss_rows.numel(), LOSS_REDUCTIONS[reduction], _p(out), _p(inv), _stream())
+    return out, inv
+
+
 # ------------------------------------------------------------------------------------------------ optimisers
 def sgd_step(p, g, mom, shadow, lr, momentum, weight_decay, grad_scale=1.0, first_step=False):
     lib.pfr_sgd_step(_p(p), _p(g), _p(mom), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),

@@ -31,7 +31,7 @@ def _live(key, default):
 
 def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs, device, n_epochs=1, seed=0,
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
-         noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None):
+         noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True):
     torch.manual_seed(seed)
     dataset = SyntheticRecDataset(n_train_ids + n_val_ids, photos, image_size, seed=seed, noise=noise, raw_uint8=device_augment,
                                   noise_bank=noise_bank)
@@ -67,8 +67,10 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
 
     def loss(config, model_):
         _ = config
-        return SoftmaxBasedMetricLearning(model=model_, num_class=n_train_ids, embedding_size=512, is_focal=True,
-                                          arc_margin=True)
+        # loss_kwargs go to FocalLoss (is_focal) or nn.CrossEntropyLoss as in the reference (losses/__init__.py:28-33).  A learnable
+        # FocalLoss alpha is in no optimizer group below, as in the reference's configs: it stays at its initial ones unless a config adds it.
+        return SoftmaxBasedMetricLearning(model=model_, num_class=n_train_ids, embedding_size=512, is_focal=is_focal,
+                                          loss_kwargs=loss_kwargs, arc_margin=True)
 
     def optimizer(model_):
         params1 = [p for i, p in model_.module.named_parameters() if 'fc' not in i]

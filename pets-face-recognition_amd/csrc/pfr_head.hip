@@ -10,7 +10,9 @@
 //
 // Kernels here: row L2-normalisation (forward: writes the compute-dtype x̂ and, for the weight, also x̂ᵀ; backward:
 // dx = (dx̂ − x̂·(x̂·dx̂))/‖x‖) with wave-shuffle reductions, and ONE fused row kernel for
-// margin → scale → log-softmax → loss → ∂loss/∂cos (the three B×C temporaries of the reference never exist).
+// margin → scale → log-softmax → loss → ∂loss/∂cos (the three B×C temporaries of the reference never exist).  The criterion of that
+// kernel is a template switch: plain / focal CE, focal CE of alpha·logits (learnable alpha; its gradient is a column kernel of its
+// own), nn.CrossEntropyLoss with class weights and label smoothing; the loss reduction (mean / sum / weighted mean) stays on the device.
 // The two cosine GEMMs and their gradients run on the MFMA implicit-GEMM kernels (pfr_igemm.hip / pfr_wgrad.hip).
 #include "pfr_common.h"
 
@@ -238,15 +240,31 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* sh) {
   return r;
 }
 
+// The criterion of the row kernel, a compile-time switch (CRIT_PLAIN is the code every FE config of the reference runs):
+//   CRIT_PLAIN  focal / plain cross-entropy of the margin logits l                      (losses/losses.py:22-28 with alpha=None)
+//   CRIT_ALPHA  the same on z = alpha·l, alpha a learnable [C] vector                   (losses/losses.py:13-24 with alpha=True)
+//   CRIT_WCE    nn.CrossEntropyLoss(weight=w, label_smoothing=e) on l (torch semantics):
+//               row = (1−e)·w_t·(lse − l_t) + (e/C)·(W·lse − Σ_c w_c·l_c), W = Σ_c w_c ; 'mean' divides Σ rows by Σ_i w_{t_i}
+//               ∂row/∂l_c = S·softmax(l)_c − (1−e)·w_t·[c==t] − (e/C)·w_c, S = (1−e)·w_t + (e/C)·W
+enum { CRIT_PLAIN = 0, CRIT_ALPHA = 1, CRIT_WCE = 2 };
+struct CritParams {
+  const float* alpha;       // [C], CRIT_ALPHA
+  const float* weight;      // [C] or null (= all ones), CRIT_WCE
+  float smoothing;          // e, CRIT_WCE
+  float* row_stats;         // [B][4] or null: {lse, gradient factor of the row (focal f / S), target margin logit l_t, w_t}
+  const float* gscale_dev2; // second device-side factor of the gradient scale (1 / Σ w_t of the weighted mean) or null
+};
+
 // one block per sample row: 256 threads, or 1024 for long rows (three dependent passes over the row — at 10 000 classes and
 // one wave per SIMD each pass is ~40 exposed memory round trips: 30 us with 256 threads)
-template <typename TG>
+template <typename TG, int CRIT>
 __global__ __launch_bounds__(1024) void margin_ce_kernel(const float* __restrict__ cosv, const int64_t* __restrict__ label,
                                                         MarginParams mp, float* __restrict__ logits, float* __restrict__ loss_rows,
                                                         TG* __restrict__ dcos, int C, int ldc, float gscale,
-                                                        const float* __restrict__ gscale_dev) {
+                                                        const float* __restrict__ gscale_dev, CritParams cp) {
   __shared__ float sh[16];
   if (gscale_dev) gscale *= gscale_dev[0];
+  if (CRIT == CRIT_WCE && cp.gscale_dev2) gscale *= cp.gscale_dev2[0];
   const int row = blockIdx.x;
   const int nt = blockDim.x;
   const float* cr = cosv + (size_t)row * ldc;
@@ -269,38 +287,145 @@ __global__ __launch_bounds__(1024) void margin_ce_kernel(const float* __restrict
     dphi = take ? dph : 1.f;
   }
   const float lt = mp.s * phi;
-  float mx = -INFINITY;
-  for (int j = threadIdx.x; j < C; j += nt) {
-    const float l = (j == t) ? lt : mp.s * cr[j];
-    mx = fmaxf(mx, l);
-  }
-  mx = block_reduce_max(mx, sh);
-  float se = 0.f;
-  for (int j = threadIdx.x; j < C; j += nt) {
-    const float l = (j == t) ? lt : mp.s * cr[j];
-    se += expf(l - mx);
-  }
-  se = block_reduce_sum(se, sh);
-  const float lse = mx + logf(se);
-  const float logp = lse - lt;  // cross-entropy of this row
-  const float pt = expf(-logp);
-  float f = 1.f, lossv = logp;
-  if (mp.gamma != 0.f) {
-    const float om = fmaxf(1.f - pt, 0.f);
-    lossv = powf(om, mp.gamma) * logp;
-    f = powf(om, mp.gamma) + mp.gamma * logp * pt * powf(om, mp.gamma - 1.f);
-  }
-  if (threadIdx.x == 0 && loss_rows) loss_rows[row] = lossv;
-  const float gs = gscale * f;
-  for (int j = threadIdx.x; j < C; j += nt) {
-    const float l = (j == t) ? lt : mp.s * cr[j];
-    if (logits) logits[(size_t)row * C + j] = l;
-    if (dcos) {
-      const float p = expf(l - lse);
-      float d = (j == t) ? (p - 1.f) * dphi : p;
-      dcos[(size_t)row * ldc + j] = from_f32<TG>(d * mp.s * gs);
+  if constexpr (CRIT == CRIT_PLAIN) {
+    float mx = -INFINITY;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : mp.s * cr[j];
+      mx = fmaxf(mx, l);
+    }
+    mx = block_reduce_max(mx, sh);
+    float se = 0.f;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : mp.s * cr[j];
+      se += expf(l - mx);
+    }
+    se = block_reduce_sum(se, sh);
+    const float lse = mx + logf(se);
+    const float logp = lse - lt;  // cross-entropy of this row
+    const float pt = expf(-logp);
+    float f = 1.f, lossv = logp;
+    if (mp.gamma != 0.f) {
+      const float om = fmaxf(1.f - pt, 0.f);
+      lossv = powf(om, mp.gamma) * logp;
+      f = powf(om, mp.gamma) + mp.gamma * logp * pt * powf(om, mp.gamma - 1.f);
+    }
+    if (threadIdx.x == 0 && loss_rows) loss_rows[row] = lossv;
+    if (threadIdx.x == 0 && cp.row_stats) reinterpret_cast<f32x4*>(cp.row_stats)[row] = f32x4{lse, f, lt, 1.f};
+    const float gs = gscale * f;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : mp.s * cr[j];
+      if (logits) logits[(size_t)row * C + j] = l;
+      if (dcos) {
+        const float p = expf(l - lse);
+        float d = (j == t) ? (p - 1.f) * dphi : p;
+        dcos[(size_t)row * ldc + j] = from_f32<TG>(d * mp.s * gs);
+      }
+    }
+  } else if constexpr (CRIT == CRIT_ALPHA) {
+    // z = alpha·l: the maximum, the sum and the target all in z (alpha may be negative or > 1); the logits written stay l
+    const float zt = cp.alpha[t] * lt;
+    float mx = -INFINITY;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float z = cp.alpha[j] * ((j == t) ? lt : mp.s * cr[j]);
+      mx = fmaxf(mx, z);
+    }
+    mx = block_reduce_max(mx, sh);
+    float se = 0.f;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float z = cp.alpha[j] * ((j == t) ? lt : mp.s * cr[j]);
+      se += expf(z - mx);
+    }
+    se = block_reduce_sum(se, sh);
+    const float lse = mx + logf(se);
+    const float logp = lse - zt;
+    const float pt = expf(-logp);
+    float f = 1.f, lossv = logp;
+    if (mp.gamma != 0.f) {
+      const float om = fmaxf(1.f - pt, 0.f);
+      lossv = powf(om, mp.gamma) * logp;
+      f = powf(om, mp.gamma) + mp.gamma * logp * pt * powf(om, mp.gamma - 1.f);
+    }
+    if (threadIdx.x == 0 && loss_rows) loss_rows[row] = lossv;
+    if (threadIdx.x == 0 && cp.row_stats) reinterpret_cast<f32x4*>(cp.row_stats)[row] = f32x4{lse, f, lt, 1.f};
+    const float gs = gscale * f;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : mp.s * cr[j];
+      if (logits) logits[(size_t)row * C + j] = l;
+      if (dcos) {
+        const float a = cp.alpha[j];
+        const float p = expf(a * l - lse);
+        float d = (j == t) ? (p - 1.f) * dphi : p;   // dz / f, then dl = alpha·dz
+        dcos[(size_t)row * ldc + j] = from_f32<TG>(a * d * mp.s * gs);
+      }
+    }
+  } else {
+    const float e = cp.smoothing, wt = cp.weight ? cp.weight[t] : 1.f;
+    float mx = -INFINITY;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : mp.s * cr[j];
+      mx = fmaxf(mx, l);
+    }
+    mx = block_reduce_max(mx, sh);
+    // the smoothing term rides in the pass of the exponentials: Σ w_c·l_c (and W = Σ w_c when there are weights)
+    float se = 0.f, swl = 0.f, sw = 0.f;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : mp.s * cr[j];
+      se += expf(l - mx);
+      if (e != 0.f) {
+        if (cp.weight) {
+          const float w = cp.weight[j];
+          swl = fmaf(w, l, swl);
+          sw += w;
+        } else {
+          swl += l;
+        }
+      }
+    }
+    se = block_reduce_sum(se, sh);
+    float W = (float)C;
+    if (e != 0.f) {
+      swl = block_reduce_sum(swl, sh);
+      if (cp.weight) W = block_reduce_sum(sw, sh);
+    }
+    const float lse = mx + logf(se);
+    const float hard = (1.f - e) * wt, soft = e / (float)C;
+    float lossv = hard * (lse - lt), S = hard;
+    if (e != 0.f) {
+      lossv += soft * (W * lse - swl);
+      S += soft * W;
+    }
+    if (threadIdx.x == 0 && loss_rows) loss_rows[row] = lossv;
+    if (threadIdx.x == 0 && cp.row_stats) reinterpret_cast<f32x4*>(cp.row_stats)[row] = f32x4{lse, S, lt, wt};
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : mp.s * cr[j];
+      if (logits) logits[(size_t)row * C + j] = l;
+      if (dcos) {
+        float d = S * expf(l - lse);
+        if (e != 0.f) d -= soft * (cp.weight ? cp.weight[j] : 1.f);
+        if (j == t) d = (d - hard) * dphi;
+        dcos[(size_t)row * ldc + j] = from_f32<TG>(d * mp.s * gscale);
+      }
     }
   }
+}
+
+static void margin_params(MarginParams& mp, int mode, float s, float m, float gamma) {
+  mp.s = s; mp.m = m; mp.mode = mode; mp.gamma = gamma;
+  mp.cos_m = (float)cos((double)m);
+  mp.sin_m = (float)sin((double)m);
+  mp.th = (float)cos(M_PI - (double)m);
+  mp.mm = (float)(sin(M_PI - (double)m) * (double)m);
+}
+
+template <int CRIT>
+static void launch_margin_ce(const float* cosv, const int64_t* label, int B, int C, int ldc, const MarginParams& mp, float grad_scale,
+                             const float* grad_scale_dev, float* logits, float* loss_rows, void* dcos, int dcos_dtype, const CritParams& cp,
+                             hipStream_t st) {
+  const int nt = C >= 4096 ? 1024 : 256;
+  if (dcos_dtype == PFR_BF16)
+    hipLaunchKernelGGL((margin_ce_kernel<bf16_t, CRIT>), dim3(B), dim3(nt), 0, st, cosv, label, mp, logits, loss_rows, (bf16_t*)dcos, C, ldc, grad_scale, grad_scale_dev, cp);
+  else
+    hipLaunchKernelGGL((margin_ce_kernel<float, CRIT>), dim3(B), dim3(nt), 0, st, cosv, label, mp, logits, loss_rows, (float*)dcos, C, ldc, grad_scale, grad_scale_dev, cp);
 }
 
 extern "C" int pfr_margin_ce(const float* cosv, const int64_t* label, int B, int C, int ldc, int mode, float s, float m,
@@ -309,17 +434,76 @@ extern "C" int pfr_margin_ce(const float* cosv, const int64_t* label, int B, int
   PFR_CHECK_ARG(cosv && label && B > 0 && C > 0, "pfr_margin_ce: bad args");
   PFR_CHECK_ARG(mode >= 0 && mode <= 3, "pfr_margin_ce: bad margin mode %d", mode);
   MarginParams mp;
-  mp.s = s; mp.m = m; mp.mode = mode; mp.gamma = gamma;
-  mp.cos_m = (float)cos((double)m);
-  mp.sin_m = (float)sin((double)m);
-  mp.th = (float)cos(M_PI - (double)m);
-  mp.mm = (float)(sin(M_PI - (double)m) * (double)m);
+  margin_params(mp, mode, s, m, gamma);
   if (ldc <= 0) ldc = C;
-  const int nt = C >= 4096 ? 1024 : 256;
-  if (dcos_dtype == PFR_BF16)
-    hipLaunchKernelGGL(margin_ce_kernel<bf16_t>, dim3(B), dim3(nt), 0, st, cosv, label, mp, logits, loss_rows, (bf16_t*)dcos, C, ldc, grad_scale, grad_scale_dev);
-  else
-    hipLaunchKernelGGL(margin_ce_kernel<float>, dim3(B), dim3(nt), 0, st, cosv, label, mp, logits, loss_rows, (float*)dcos, C, ldc, grad_scale, grad_scale_dev);
+  launch_margin_ce<CRIT_PLAIN>(cosv, label, B, C, ldc, mp, grad_scale, grad_scale_dev, logits, loss_rows, dcos, dcos_dtype, CritParams{}, st);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+extern "C" int pfr_margin_ce_ex(const float* cosv, const int64_t* label, int B, int C, int ldc, int mode, float s, float m, float gamma,
+                                const float* alpha, const float* class_weight, float label_smoothing, float grad_scale,
+                                const float* grad_scale_dev, const float* grad_scale_dev2, float* logits, float* loss_rows, float* row_stats,
+                                void* dcos, int dcos_dtype, hipStream_t st) {
+  PFR_CHECK_ARG(cosv && label, "pfr_margin_ce_ex: null pointer");
+  PFR_CHECK_ARG(B > 0 && C > 0 && (ldc <= 0 || ldc >= C), "pfr_margin_ce_ex: bad shape B=%d C=%d ldc=%d", B, C, ldc);
+  PFR_CHECK_ARG(mode >= 0 && mode <= 3, "pfr_margin_ce_ex: bad margin mode %d", mode);
+  PFR_CHECK_ARG(label_smoothing >= 0.f && label_smoothing <= 1.f, "pfr_margin_ce_ex: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  PFR_CHECK_ARG(dcos_dtype == PFR_F32 || dcos_dtype == PFR_BF16, "pfr_margin_ce_ex: bad dcos dtype %d", dcos_dtype);
+  const bool wce = class_weight || label_smoothing != 0.f;
+  if (alpha && wce) { pfr_set_error("pfr_margin_ce_ex: alpha excludes class_weight / label_smoothing"); return PFR_ERR_UNSUPPORTED; }
+  if (wce && gamma != 0.f) { pfr_set_error("pfr_margin_ce_ex: focal gamma excludes class_weight / label_smoothing"); return PFR_ERR_UNSUPPORTED; }
+  PFR_CHECK_ARG(wce || !grad_scale_dev2, "pfr_margin_ce_ex: grad_scale_dev2 belongs to the weighted mean only");
+  MarginParams mp;
+  margin_params(mp, mode, s, m, gamma);
+  if (ldc <= 0) ldc = C;
+  CritParams cp{alpha, class_weight, label_smoothing, row_stats, grad_scale_dev2};
+  if (alpha) launch_margin_ce<CRIT_ALPHA>(cosv, label, B, C, ldc, mp, grad_scale, grad_scale_dev, logits, loss_rows, dcos, dcos_dtype, cp, st);
+  else if (wce) launch_margin_ce<CRIT_WCE>(cosv, label, B, C, ldc, mp, grad_scale, grad_scale_dev, logits, loss_rows, dcos, dcos_dtype, cp, st);
+  else launch_margin_ce<CRIT_PLAIN>(cosv, label, B, C, ldc, mp, grad_scale, grad_scale_dev, logits, loss_rows, dcos, dcos_dtype, cp, st);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// dalpha_c = gscale · Σ_i dz_ic · l_ic, dz_ic = f_i · (softmax(z_i)_c − [c == t_i]) recomputed from cos, alpha and the row statistics of
+// margin_ce_kernel<CRIT_ALPHA> (dz itself is never stored).  A workgroup owns 64 consecutive classes: lane = class (coalesced reads of
+// cos), wave w walks rows w, w + nw, ... in that order, the nw partial sums meet in LDS and wave 0 adds them in wave order: no
+// atomics, the same bits every run.
+__global__ __launch_bounds__(1024) void alpha_grad_kernel(const float* __restrict__ cosv, const int64_t* __restrict__ label,
+                                                          const float* __restrict__ alpha, const float* __restrict__ row_stats,
+                                                          float* __restrict__ dalpha, int B, int C, int ldc, float s, float gscale,
+                                                          const float* __restrict__ gscale_dev) {
+  __shared__ float part[16][64];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  const bool live = c < C;
+  const int cc = live ? c : C - 1;
+  const float a = alpha[cc];
+  float acc = 0.f;
+  for (int i = w; i < B; i += nw) {
+    const f32x4 st = reinterpret_cast<const f32x4*>(row_stats)[i];   // {lse, f, l_t, -}
+    const float l = (cc == (int)label[i]) ? st[2] : s * cosv[(size_t)i * ldc + cc];
+    const float p = expf(a * l - st[0]);
+    const float dz = st[1] * ((cc == (int)label[i]) ? p - 1.f : p);
+    acc = fmaf(dz, l, acc);
+  }
+  part[w][lane] = acc;
+  __syncthreads();
+  if (w == 0 && live) {
+    float r = part[0][lane];
+    for (int k = 1; k < nw; ++k) r += part[k][lane];
+    if (gscale_dev) gscale *= gscale_dev[0];
+    dalpha[c] = r * gscale;
+  }
+}
+extern "C" int pfr_alpha_grad(const float* cosv, const int64_t* label, const float* alpha, const float* row_stats, int B, int C, int ldc,
+                              float s, float grad_scale, const float* grad_scale_dev, float* dalpha, hipStream_t st) {
+  PFR_CHECK_ARG(cosv && label && alpha && row_stats && dalpha, "pfr_alpha_grad: null pointer");
+  PFR_CHECK_ARG(B > 0 && C > 0 && (ldc <= 0 || ldc >= C), "pfr_alpha_grad: bad shape B=%d C=%d ldc=%d", B, C, ldc);
+  if (ldc <= 0) ldc = C;
+  const int nt = B >= 64 ? 1024 : 256;
+  hipLaunchKernelGGL(alpha_grad_kernel, dim3((C + 63) / 64), dim3(nt), 0, st, cosv, label, alpha, row_stats, dalpha, B, C, ldc, s, grad_scale, grad_scale_dev);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }
@@ -335,6 +519,34 @@ __global__ void mean_kernel(const float* __restrict__ x, float* __restrict__ out
 extern "C" int pfr_mean(const float* x, float* out, int n, hipStream_t st) {
   PFR_CHECK_ARG(x && out && n > 0, "pfr_mean: bad args");
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, x, out, n);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// the criterion's reduction of the per-row losses without a host round trip: out_loss = Σ rows / d and out_inv_denom = 1 / d with
+// d = n ('mean' of the focal criteria), 1 ('sum') or Σ_i w_{t_i} (nn.CrossEntropyLoss(weight=, reduction='mean'); w_t is row_stats[i][3])
+__global__ void loss_reduce_kernel(const float* __restrict__ x, const float* __restrict__ row_stats, float* __restrict__ out,
+                                   float* __restrict__ out_inv, int n, int reduction) {
+  __shared__ float sh[4];
+  float a = 0.f, d = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    a += x[i];
+    if (reduction == 2) d += row_stats[4 * (size_t)i + 3];
+  }
+  a = block_reduce_sum(a, sh);
+  if (reduction == 2) d = block_reduce_sum(d, sh);
+  else d = reduction == 0 ? (float)n : 1.f;
+  if (threadIdx.x == 0) {
+    out[0] = a / d;
+    if (out_inv) out_inv[0] = 1.f / d;
+  }
+}
+extern "C" int pfr_loss_reduce(const float* loss_rows, const float* row_stats, int n, int reduction, float* out_loss, float* out_inv_denom,
+                               hipStream_t st) {
+  PFR_CHECK_ARG(loss_rows && out_loss && n > 0, "pfr_loss_reduce: bad args");
+  PFR_CHECK_ARG(reduction >= 0 && reduction <= 2, "pfr_loss_reduce: bad reduction mode %d", reduction);
+  PFR_CHECK_ARG(reduction != 2 || row_stats, "pfr_loss_reduce: the weighted mean needs row_stats");
+  hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, loss_rows, row_stats, out_loss, out_inv_denom, n, reduction);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }

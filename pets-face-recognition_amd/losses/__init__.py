@@ -6,7 +6,7 @@ import torch
 import torch.nn as nn
 
 from .large_margin import ArcMarginProduct, AddMarginProduct, _MarginHead
-from .losses import FocalLoss
+from .losses import FocalLoss, describe_criterion
 
 
 class SoftmaxBasedMetricLearning(nn.Module):
@@ -24,15 +24,20 @@ class SoftmaxBasedMetricLearning(nn.Module):
         self.return_logits = True  # the reference always returns logits; set False to skip writing them (bench)
 
     def _fusable(self, emb):
-        if not emb.is_cuda or not isinstance(self.add_margin, _MarginHead):
+        """Criterion description (losses.losses.Criterion) when the whole head, normalise → cosine GEMM → margin → criterion, runs as
+        the fused HIP path for this embedding, else None (then: the margin-logit kernels, then `self.focal_loss` on the logits).
+        Fused: FocalLoss with a fixed or an adaptive (learnable) alpha; nn.CrossEntropyLoss with `weight`, `label_smoothing` and
+        reduction 'mean' / 'sum'.  Left unfused on purpose: reduction='none', a non-default ignore_index, a weight / alpha that is not an
+        fp32 [num_class] tensor on the embedding's device, CPU tensors, anything but a [B, in_features] embedding."""
+        head = self.add_margin
+        if not emb.is_cuda or not isinstance(head, _MarginHead) or emb.dim() != 2 or emb.shape[1] != head.in_features:
             return None
-        fl = self.focal_loss
-        if isinstance(fl, FocalLoss) and not fl.adaptive_flag:
-            return float(fl.gamma)
-        if type(fl) is nn.CrossEntropyLoss and fl.weight is None and fl.reduction == "mean" and \
-                getattr(fl, "label_smoothing", 0.0) == 0.0 and fl.ignore_index == -100:
-            return 0.0
-        return None
+        return describe_criterion(self.focal_loss, head.out_features, emb.device)
+
+    def _unfused(self, tensor, label):
+        logits = self.add_margin(tensor, label)
+        loss = self.focal_loss(logits, label)
+        return {'loss': loss, 'emb': tensor, 'logits': logits}
 
     def forward(self, img, label=None, **__):
         if isinstance(img, (list, tuple)):
@@ -41,17 +46,15 @@ class SoftmaxBasedMetricLearning(nn.Module):
             tensor = self.module(img)
         if label is None:
             return tensor
-        gamma = self._fusable(tensor)
-        if gamma is not None:
-            from ._head_hip import MarginCEFunction, resolve_dtype
-            head = self.add_margin
-            dt = head.compute_dtype or getattr(self.module, "compute_dtype", None)
-            loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, gamma,
-                                                  resolve_dtype(dt), self.return_logits)
-            return {'loss': loss, 'emb': tensor, 'logits': logits if self.return_logits else None}
-        logits = self.add_margin(tensor, label)
-        loss = self.focal_loss(logits, label)
-        return {'loss': loss, 'emb': tensor, 'logits': logits}
+        crit = self._fusable(tensor)
+        if crit is None:
+            return self._unfused(tensor, label)
+        from ._head_hip import MarginCEFunction, resolve_dtype
+        head = self.add_margin
+        dt = head.compute_dtype or getattr(self.module, "compute_dtype", None)
+        loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
+                                              resolve_dtype(dt), self.return_logits, crit.alpha)
+        return {'loss': loss, 'emb': tensor, 'logits': logits if self.return_logits else None}
 
 
 class DummyWrapper(nn.Module):

@@ -57,19 +57,35 @@ def _cosine_bwd(dcos, emb, weight, saved, T):
 
 
 class MarginCEFunction(torch.autograd.Function):
-    """(emb, weight, label) → (loss, logits): normalise → cosine GEMM → margin → scale → softmax-CE, fused."""
+    """(emb, weight, label[, alpha]) → (loss, logits): normalise → cosine GEMM → margin → scale → criterion, fused.  `crit` is the
+    losses.losses.Criterion description of the loss (gamma, adaptive alpha, class weight, label smoothing, reduction); `alpha` is the
+    criterion's learnable [C] vector passed as an input so that autograd hands its gradient back (None when crit.alpha is None).
+    Every criterion is the same launches: only the row kernel's instantiation differs, plus one column kernel for d loss / d alpha."""
 
     @staticmethod
-    def forward(ctx, emb, weight, label, mode, s, m, gamma, T, want_logits):
+    def forward(ctx, emb, weight, label, mode, s, m, crit, T, want_logits, alpha=None):
         emb = emb.contiguous().float()
         w = weight.detach().contiguous()
         label = label.contiguous().long()
         C = w.shape[0]
+        B = emb.shape[0]
         cos, saved = _cosine_fwd(emb, w, T)
-        logits, loss_rows, _ = ops.margin_ce(cos, label, C, mode, s, m, gamma=gamma, want_logits=want_logits)
-        loss = ops.mean(loss_rows)
-        ctx.save_for_backward(emb, w, label, cos, *saved)
-        ctx.cfg = (mode, s, m, gamma, T, C)
+        stats = inv_denom = None
+        if crit.is_plain:
+            logits, loss_rows, _ = ops.margin_ce(cos, label, C, mode, s, m, gamma=crit.gamma, want_logits=want_logits)
+            loss = ops.mean(loss_rows)
+        else:
+            alpha = None if alpha is None else alpha.detach().contiguous()
+            logits, loss_rows, stats, _ = ops.margin_ce_ex(cos, label, C, mode, s, m, gamma=crit.gamma, alpha=alpha, class_weight=crit.weight,
+                                                           label_smoothing=crit.smoothing, want_logits=want_logits)
+            if alpha is not None:
+                loss = ops.mean(loss_rows)
+            elif crit.reduction == "sum":
+                loss, _ = ops.loss_reduce(loss_rows, None, "sum")
+            else:   # F.cross_entropy's 'mean' divides by the sum of the targets' weights (= B without weights)
+                loss, inv_denom = ops.loss_reduce(loss_rows, stats, "weighted_mean")
+        ctx.save_for_backward(emb, w, label, cos, alpha, crit.weight, stats, inv_denom, *saved)
+        ctx.cfg = (mode, s, m, crit, T, C)
         if logits is None:
             logits = torch.empty(0, device=emb.device)
         ctx.mark_non_differentiable(logits)
@@ -77,14 +93,24 @@ class MarginCEFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dlogits):
-        emb, w, label, cos, *saved = ctx.saved_tensors
-        mode, s, m, gamma, T, C = ctx.cfg
+        emb, w, label, cos, alpha, cweight, stats, inv_denom, *saved = ctx.saved_tensors
+        mode, s, m, crit, T, C = ctx.cfg
         B = emb.shape[0]
         dloss = dloss.contiguous().float()
-        _, _, dcos = ops.margin_ce(cos, label, C, mode, s, m, gamma=gamma, grad_scale=1.0 / B, grad_scale_dev=dloss,
-                                   want_logits=False, dcos_dtype=T)
+        dalpha = None
+        if crit.is_plain:
+            _, _, dcos = ops.margin_ce(cos, label, C, mode, s, m, gamma=crit.gamma, grad_scale=1.0 / B, grad_scale_dev=dloss,
+                                       want_logits=False, dcos_dtype=T)
+        else:
+            # 'mean' of the focal criteria: 1 / B; weighted mean: the forward's device scalar 1 / Σ w_t; 'sum': 1
+            gs = 1.0 / B if alpha is not None else 1.0
+            _, _, _, dcos = ops.margin_ce_ex(cos, label, C, mode, s, m, gamma=crit.gamma, alpha=alpha, class_weight=cweight,
+                                             label_smoothing=crit.smoothing, grad_scale=gs, grad_scale_dev=dloss, grad_scale_dev2=inv_denom,
+                                             want_logits=False, want_stats=False, dcos_dtype=T)
+            if alpha is not None and ctx.needs_input_grad[9]:
+                dalpha = ops.alpha_grad(cos, label, alpha, stats, C, s, grad_scale=gs, grad_scale_dev=dloss)
         demb, dw = _cosine_bwd(dcos, emb, w, saved, T)
-        return demb, dw, None, None, None, None, None, None, None
+        return demb, dw, None, None, None, None, None, None, None, dalpha
 
 
 class MarginFunction(torch.autograd.Function):
@@ -117,25 +143,37 @@ class MarginFunction(torch.autograd.Function):
 
 
 class FocalCEFunction(torch.autograd.Function):
-    """(logits, target) → mean((1-p)^γ · CE): standalone FocalLoss / CrossEntropyLoss on CUDA logits."""
+    """(logits, target[, alpha]) → mean((1-p)^γ · CE) of alpha·logits: standalone FocalLoss / CrossEntropyLoss on CUDA logits."""
 
     @staticmethod
-    def forward(ctx, logits, target, gamma):
+    def forward(ctx, logits, target, gamma, alpha=None):
         logits = logits.contiguous().float()
         target = target.contiguous().long()
         B, C = logits.shape
-        _, rows, _ = ops.margin_ce(logits, target, C, "none", 1.0, 0.0, gamma=gamma, want_logits=False)
-        ctx.save_for_backward(logits, target)
+        stats = None
+        if alpha is None:
+            _, rows, _ = ops.margin_ce(logits, target, C, "none", 1.0, 0.0, gamma=gamma, want_logits=False)
+        else:
+            alpha = alpha.detach().contiguous()
+            _, rows, stats, _ = ops.margin_ce_ex(logits, target, C, "none", 1.0, 0.0, gamma=gamma, alpha=alpha, want_logits=False)
+        ctx.save_for_backward(logits, target, alpha, stats)
         ctx.gamma = gamma
         return ops.mean(rows)
 
     @staticmethod
     def backward(ctx, dloss):
-        logits, target = ctx.saved_tensors
+        logits, target, alpha, stats = ctx.saved_tensors
         B, C = logits.shape
-        _, _, d = ops.margin_ce(logits, target, C, "none", 1.0, 0.0, gamma=ctx.gamma, grad_scale=1.0 / B,
-                                grad_scale_dev=dloss.contiguous().float(), want_logits=False, dcos_dtype=torch.float32)
-        return d, None, None
+        dloss = dloss.contiguous().float()
+        if alpha is None:
+            _, _, d = ops.margin_ce(logits, target, C, "none", 1.0, 0.0, gamma=ctx.gamma, grad_scale=1.0 / B,
+                                    grad_scale_dev=dloss, want_logits=False, dcos_dtype=torch.float32)
+            return d, None, None, None
+        _, _, _, d = ops.margin_ce_ex(logits, target, C, "none", 1.0, 0.0, gamma=ctx.gamma, alpha=alpha, grad_scale=1.0 / B,
+                                      grad_scale_dev=dloss, want_logits=False, want_stats=False, dcos_dtype=torch.float32)
+        dalpha = ops.alpha_grad(logits, target, alpha, stats, C, 1.0, grad_scale=1.0 / B, grad_scale_dev=dloss) \
+            if ctx.needs_input_grad[3] else None
+        return d, None, None, dalpha
 
 
 def resolve_dtype(dt):
