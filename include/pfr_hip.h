@@ -475,6 +475,32 @@ int pfr_augment_params(const int* flags, const float* angles, int N, int out_w, 
 long pfr_augment_ws_bytes(int N, int H, int W);
 int pfr_augment_train(const unsigned char* x, int N, int H, int W, int crop_h, int crop_w, int out_h, int out_w,
                       const int* records, float* y, void* ws, pfr_stream_t stream);
+/* geometry-first order of the body configs (configs/dog_fe/body_dog_fe.py:18-27): crop → resize → rotate to a uint8 image, then
+ * sharpness (SMOOTH) and autocontrast on THAT image (their frame / lo-hi see the rotation's zero fill), then ToTensor.  Same
+ * arguments and records as pfr_augment_train; ws: pfr_augment_geo_ws_bytes. */
+long pfr_augment_geo_ws_bytes(int N, int out_h, int out_w);
+int pfr_augment_train_geo(const unsigned char* x, int N, int H, int W, int crop_h, int crop_w, int out_h, int out_w,
+                          const int* records, float* y, void* ws, pfr_stream_t stream);
+
+/* ---- fit stage: a ragged batch of uint8 HWC frames → one uniform uint8 canvas, bit-exact with Pillow (csrc/pfr_augment_fit.hip).
+ * mode 0 RESIZE: Image.resize((canvas_w, canvas_h), BILINEAR) (simple / no-align configs, simple_fe_dog.py:17-31), with the
+ * per-image sharpness / autocontrast pre-ops applied to the raw frame; mode 1 THUMBNAIL_PAD: Image.thumbnail((canvas_w, canvas_h),
+ * BICUBIC, reducing_gap=2.0) + centred zero pad (`resize_with_padding` of the body configs, body_dog_fe.py:18-33).
+ * pfr_augment_fit_params (HOST arrays; no device work): shapes int32 [N][2] = (H, W) → records int32 [N][32] and the 22-bit
+ * fixed-point coefficient tables of both axes of every image in `coeffs` (capacity in ints: pfr_augment_fit_coeff_ints, -1 on
+ * error).  Record: 0 H, 1 W, 2-3 target w / h (thumbnail size or the canvas), 4-5 reduce factors x / y, 6-9 reduce box, 10-13
+ * fractional resize box (float32 bit patterns), 14-15 pad left / top, 16-17 x table offset in `coeffs` / taps, 18-19 y table
+ * offset / taps, 20-21 sharpness / autocontrast flags (written 0: the caller sets them before the upload, RESIZE only), 22-23
+ * size after the reduce, 24 mode, 25-26 horizontal / vertical pass needed.  A table is [out][2 + taps] = (first tap, count,
+ * k...); a pass Pillow skips gets the identity table.  Frames with a side above 4096 or taller than 100:1 are refused.
+ * pfr_augment_fit: data = the packed frames on the device, offsets = int64 [N] byte offset of each frame (device), records /
+ * coeffs uploaded → out_u8 [N][canvas_h][canvas_w][3].  ws: pfr_augment_fit_ws_bytes(total bytes of data, N). */
+long pfr_augment_fit_coeff_ints(int mode, const int* shapes, int N, int canvas_h, int canvas_w);
+int pfr_augment_fit_params(int mode, const int* shapes, int N, int canvas_h, int canvas_w, int* records, int* coeffs,
+                           long coeff_capacity);
+long pfr_augment_fit_ws_bytes(long total_bytes, int N);
+int pfr_augment_fit(const unsigned char* data, const long* offsets, const int* records, const int* coeffs, int N, int canvas_h,
+                    int canvas_w, unsigned char* out_u8, void* ws, pfr_stream_t stream);
 
 /* Linear layer with a fused activation epilogue — the Swin MLP `FeedForward` (reference models/swin.py:40-52: Linear →
  * GELU → Linear) and its autograd.  x [M][K], w [N][K] (nn.Linear layout), y / y2 [M][N], all of `dtype`.

@@ -31,10 +31,21 @@ def _live(key, default):
 
 def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs, device, n_epochs=1, seed=0,
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
-         noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True):
+         noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
+         ragged=False, pipeline='head'):
+    # pipeline: which of the reference's three Compose shapes runs on the device (data_loading/augment.py): 'head' (uniform frames),
+    # 'simple' / 'body' (ragged frames: the detector's raw crops, each with its own size)
+    if pipeline not in ('head', 'simple', 'body'):
+        raise ValueError(f"pipeline must be 'head', 'simple' or 'body', got {pipeline!r}")
+    if (pipeline != 'head') != bool(ragged) or (ragged and not device_augment):
+        raise ValueError("the 'simple' and 'body' pipelines read ragged frames (ragged=True, device_augment=True); 'head' reads uniform ones")
     torch.manual_seed(seed)
     dataset = SyntheticRecDataset(n_train_ids + n_val_ids, photos, image_size, seed=seed, noise=noise, raw_uint8=device_augment,
-                                  noise_bank=noise_bank)
+                                  noise_bank=noise_bank, **({'ragged': True} if ragged else {}))
+    collate = {}
+    if ragged:
+        from data_loading import ragged_collate
+        collate = {'collate_fn': ragged_collate}
     train_users = list(range(n_train_ids))
     val_users = list(range(n_train_ids, n_train_ids + n_val_ids))
     labels = dataset.get_labels()
@@ -94,12 +105,20 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         # (batch size and the base rate are read from the config namespace at call time: main.py's find_max_batch_size /
         # find_optimal_init_lr write train_batch_size / init_lr there, reference main.py:79-89)
         return DataLoader(train, _live('train_batch_size', train_bs), shuffle=True, drop_last=True, num_workers=workers, pin_memory=device != 'cpu',
-                          persistent_workers=workers > 0, prefetch_factor=4 if workers > 0 else None)
+                          persistent_workers=workers > 0, prefetch_factor=4 if workers > 0 else None, **collate)
 
     def val_dataloader():
-        return DataLoader(val, _live('test_batch_size', test_bs), num_workers=0)
+        return DataLoader(val, _live('test_batch_size', test_bs), num_workers=0, **collate)
 
-    if device_augment:
+    if device_augment and pipeline != 'head':
+        # simple_fe_dog.py:17-31 / body_dog_fe.py:18-33 on ragged batches, at this config's network input size
+        from data_loading import DeviceAugmentation
+        gen = torch.Generator().manual_seed(seed + _rank())
+        hw, crop = (image_size, image_size), (image_size - 4, image_size - 4)
+        fit, order = (('resize', hw), 'color_first') if pipeline == 'simple' else (('thumbnail_pad', hw), 'geometry_first')
+        ns['device_train_augmentation'] = DeviceAugmentation(crop, hw, 0.1, 0.3, 5.0, gen, fit=fit, order=order)
+        ns['device_val_augmentation'] = DeviceAugmentation(None, None, 0.0, 0.0, 0.0, fit=fit)
+    elif device_augment:
         # the reference's train/val Compose pipelines (fe_dogs_config.py:17-32) applied on the device to uint8 batches
         from data_loading import DeviceAugmentation, val_augmentation
         ns['device_train_augmentation'] = DeviceAugmentation((image_size - 4, image_size - 4), (image_size, image_size), 0.1, 0.3,

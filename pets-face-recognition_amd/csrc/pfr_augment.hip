@@ -17,13 +17,12 @@
 // The crop, both resize passes, the rotation and ToTensor never touch HBM in between.  Random decisions are inputs
 // (device int32 [N][12] records built by pfr_augment_params on the host).
 #include "pfr_common.h"
+#include "pfr_augment_dev.h"
 #include <math.h>
 #include <mutex>
 #include <vector>
 
-#define AUG_PREC 22     // Resample.c PRECISION_BITS = 32 - 8 - 2
 #define AUG_MAXK 9      // taps per output sample supported (ksize = 2*ceil(max(scale,1)) + 1 → down-scaling up to 4x)
-#define AUG_SLABS 8     // row slabs per image in aug_pre (one workgroup each); lo/hi partials are merged by aug_post
 #define AUG_REC 12      // ints per image record: sharp, contrast, top, left, rot_valid, a0, a1, a2, a3, a4, a5, pad
 
 // ---- host: coefficient tables (Resample.c precompute_coeffs + normalize_coeffs_8bpc, bilinear) ---------------------------
@@ -124,16 +123,7 @@ extern "C" int pfr_augment_params(const int* flags, const float* angles, int N, 
   return PFR_OK;
 }
 
-// ---- device ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_min_i(int v) {
-  for (int o = 32; o; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-  for (int o = 32; o; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-
+// ---- device (wave_min_i / wave_max_i / aug_smooth_px / autocontrast_lut / aug_build_lut: pfr_augment_dev.h) --------------------------
 // blurred copy (sharp) and per-band lo / hi (contrast) of one row slab of one image;
 // lohi [N][AUG_SLABS][8] = lo0, hi0, lo1, hi1, lo2, hi2 of the slab
 __global__ __launch_bounds__(1024) void aug_pre_kernel(const uint8_t* __restrict__ x, int H, int W, const int* __restrict__ rec,
@@ -150,15 +140,7 @@ __global__ __launch_bounds__(1024) void aug_pre_kernel(const uint8_t* __restrict
     const int yy = i / rowb, xb = i - yy * rowb, xx = xb / 3, c = xb - xx * 3;
     int v = src[i];
     if (sharp) {
-      if (yy > 0 && yy < H - 1 && xx > 0 && xx < W - 1 && H >= 3 && W >= 3) {
-        int s = 4 * v;
-#pragma unroll
-        for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-          for (int dx = -3; dx <= 3; dx += 3) s += src[i + dy * rowb + dx];
-        v = (2 * s + 13) / 26;          // = (UINT8)(S/13 + 0.5) of Filter.c (S/13 + 0.5 is never within 0.038 of an integer)
-        v = v > 255 ? 255 : v;
-      }
+      if (yy > 0 && yy < H - 1 && xx > 0 && xx < W - 1 && H >= 3 && W >= 3) v = aug_smooth_px(src, i, rowb);
       dst[i] = (uint8_t)v;
     }
     lo[c] = min(lo[c], v);
@@ -180,43 +162,13 @@ __global__ __launch_bounds__(1024) void aug_pre_kernel(const uint8_t* __restrict
   }
 }
 
-// ImageOps.autocontrast's LUT entry in Python-double arithmetic.  The reference rounds the product before the add; the
-// library is built with -ffp-contract=fast (which ignores contraction pragmas), so the products are pinned in registers by
-// empty asm statements to keep the compiler from forming an fma.
-__device__ __forceinline__ uint8_t autocontrast_lut(int ix, int lo, int hi) {
-  if (hi <= lo) return (uint8_t)ix;
-  const double scale = 255.0 / (double)(hi - lo);
-  double offset = (double)(-lo) * scale;
-  double prod = (double)ix * scale;
-  asm volatile("" : "+v"(offset), "+v"(prod));
-  const int v = (int)(prod + offset);
-  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
-__global__ __launch_bounds__(256) void aug_post_kernel(const uint8_t* __restrict__ x, const uint8_t* __restrict__ blur, int H, int W,
-                                                       int crop_h, int crop_w, int out_h, int out_w, const int* __restrict__ rec,
-                                                       const int* __restrict__ lohi, const int* __restrict__ cx, int ksx,
-                                                       const int* __restrict__ cy, int ksy, float* __restrict__ y) {
-  __shared__ uint8_t lut[3][256];
-  const int n = blockIdx.y;
-  const int* r = rec + n * AUG_REC;
-  const int sharp = r[0], contrast = r[1], top = r[2], left = r[3];
-  if (contrast) {
-    for (int i = threadIdx.x; i < 768; i += 256) {
-      const int c = i >> 8;
-      int lo = 255, hi = 0;
-#pragma unroll
-      for (int sl = 0; sl < AUG_SLABS; ++sl) {
-        lo = min(lo, lohi[(n * AUG_SLABS + sl) * 8 + 2 * c]);
-        hi = max(hi, lohi[(n * AUG_SLABS + sl) * 8 + 2 * c + 1]);
-      }
-      lut[c][i & 255] = autocontrast_lut(i & 255, lo, hi);
-    }
-    __syncthreads();
-  }
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= out_h * out_w) return;
-  const int oy = p / out_w, ox = p - oy * out_w;
+// one output pixel of crop → resize → rotate: inverse-rotate (r[4..10]), then the taps of the two resize passes read from
+// `src` (one image, W pixels per row, ends at img_end) at the crop offset, through `lut` when `contrast`.  res = 0 where the
+// rotation samples outside the image.
+__device__ __forceinline__ void aug_geometry_px(const uint8_t* __restrict__ src, const uint8_t* img_end, int W, int top, int left,
+                                                int crop_h, int crop_w, int out_h, int out_w, int ox, int oy, const int* __restrict__ r,
+                                                const int* __restrict__ cx, int ksx, const int* __restrict__ cy, int ksy, bool contrast,
+                                                const uint8_t (*lut)[256], int res[3]) {
   int sx = ox, sy = oy;
   bool inside = true;
   if (r[4]) {
@@ -224,10 +176,8 @@ __global__ __launch_bounds__(256) void aug_post_kernel(const uint8_t* __restrict
     sy = (r[10] + r[8] * ox + r[9] * oy) >> 16;
     inside = sx >= 0 && sx < out_w && sy >= 0 && sy < out_h;
   }
-  int res[3] = {0, 0, 0};
+  res[0] = res[1] = res[2] = 0;
   if (inside) {
-    const uint8_t* src = (sharp ? blur : x) + (size_t)n * H * W * 3;
-    const uint8_t* img_end = src + (size_t)H * W * 3;
     // horizontal pass first (8-bit intermediate), then vertical (Resample.c ImagingResampleInner); an axis whose size
     // does not change is not resampled at all
     const bool rx = crop_w != out_w, ry = crop_h != out_h;
@@ -296,10 +246,64 @@ __global__ __launch_bounds__(256) void aug_post_kernel(const uint8_t* __restrict
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void aug_post_kernel(const uint8_t* __restrict__ x, const uint8_t* __restrict__ blur, int H, int W,
+                                                       int crop_h, int crop_w, int out_h, int out_w, const int* __restrict__ rec,
+                                                       const int* __restrict__ lohi, const int* __restrict__ cx, int ksx,
+                                                       const int* __restrict__ cy, int ksy, float* __restrict__ y) {
+  __shared__ uint8_t lut[3][256];
+  const int n = blockIdx.y;
+  const int* r = rec + n * AUG_REC;
+  const int sharp = r[0], contrast = r[1], top = r[2], left = r[3];
+  if (contrast) aug_build_lut(lut, lohi, n);
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= out_h * out_w) return;
+  const int oy = p / out_w, ox = p - oy * out_w;
+  const uint8_t* src = (sharp ? blur : x) + (size_t)n * H * W * 3;
+  int res[3];
+  aug_geometry_px(src, src + (size_t)H * W * 3, W, top, left, crop_h, crop_w, out_h, out_w, ox, oy, r, cx, ksx, cy, ksy, contrast, lut, res);
   const size_t plane = (size_t)out_h * out_w;
   float* yo = y + (size_t)n * 3 * plane + p;
 #pragma unroll
   for (int c = 0; c < 3; ++c) yo[c * plane] = (float)res[c] / 255.0f;   // ToTensor: float32 division
+}
+
+// ---- geometry-first order (configs/dog_fe/body_dog_fe.py:18-27): crop → resize → rotate to a uint8 image, THEN sharpness and
+// autocontrast on that image (aug_pre_kernel on the rotated result: the blur's frame and the lo / hi see the zero fill), ToTensor
+__global__ __launch_bounds__(256) void aug_geo_kernel(const uint8_t* __restrict__ x, int H, int W, int crop_h, int crop_w, int out_h,
+                                                      int out_w, const int* __restrict__ rec, const int* __restrict__ cx, int ksx,
+                                                      const int* __restrict__ cy, int ksy, uint8_t* __restrict__ g) {
+  const int n = blockIdx.y;
+  const int* r = rec + n * AUG_REC;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= out_h * out_w) return;
+  const int oy = p / out_w, ox = p - oy * out_w;
+  const uint8_t* src = x + (size_t)n * H * W * 3;
+  int res[3];
+  aug_geometry_px(src, src + (size_t)H * W * 3, W, r[2], r[3], crop_h, crop_w, out_h, out_w, ox, oy, r, cx, ksx, cy, ksy, false, nullptr, res);
+  uint8_t* go = g + ((size_t)n * out_h * out_w + p) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) go[c] = (uint8_t)res[c];
+}
+
+__global__ __launch_bounds__(256) void aug_tensor_kernel(const uint8_t* __restrict__ g, const uint8_t* __restrict__ blur, int out_h, int out_w,
+                                                         const int* __restrict__ rec, const int* __restrict__ lohi, float* __restrict__ y) {
+  __shared__ uint8_t lut[3][256];
+  const int n = blockIdx.y;
+  const int sharp = rec[n * AUG_REC + 0], contrast = rec[n * AUG_REC + 1];
+  if (contrast) aug_build_lut(lut, lohi, n);
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const size_t plane = (size_t)out_h * out_w;
+  if (p >= (int)plane) return;
+  const uint8_t* src = (sharp ? blur : g) + ((size_t)n * plane + p) * 3;
+  float* yo = y + (size_t)n * 3 * plane + p;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    int v = src[c];
+    if (contrast) v = lut[c][v];
+    yo[c * plane] = (float)v / 255.0f;   // ToTensor: float32 division
+  }
 }
 
 extern "C" long pfr_augment_ws_bytes(int N, int H, int W) { return (long)N * H * W * 3 + (long)N * AUG_SLABS * 8 * 4 + 256; }
@@ -321,6 +325,37 @@ extern "C" int pfr_augment_train(const unsigned char* x, int N, int H, int W, in
   PFR_CHECK_LAUNCH();
   hipLaunchKernelGGL(aug_post_kernel, dim3((out_h * out_w + 255) / 256, N), dim3(256), 0, st, x, blur, H, W, crop_h, crop_w, out_h,
                      out_w, records, lohi, tx.dev, tx.ksize, ty.dev, ty.ksize, y);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// geometry-first: ws = the uint8 geometry result [N][out_h][out_w][3], then the workspace of aug_pre_kernel over that image
+extern "C" long pfr_augment_geo_ws_bytes(int N, int out_h, int out_w) {
+  return (((long)N * out_h * out_w * 3 + 255) & ~255L) + pfr_augment_ws_bytes(N, out_h, out_w);
+}
+
+extern "C" int pfr_augment_train_geo(const unsigned char* x, int N, int H, int W, int crop_h, int crop_w, int out_h, int out_w,
+                                     const int* records, float* y, void* ws, hipStream_t st) {
+  PFR_CHECK_ARG(x && records && y && ws, "pfr_augment_train_geo: null pointer");
+  PFR_CHECK_ARG(N > 0 && N <= 65535 && crop_h > 0 && crop_w > 0 && crop_h <= H && crop_w <= W && out_h > 0 && out_w > 0,
+                "pfr_augment_train_geo: bad sizes (N=%d %dx%d crop %dx%d out %dx%d)", N, H, W, crop_h, crop_w, out_h, out_w);
+  CoefTable tx, ty;
+  if (!get_coef(crop_w, out_w, &tx) || !get_coef(crop_h, out_h, &ty)) {
+    pfr_set_error("pfr_augment_train_geo: resize %dx%d -> %dx%d needs more than %d taps or table allocation failed", crop_h, crop_w,
+                  out_h, out_w, AUG_MAXK);
+    return PFR_ERR_UNSUPPORTED;
+  }
+  const size_t img = (size_t)N * out_h * out_w * 3;
+  uint8_t* geo = (uint8_t*)ws;
+  uint8_t* blur = geo + ((img + 255) & ~(size_t)255);
+  int* lohi = (int*)(blur + ((img + 255) & ~(size_t)255));
+  const dim3 grid((out_h * out_w + 255) / 256, N);
+  hipLaunchKernelGGL(aug_geo_kernel, grid, dim3(256), 0, st, x, H, W, crop_h, crop_w, out_h, out_w, records, tx.dev, tx.ksize, ty.dev,
+                     ty.ksize, geo);
+  PFR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(aug_pre_kernel, dim3(N, AUG_SLABS), dim3(1024), 0, st, geo, out_h, out_w, records, blur, lohi);
+  PFR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(aug_tensor_kernel, grid, dim3(256), 0, st, geo, blur, out_h, out_w, records, lohi, y);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }

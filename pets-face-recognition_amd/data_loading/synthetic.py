@@ -8,7 +8,7 @@ from torch.utils.data import Dataset
 
 
 class SyntheticRecDataset(Dataset):
-    def __init__(self, n_identities, photos_per_identity, image_size=224, seed=0, noise=0.15, raw_uint8=False, noise_bank=0):
+    def __init__(self, n_identities, photos_per_identity, image_size=224, seed=0, noise=0.15, raw_uint8=False, noise_bank=0, ragged=False):
         self.n_id, self.ppi, self.size, self.seed, self.noise = n_identities, photos_per_identity, image_size, seed, noise
         # noise_bank = K > 0: the per-photo noise comes from K pre-drawn frames (photo i uses frame i % K) instead of a fresh
         # 150 k-sample draw per item — a loader whose per-item cost is that of a cached, already decoded frame (throughput runs)
@@ -19,6 +19,18 @@ class SyntheticRecDataset(Dataset):
         # raw_uint8: hand out the HWC uint8 frame the reference's dataset holds BEFORE its transform (dataset.py:100-121);
         # the augmentation then runs on the device for the whole batch (data_loading/augment.py)
         self.raw_uint8 = raw_uint8
+        # ragged: every item has its own seeded size (sides 64..1400, aspect 1:3..3:1), like the detector's raw crops the reference's
+        # simple / no-align / body configs read; needs raw_uint8 and data_loading.ragged.ragged_collate
+        if ragged and not raw_uint8:
+            raise ValueError("SyntheticRecDataset: ragged=True hands out uint8 HWC frames (raw_uint8=True)")
+        self.ragged = ragged
+        # ragged + noise_bank = K: K whole FRAMES are rendered once, here (slot k: the size and noise of item k, the pattern of identity
+        # k % n_identities) and item i hands out frame i % K — the per-item cost of a cached, already decoded crop.  The content then does
+        # not follow the label: throughput runs only, like noise_bank itself
+        self.frame_bank = None
+        if ragged and noise_bank:
+            bank, self.noise_bank = self.noise_bank, None
+            self.frame_bank = [self._render(k % n_identities, self.item_size(k), bank[k]) for k in range(bank.shape[0])]
         self.labels = torch.arange(n_identities).repeat_interleave(photos_per_identity)
         self.label_map = {u: u for u in range(n_identities)}
         # identity -> dataset indices, the attribute the reference's PairGenerator samples from (dataset.py:93-96)
@@ -33,18 +45,35 @@ class SyntheticRecDataset(Dataset):
     def get_labels(self):
         return self.labels.tolist()
 
-    def _pattern(self, ident):
+    def _pattern(self, ident, hw=None):
         g = torch.Generator().manual_seed(self.seed * 1000003 + ident)
         low = torch.rand(3, 7, 7, generator=g)
-        return torch.nn.functional.interpolate(low[None], size=(self.size, self.size), mode='bilinear', align_corners=False)[0]
+        return torch.nn.functional.interpolate(low[None], size=hw or (self.size, self.size), mode='bilinear', align_corners=False)[0]
+
+    def item_size(self, i):
+        """(H, W) of item i"""
+        if not self.ragged:
+            return self.size, self.size
+        from .ragged import seeded_size
+        return seeded_size(self.seed * 15485863 + i)
+
+    def _render(self, ident, hw, nz):
+        nz = torch.nn.functional.interpolate(nz[None], size=hw, mode='nearest')[0]
+        x = (self._pattern(ident, hw) + nz).clamp_(0, 1)
+        return (x * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous()
 
     def __getitem__(self, i):
         ident = int(self.labels[i])
+        if self.frame_bank is not None:
+            return {'x': self.frame_bank[i % len(self.frame_bank)], 'label': torch.tensor(self.label_map[ident], dtype=torch.int64),
+                    'index': torch.tensor(i, dtype=torch.int64)}
+        hw = self.item_size(i) if self.ragged else None
         if self.noise_bank is not None:
             x = (self._pattern(ident) + self.noise_bank[i % self.noise_bank.shape[0]]).clamp_(0, 1)
         else:
             g = torch.Generator().manual_seed(self.seed * 7919 + i)
-            x = (self._pattern(ident) + self.noise * torch.randn(3, self.size, self.size, generator=g)).clamp_(0, 1)
+            h, w = hw or (self.size, self.size)
+            x = (self._pattern(ident, hw) + self.noise * torch.randn(3, h, w, generator=g)).clamp_(0, 1)
         if self.raw_uint8:
             x = (x * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous()
         return {'x': x, 'label': torch.tensor(self.label_map[ident], dtype=torch.int64), 'index': torch.tensor(i, dtype=torch.int64)}

@@ -52,7 +52,14 @@ class Controller(nn.Module):
     # ------------------------------------------------------------------ steps
     def _images(self, x, train):
         """uint8 [N, H, W, 3] batches are raw frames: the config's device-side Compose pipeline (the reference's
-        train_augmentation / val_augmentation, fe_dogs_config.py:17-32) turns them into the float NCHW batch"""
+        train_augmentation / val_augmentation, fe_dogs_config.py:17-32) turns them into the float NCHW batch.  A dict with 'data'
+        and 'shape' is a ragged batch of raw frames (data_loading/ragged.py) and goes through the same config entries, whose fit
+        stage brings it to the network's canvas first"""
+        if isinstance(x, dict) and 'data' in x and 'shape' in x:
+            aug = self.config.get('device_train_augmentation' if train else 'device_val_augmentation')
+            if aug is None:
+                raise ValueError("ragged image batch but the config defines no device_train_augmentation / device_val_augmentation")
+            return aug(x)
         if x.dtype != torch.uint8:
             return x
         aug = self.config.get('device_train_augmentation' if train else 'device_val_augmentation')
