@@ -10,7 +10,9 @@ import weakref
 
 from .lib import lib, PfrError
 
-# entry kinds of the engines' backward lists (models/_fe_engine.py) → plan kinds
+# entry kinds of the engines' launch lists besides plain (function, args) launches on the main stream = the roles of
+# csrc/pfr_plan.hip; defined here only (the plan builders and the interpreter models/_plan_engine.run_ops import them).
+# MWAIT: a wait that only a grad-ready hook (DDP bucket) needs
 SIDE, FORK, SREC, WAIT, MWAIT = 1, 2, 3, 4, 5
 
 

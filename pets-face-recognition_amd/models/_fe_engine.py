@@ -15,11 +15,13 @@ resnet (/root/reference/losses/__init__.py:38-41 called from engine/controller.p
     tail (BN + projection-BN + residual add + ReLU) is one pass that also writes the ReLU sign as a bit mask, which the two
     backward kernels of the block's last BN and the residual join in conv1's data-gradient epilogue read; inner BNs recompute
     their ReLU mask from scale*x+shift;
-  * a step's launch lists are replayed from C (csrc/pfr_plan.hip) unless PFR_C_PLAN=0 or a launch tracer is installed;
-    two plan slots per input shape allow list inputs (two forwards before one backward), each with its own BN coefficients.
+  * the plan runtime is models/_plan_engine.PlanEngine (shared with the Swin engine): a step's launch lists are replayed from
+    C (csrc/pfr_plan.hip) unless PFR_C_PLAN=0 or a launch tracer is installed; one plan slot per forward pass in flight allows
+    list inputs (two forwards before one backward), each with its own BN coefficients.  This module keeps what is ResNet's:
+    parameter adoption, the plan builders, the folded / graphed inference path and the overwrite / accumulate backward pair.
 """
 import os
-import weakref
+import struct
 
 import torch
 import torch.nn as nn
@@ -27,24 +29,15 @@ import torch.nn as nn
 from .._hip import lib, dtype_id, PfrError
 from .._hip.lib import _TRACER
 from .._hip.ops import conv_out_hw
-from .._hip.cplan import CPlan
-
-_ALIGN = 64  # elements; keeps every parameter 16-byte aligned in both fp32 and bf16 shadows
-
-
-def default_compute_dtype():
-    v = os.environ.get("PFR_COMPUTE_DTYPE", "bf16").lower()
-    return torch.float32 if v in ("f32", "fp32", "float32") else torch.bfloat16
+from .._hip.cplan import SIDE, FORK, SREC, WAIT, MWAIT
+from ._plan_engine import (PlanEngine, Plan, PlanTicket, engine_forward, flat_offsets, default_compute_dtype,  # noqa: F401
+                           _ALIGN, _padded)
 
 
 def flat_layout(model):
     """name -> offset (in elements) of every parameter inside the flat master / gradient buffers, and their length: forward
     (registration) order, each parameter padded to a multiple of _ALIGN elements"""
-    offs, total = {}, 0
-    for name, p in model.named_parameters():
-        offs[name] = total
-        total += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
-    return offs, total
+    return flat_offsets(model.named_parameters())
 
 
 def grad_ready_marks(model):
@@ -69,69 +62,20 @@ class _BN:
     pass
 
 
-# op codes of the backward list besides plain (ctypes function, args) launches on the main stream
-_SIDE, _FORK, _SREC, _WAIT, _MWAIT = 1, 2, 3, 4, 5   # _MWAIT: a wait that only a grad-ready hook (DDP bucket) needs
+class FEEngine(PlanEngine):
+    max_plans = 8
+    bwd_lists = ("bwd0", "bwd1")   # every gradient write has an overwrite and an accumulate variant
 
-
-def _side_with_ddp():
-    """main + side + communication stream + RCCL's internal stream need more than HIP's default 4 hardware queues: with
-    4, two of them share a queue and serialise (measured 9.05 k vs 9.70 k img/s); the package asks for 8 at import."""
-    try:
-        return int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) >= 8
-    except ValueError:
-        return False
-
-
-class PlanTicket:
-    """Held by the autograd node of one forward pass: while it is alive (and its backward has not run) the plan that
-    produced the saved activations is not handed to another forward pass."""
-    __slots__ = ("__weakref__",)
-
-
-class _Plan:
-    __slots__ = ("ops", "bufs", "meta")
-
-    def __init__(self):
-        self.ops = []
-        self.bufs = {}
-        self.meta = {}
-
-    def run(self, stream, hook=None):
-        for fn, args in self.ops:
-            if fn is None:
-                if hook is not None:
-                    hook(*args)
-            else:
-                fn(*args, stream)
-
-
-class FEEngine:
     def __init__(self, model, device, compute_dtype=None):
-        if not str(device).startswith("cuda"):
-            raise PfrError("FEEngine runs on the HIP device only (no CPU fallback)")
-        lib.pfr_version()  # fail loudly if the shared library is missing
-        self.device = torch.device(device)
-        self.dtype = compute_dtype or default_compute_dtype()
-        self.did = dtype_id(self.dtype)
-        self.kp = 8 if self.dtype == torch.bfloat16 else 4
-        self.model_id = id(model)
+        super().__init__(model, device, compute_dtype)
         self.fc_id = id(model.fc)
-        self.plans = {}
-        self.side = None          # side stream of the weight-gradient launches (see build_plan)
-        self.side_events = []
         self.fold_eval = True     # inference: BN folded into the convs (36 k -> 56 k img/s; the unfolded eval plan stays for tests)
         self.fold_w = None
         self.fold_cache = True    # inference: re-fold only when the parameters changed
         self.fold_state = None
         self.graph_eval = os.environ.get("PFR_GRAPH_EVAL", "0") == "1"   # opt-in: inference plans replayed as hipGraphs
-        self.wt_fork = self.wt_ready = None
-        self.wt_pending = False
-        self.side_stream_enabled = os.environ.get("PFR_SIDE_STREAM", "1") != "0"
         # (BN-apply + ReLU fused into the CONSUMER conv's operand prologue cost ~2x the kernel time it saved — the transform is repeated
         #  per tap and per Cout tile — and was retired in round 4: profiles/HISTORY.md; z = relu(BN(c)) is materialised once by pfr_bn_act)
-        # replay the step's launch lists from C (csrc/pfr_plan.hip) instead of a Python loop: ~16 ms -> ~2 ms of host time per
-        # ResNet-50 step (PFR_C_PLAN=0 keeps the interpreter loop; a launch tracer always uses it)
-        self.c_plan = os.environ.get("PFR_C_PLAN", "1") != "0"
         # Opt-in (PFR_FUSE_BNB=1): BatchNorm-backward sums (Σ g·mask, Σ g·mask·x̂) out of the epilogue of the data-gradient launch
         # that produces g (pfr_conv2d_dgrad_bn) instead of a separate pass over g and x (pfr_bn_bwd_reduce).  It removes one
         # read of g per BN layer (-5.7 GB/step) and 45 launches, but MEASURED SLOWER (25.2 vs 23.2 ms/step): the data-gradient
@@ -162,8 +106,6 @@ class FEEngine:
         # (checked without a synchronisation at the start of every forward pass, so the fallback takes effect a step or two later)
         self.gram_flag = torch.zeros(1, dtype=torch.int32).pin_memory()
         self.ws_main = None             # split-K workspace of weight-gradient launches on the MAIN stream (self.ws belongs to the side stream)
-        self.grad_ready_hook = None     # callable(lo, hi): flat-grad range [lo, hi) is final (DDP bucket hook)
-        self.hook_syncs_side = False    # True: the hook makes ITS stream wait for self.side (the main stream then never waits at a mark)
         self.bucket_elems = 6 * 1024 * 1024
         self._adopt(model)
 
@@ -305,18 +247,10 @@ class FEEngine:
         self.fc = f
         self.emb_dim = f.Cout
         self.all_convs = [c for c in self._conv_of.values()] + [f]
-        # wgrad workspace (max over layers is found at plan-build time)
-        self.ws = None
         torch.cuda.synchronize(dev)
 
     def matches(self, model):
-        return (id(model) == self.model_id and id(model.fc) == self.fc_id
-                and self.first_param.data.data_ptr() == self.master.data_ptr())
-
-    def attach_grads(self):
-        """Point every parameter's .grad at its slice of the flat gradient buffer."""
-        for p, gv in self._views.values():
-            p.grad = gv
+        return super().matches(model) and id(model.fc) == self.fc_id
 
     def flat_ranges(self, params):
         """Contiguous [lo, hi) ranges of the flat buffers covered by `params` (for fused optimizers / buckets)."""
@@ -326,7 +260,7 @@ class FEEngine:
             lo = (p.data.data_ptr() - base) // 4
             if lo < 0 or lo >= self.n_flat:
                 raise PfrError("parameter does not belong to this engine")
-            hi = lo + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+            hi = lo + _padded(p.numel())
             spans.append((lo, hi))
         spans.sort()
         out = []
@@ -336,11 +270,6 @@ class FEEngine:
             else:
                 out.append((lo, hi))
         return out
-
-    def _side_ok(self):
-        """Side stream off: PFR_SIDE_STREAM=0; a launch tracer is active (it brackets launches with events on ONE stream);
-        or gradients are being all-reduced (DDP) while fewer than 8 hardware queues are available (see _side_with_ddp)."""
-        return self.side_stream_enabled and _TRACER[0] is None and (self.grad_ready_hook is None or _side_with_ddp())
 
     # ------------------------------------------------------------------------------------------ weights
     def refresh_weights(self, stream, for_backward=True, cast=True):
@@ -354,29 +283,10 @@ class FEEngine:
             lib.pfr_s2d_weight(self.master.data_ptr() + 4 * st.off, self.s2d.w.data_ptr(), self.did, st.Cout, st.Cin, self.s2d.Cin,
                                stream)
         if for_backward:
-            # the flipped / transposed copies are first needed by the backward pass: build them on the side stream,
-            # concurrent with the forward pass (backward() waits for wt_ready)
-            sptr = stream
-            use_side = self._side_ok()
-            if use_side:
-                if self.side is None:
-                    self.side = torch.cuda.Stream(device=self.device)
-                if self.wt_fork is None:
-                    self.wt_fork, self.wt_ready = torch.cuda.Event(), torch.cuda.Event()
-                self.wt_fork.record(torch.cuda.current_stream())
-                self.side.wait_event(self.wt_fork)
-                sptr = self.side.cuda_stream
-            # one launch for every conv's data-gradient weights (descriptor table built once: the pointers are fixed)
-            tab = getattr(self, "_wt_table", None)
-            if tab is None:
-                import struct
-                convs = [c for c in self.all_convs if c.need_wt]
-                raw = b"".join(struct.pack("<QQiiii", c.w.data_ptr(), c.wt.data_ptr(), c.Cout, c.R, c.S, c.Cin) for c in convs)
-                tab = self._wt_table = (torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device), len(convs))
-            lib.pfr_weight_dgrad_layout_batch(tab[0].data_ptr(), tab[1], self.did, sptr)
-            self.wt_pending = use_side
-            if use_side:
-                self.wt_ready.record(self.side)
+            self._refresh_dgrad_layouts(stream)
+
+    def _wt_records(self):
+        return [(c.w.data_ptr(), c.wt.data_ptr(), c.Cout, c.R, c.S, c.Cin) for c in self.all_convs if c.need_wt]
 
     def _use_s2d(self, H, W):
         return self.s2d is not None and H % 2 == 0 and W % 2 == 0
@@ -392,7 +302,6 @@ class FEEngine:
     # ------------------------------------------------------------------------------------------ inference (BN folded)
     def _fold_setup(self):
         """Folded-weight buffers + the descriptor table of pfr_fold_bn (one record per conv/BN pair)."""
-        import struct
         pairs = [self.stem] + [cb for convs, down in self.blocks for cb in convs] + [down for _, down in self.blocks if down]
         if self.s2d is not None:
             pairs.append((self.s2d, self.stem[1]))
@@ -414,7 +323,7 @@ class FEEngine:
             c.bf = self.fold_b[bo:bo + c.Cout]
             rec += struct.pack("<7q2qfi", src, bn.gamma.data_ptr(), bn.beta.data_ptr(), bn.rm.data_ptr(), bn.rv.data_ptr(),
                                c.wf.data_ptr(), c.bf.data_ptr(), c.Cout, K, float(bn.eps), f32)
-            wo += (c.Cout * K + _ALIGN - 1) // _ALIGN * _ALIGN
+            wo += _padded(c.Cout * K)
             bo += c.Cout
         assert len(rec) == 80 * len(pairs)
         self.fold_desc = torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(self.device)
@@ -426,7 +335,7 @@ class FEEngine:
         forward), so a bottleneck is three conv launches: bias + ReLU, and for the last one + shortcut, in the epilogue."""
         if getattr(self, "fold_w", None) is None:
             self._fold_setup()
-        plan = _Plan()
+        plan = Plan()
         ops = plan.ops
         st, _ = self.stem
 
@@ -476,9 +385,7 @@ class FEEngine:
 
     # ------------------------------------------------------------------------------------------ plan building
     def _A(self, plan, shape, dtype=None):
-        t = torch.empty(shape, dtype=dtype or self.dtype, device=self.device)
-        plan.bufs[len(plan.bufs)] = t
-        return t
+        return plan.keep(torch.empty(shape, dtype=dtype or self.dtype, device=self.device))
 
     def _conv_fwd(self, ops, x, xshape, w, y, c, stride, pad, OH, OW, pro=None, part=None, bias=None, idil=0,
                   accumulate=0, Cout=None, R=None, S=None):
@@ -581,7 +488,7 @@ class FEEngine:
         return out
 
     def build_plan(self, N, H, W, train, with_backward):
-        plan = _Plan()
+        plan = Plan()
         ops = plan.ops
         T = self.dtype
         st, stbn = self.stem
@@ -598,7 +505,7 @@ class FEEngine:
         for b in self.bn_list:
             b.coef = torch.zeros((4, b.C), dtype=torch.float32, device=self.device)    # mean, invstd, scale, shift
             b.bcoef = torch.zeros((3, b.C), dtype=torch.float32, device=self.device)   # backward coefficients
-            plan.bufs[len(plan.bufs)] = (b.coef, b.bcoef)
+            plan.keep((b.coef, b.bcoef))
         saved = {}
         # ---- stem: conv 7x7/2 (space-to-depth form when H, W are even) → (BN+ReLU+MaxPool fused)
         if use_s2d:
@@ -719,9 +626,10 @@ class FEEngine:
         # =================================================================== backward (appended after n_fwd)
         # Weight gradients feed nothing downstream until the optimizer, so they run on a SIDE stream, concurrent with the
         # dgrad -> BN-backward chain of the following layers (MFMA/LDS-bound wgrad next to HBM-bound streaming kernels).
-        # Symbolic ops: ("fork", k): side waits for main's current point; ("srec", k): side records "wgrad k done";
-        # ("wait", k): main waits for wgrad k (emitted before a pooled buffer it read is handed out again, before every
+        # Stream roles (_hip/cplan.py): (FORK, k): side waits for main's current point; (SREC, k): side records "wgrad k done";
+        # (WAIT, k): main waits for wgrad k (emitted before a pooled buffer it read is handed out again, before every
         # grad-ready mark and at the end).  The pool is FIFO so that a re-used buffer is the one released longest ago.
+        # Symbolic (resolved by PlanEngine.resolve / _resolve_op): what depends on the workspace pointer or the accumulate flag.
         pool = {}
         lag = 32
         pending = {}   # data_ptr -> index of the last side-stream wgrad that reads this buffer
@@ -740,7 +648,7 @@ class FEEngine:
                     lst.pop(i)
                     if k is not None:
                         del pending[t.data_ptr()]
-                        ops.append(("wait", (k,)))
+                        ops.append((WAIT, k))
                     return t
             return self._A(plan, shape, dtype)
 
@@ -749,7 +657,7 @@ class FEEngine:
 
         ws_need = [0]
 
-        def wgrad(x, xshape, dy, dyshape, c, pro=None, out=None, C=None, acc=0):
+        def wgrad(x, xshape, dy, dyshape, c, pro=None, out=None):
             Nq, Hq, Wq, Cq = xshape
             _, OH, OW, Co = dyshape
             KK = c.R * c.S * Cq
@@ -762,10 +670,11 @@ class FEEngine:
             dst = out if out is not None else c.g
             k = nside[0]
             nside[0] += 1
-            ops.append(("fork", (k,)))
+            ops.append((FORK, k))
+            # (slot 3: split-K workspace, last slot: accumulate flag — both late-bound; a buffer of its own is always overwritten)
             ops.append(("wgrad_noacc" if out is not None else "wgrad", (x.data_ptr(), dy.data_ptr(), dst.data_ptr(), None, self.did, Nq, Hq, Wq, Cq, Co, c.R, c.S,
-                                  c.stride, c.pad, OH, OW, Co, ps, psh, prelu, 1.0, acc)))
-            ops.append(("srec", (k,)))
+                                  c.stride, c.pad, OH, OW, Co, ps, psh, prelu, 1.0, 0)))
+            ops.append((SREC, k))
             pending[dy.data_ptr()] = k
 
         ws_main_need = [0]
@@ -781,12 +690,12 @@ class FEEngine:
                                        c.stride, c.pad, OH, OW, Co, 0, 0, 0, 1.0, 0)))
 
         def side_op(fn, args):
-            """any launch on the side stream (fork / record like a weight gradient) → its index for a later ("wait", k)"""
+            """any launch on the side stream (fork / record like a weight gradient) → its index for a later (WAIT, k)"""
             k = nside[0]
             nside[0] += 1
-            ops.append(("fork", (k,)))
-            ops.append(("sideop", (fn, args)))
-            ops.append(("srec", (k,)))
+            ops.append((FORK, k))
+            ops.append((SIDE, (fn, tuple(args))))
+            ops.append((SREC, k))
             return k
 
         def dgrad(dy, dyshape, c, dx, dxshape, accumulate=0):
@@ -794,7 +703,7 @@ class FEEngine:
             self._conv_fwd(ops, dy, dyshape, c.wt, dx, c, 1, c.R - 1 - c.pad, dxshape[1], dxshape[2], idil=log2,
                            accumulate=accumulate, Cout=c.Cin)
 
-        def bn_bwd(dout, out_act, x, xshape, bn, mask_mode, dx, gres, acc, pre=None):
+        def bn_bwd(dout, out_act, x, xshape, bn, mask_mode, dx, gres, pre=None):
             rows = xshape[0] * xshape[1] * xshape[2]
             C = xshape[3]
             oa = 0 if out_act is None else out_act.data_ptr()
@@ -806,9 +715,9 @@ class FEEngine:
                 ops.append((lib.pfr_bn_bwd_reduce, (dout.data_ptr(), oa, x.data_ptr(), bn.coef[0].data_ptr(), bn.coef[1].data_ptr(),
                                                     bn.coef[2].data_ptr(), bn.coef[3].data_ptr(), mask_mode, self.did, rows, C,
                                                     part.data_ptr())))
-            ops.append((lib.pfr_bn_bwd_finalize, (part.data_ptr(), nb, C, float(rows), bn.gamma.data_ptr(), bn.coef[0].data_ptr(),
-                                                  bn.coef[1].data_ptr(), bn.dgamma.data_ptr(), bn.dbeta.data_ptr(),
-                                                  bn.bcoef.data_ptr(), acc)))
+            ops.append(("acc", (lib.pfr_bn_bwd_finalize, (part.data_ptr(), nb, C, float(rows), bn.gamma.data_ptr(), bn.coef[0].data_ptr(),
+                                                          bn.coef[1].data_ptr(), bn.dgamma.data_ptr(), bn.dbeta.data_ptr(),
+                                                          bn.bcoef.data_ptr()))))
             ops.append((lib.pfr_bn_bwd_apply, (dout.data_ptr(), oa, x.data_ptr(), bn.bcoef.data_ptr(), bn.coef[2].data_ptr(),
                                                bn.coef[3].data_ptr(), mask_mode, dx.data_ptr(),
                                                0 if gres is None else gres.data_ptr(), self.did, rows, C)))
@@ -833,12 +742,12 @@ class FEEngine:
             else:
                 ops.append((lib.pfr_conv2d_dgrad_bn, args))
 
-        acc = 0  # placeholder: _finalize_plan emits an overwrite (0) and an accumulate (1) variant of every grad write
+        # (every gradient write is emitted without its accumulate flag: resolve() makes an overwrite and an accumulate variant)
         # fc
         demb = self._A(plan, (N, self.emb_dim))
         plan.meta["demb"] = demb
         if f.dbias is not None:
-            ops.append(("colsum", (demb.data_ptr(), self.did, N, self.emb_dim, f.dbias.data_ptr(), acc)))
+            ops.append(("colsum", (demb.data_ptr(), self.did, N, self.emb_dim, f.dbias.data_ptr())))
         wgrad(gap, (N, 1, 1, Cf), demb, (N, 1, 1, self.emb_dim), f)
         dgap = G((N, Cf))
         dgrad(demb, (N, 1, 1, self.emb_dim), f, dgap, (N, 1, 1, Cf))
@@ -899,18 +808,18 @@ class FEEngine:
                 C3, K3, rows3 = c3.Cout, c3.Cin, float(oshape[0] * oshape[1] * oshape[2])
                 wgrad_main(z2, zs, dcur, oshape, c3, bnf_G1)                                   # G1 = Gᵀ z2
                 if f["side"] is not None:
-                    ops.append(("wait", (f["side"],)))                                          # G2, zsum (side stream, issued long ago)
+                    ops.append((WAIT, f["side"]))                                          # G2, zsum (side stream, issued long ago)
                 part3, np3 = p3[0]
                 # W = the bf16 weights the forward convolution multiplied with: every term that reconstructs x = z2·Wᵀ (dγ, S, the B-term of
                 # dW) must be built from the x that was actually normalised, not from the fp32 masters
                 Wm = c3.w.data_ptr()
-                ops.append((lib.pfr_bn3_bwd_coef, (part3.data_ptr(), np3, bnf_G1.data_ptr(), f["zsum"].data_ptr(), Wm, self.did, bn3.gamma.data_ptr(),
-                                                   bn3.coef[1].data_ptr(), C3, K3, rows3, bn3.dgamma.data_ptr(), bn3.dbeta.data_ptr(),
-                                                   bnf_coef.data_ptr(), acc)))
+                ops.append(("acc", (lib.pfr_bn3_bwd_coef, (part3.data_ptr(), np3, bnf_G1.data_ptr(), f["zsum"].data_ptr(), Wm, self.did,
+                                                           bn3.gamma.data_ptr(), bn3.coef[1].data_ptr(), C3, K3, rows3, bn3.dgamma.data_ptr(),
+                                                           bn3.dbeta.data_ptr(), bnf_coef.data_ptr()))))
                 np2 = lib.pfr_conv1x1_dgrad2_bn_parts(self.did, zs[0], zs[1], zs[2], C3, K3, K3)
-                ops.append((lib.pfr_bn3_bwd_weights, (bnf_coef.data_ptr(), bnf_G1.data_ptr(), f["G2"].data_ptr(), f["zsum"].data_ptr(), Wm, self.did,
-                                                      C3, K3, rows3, c3.g.data_ptr(), bnf_wat.data_ptr(), 0 if np2 > 0 else bnf_S.data_ptr(),
-                                                      bnf_bias.data_ptr(), acc)))
+                ops.append(("acc", (lib.pfr_bn3_bwd_weights, (bnf_coef.data_ptr(), bnf_G1.data_ptr(), f["G2"].data_ptr(), f["zsum"].data_ptr(), Wm,
+                                                              self.did, C3, K3, rows3, c3.g.data_ptr(), bnf_wat.data_ptr(),
+                                                              0 if np2 > 0 else bnf_S.data_ptr(), bnf_bias.data_ptr()))))
                 release(part3)
                 dz2 = G(zs)
                 if np2 > 0:
@@ -927,11 +836,11 @@ class FEEngine:
                     part2 = G((np2, 2, K3), torch.float32)
                     dgrad_bn(dcur, oshape, c3, dz2, zs, (c2raw, bn2, None, part2), res=y1, wt=bnf_wat)
                     release(y1)
-                bn_bwd(dz2, None, c2raw, zs, bn2, 2, dz2, None, acc, pre=(part2, np2))
+                bn_bwd(dz2, None, c2raw, zs, bn2, 2, dz2, None, pre=(part2, np2))
                 dy, dyshape = dz2, zs
             else:
                 dz3 = G(oshape)
-                bn_bwd(dcur, out, ylast, oshape, lastbn, 3, dz3, None, acc, pre=None if p3 is None else p3[0])
+                bn_bwd(dcur, out, ylast, oshape, lastbn, 3, dz3, None, pre=None if p3 is None else p3[0])
                 dy, dyshape = dz3, oshape
             for i in range(len(convs) - 1 - (1 if free3 else 0), 0, -1):
                 c, bn = convs[i]
@@ -944,11 +853,11 @@ class FEEngine:
                     part = G((npart, 2, xrs[3]), torch.float32)
                     dgrad_bn(dy, dyshape, c, dz, xrs, (xraw, pbn, None, part))
                     release(dy)
-                    bn_bwd(dz, None, xraw, xrs, pbn, 2, dz, None, acc, pre=(part, npart))
+                    bn_bwd(dz, None, xraw, xrs, pbn, 2, dz, None, pre=(part, npart))
                 else:
                     dgrad(dy, dyshape, c, dz, xrs)
                     release(dy)
-                    bn_bwd(dz, None, xraw, xrs, pbn, 2, dz, None, acc)
+                    bn_bwd(dz, None, xraw, xrs, pbn, 2, dz, None)
                 dy, dyshape = dz, xrs
             c0, bn0 = convs[0]
             wgrad(xin, xshape, dy, dyshape, c0)
@@ -963,7 +872,7 @@ class FEEngine:
             if down is not None:
                 dc, dbn = down
                 dgd = G(oshape)
-                bn_bwd(dcur, rmask, cd, oshape, dbn, 3, dgd, None, acc,
+                bn_bwd(dcur, rmask, cd, oshape, dbn, 3, dgd, None,
                        pre=None if (p3 is None or p3[1] is None) else p3[1])      # projection-shortcut BN: g = dcur ∘ mask
                 release(dcur)
                 wgrad(xin, xshape, dgd, oshape, dc)
@@ -1031,15 +940,15 @@ class FEEngine:
         dz = G(s1)
         ops.append((lib.pfr_maxpool_bwd, (dcur.data_ptr(), idx.data_ptr(), dz.data_ptr(), self.did, N, s1[1], s1[2], s1[3])))
         release(dcur)
-        bn_bwd(dz, None, c1, s1, stbn, 2, dz, None, acc)
+        bn_bwd(dz, None, c1, s1, stbn, 2, dz, None)
         if use_s2d:
             wgrad(x_nhwc, xin_shape, dz, s1, self.s2d, out=self.s2d.g)
-            ops.append(("wait", (nside[0] - 1,)))   # the un-packing below reads what the stem wgrad wrote
-            ops.append(("s2dunpack", (self.s2d.g.data_ptr(), st.g.data_ptr(), st.Cout, st.Cin, self.s2d.Cin, acc)))
+            ops.append((WAIT, nside[0] - 1))   # the un-packing below reads what the stem wgrad wrote
+            ops.append(("acc", (lib.pfr_s2d_wgrad, (self.s2d.g.data_ptr(), st.g.data_ptr(), st.Cout, st.Cin, self.s2d.Cin))))
         else:
             wgrad(x_nhwc, xin_shape, dz, s1, st, out=st.g_pad)
-            ops.append(("wait", (nside[0] - 1,)))   # the un-padding copy below reads what the stem wgrad wrote
-            ops.append(("copy2d", (st.g_pad.data_ptr(), self.cp, st.g.data_ptr(), st.Cin, st.Cout * st.R * st.S, st.Cin, 1.0, acc)))
+            ops.append((WAIT, nside[0] - 1))   # the un-padding copy below reads what the stem wgrad wrote
+            ops.append(("acc", (lib.pfr_copy2d_f32, (st.g_pad.data_ptr(), self.cp, st.g.data_ptr(), st.Cin, st.Cout * st.R * st.S, st.Cin, 1.0))))
         self._mark(ops, 0)
         plan.meta["n_side"] = nside[0]
         # workspace
@@ -1054,18 +963,16 @@ class FEEngine:
 
     def _mark(self, ops, off):
         # gradients of flat offsets >= off are final once main has also seen the side stream's latest wgrad
-        last = max((a[0] for f, a in ops if f == "srec"), default=None)
+        last = max((a for f, a in ops if f == SREC), default=None)
         if last is not None:
             # off == 0 is the end of the backward pass: always joined.  Intermediate marks only matter to a bucket hook.
-            ops.append(("wait" if off == 0 else "mwait", (last,)))
+            ops.append((WAIT if off == 0 else MWAIT, last))
         ops.append((None, (off,)))
 
     # ------------------------------------------------------------------------------------------ execution
-    def _check_tuning(self):
+    def _retune(self, changed):
         """A plan bakes kernel choices in (statistics-partial granularity, partial-row counts of the fused BatchNorm sums, which
-        blocks take the BN-input-free form).  When a pfr_set_tuning call changed a knob since the plans were built — another engine,
-        a test, a host sweep — this engine's own mode is re-asserted and every plan no forward pass still owns is rebuilt."""
-        ep = lib.pfr_tuning_epoch()
+        blocks take the BN-input-free form): after a foreign pfr_set_tuning call this engine's own mode is re-asserted."""
         stale = False
         if self.gram_stats and int(self.gram_flag[0]) != 0:
             import warnings
@@ -1073,95 +980,28 @@ class FEEngine:
                           "falling back to the statistics pass over conv3's output for the rest of the run")
             self.gram_stats = False
             stale = True
-        if ep == self._tuning_epoch and not stale:
-            return
-        lib.pfr_set_tuning(b"bnb", self.fuse_bnb)
-        self._tuning_epoch = lib.pfr_tuning_epoch()
-        for k, q in list(self.plans.items()):
-            if not self._plan_busy(q):
-                self.plans.pop(k)
+        if changed or stale:
+            lib.pfr_set_tuning(b"bnb", self.fuse_bnb)
+        return stale
 
-    def get_plan(self, N, H, W, train, with_backward, slot=0):
-        self._check_tuning()
-        key = (N, H, W, train, with_backward) + ((slot,) if slot else ())
-        p = self.plans.get(key)
-        if p is None:
-            if len(self.plans) >= 8:
-                # evict the oldest plan that no forward pass in flight still owns
-                for k, q in list(self.plans.items()):
-                    if not self._plan_busy(q):
-                        self.plans.pop(k)
-                        break
-            if not train and not with_backward and self.fold_eval:
-                p = self.build_eval_plan(N, H, W)
-            else:
-                p = self.build_plan(N, H, W, train, with_backward)
-                self._finalize_plan(p)
-            self.plans[key] = p
-        return p
+    def _new_plan(self, N, H, W, train, with_backward):
+        if not train and not with_backward and self.fold_eval:
+            return self.build_eval_plan(N, H, W)
+        return super()._new_plan(N, H, W, train, with_backward)
 
-    @staticmethod
-    def _plan_busy(plan):
-        own = plan.meta.get("owner")
-        return own is not None and own() is not None
-
-    def acquire_plan(self, N, H, W, train, with_backward, ticket):
-        """A plan owns the activation buffers its backward pass reads.  Two training forwards before a backward (list input of
-        SoftmaxBasedMetricLearning — reference losses/__init__.py:39 — or any two-view step) therefore get DIFFERENT plan
-        instances ("slots"); a slot is free again when its backward ran or its autograd node died."""
-        slot = 0
-        while True:
-            plan = self.get_plan(N, H, W, train, with_backward, slot)
-            if ticket is None or not self._plan_busy(plan):
-                break
-            slot += 1
-            if slot >= 8:
-                raise PfrError("more than 8 forward passes of one shape are waiting for their backward pass")
-        if ticket is not None:
-            plan.meta["owner"] = weakref.ref(ticket)
-        return plan
-
-    def _finalize_plan(self, plan):
-        """Resolve symbolic ops (workspace pointer, accumulate flag) into two concrete op lists."""
-        fwd = plan.ops[:plan.meta["n_fwd"]]
-        bwd = plan.ops[plan.meta["n_fwd"]:]
-        plan.meta["fwd"] = fwd
-        for acc in (0, 1):
-            res = []
-            for fn, args in bwd:
-                if fn in ("wgrad", "wgrad_noacc"):
-                    a = list(args)
-                    a[3] = self.ws.data_ptr()
-                    a[-1] = acc if fn == "wgrad" else 0
-                    res.append((_SIDE, (lib.pfr_conv2d_wgrad, tuple(a))))
-                elif fn == "wgrad_main":
-                    a = list(args)
-                    a[3] = self.ws_main.data_ptr() if self.ws_main is not None else 0
-                    res.append((lib.pfr_conv2d_wgrad, tuple(a)))
-                elif fn == "sideop":
-                    res.append((_SIDE, (args[0], tuple(args[1]))))
-                elif fn == "fork":
-                    res.append((_FORK, args[0]))
-                elif fn == "srec":
-                    res.append((_SREC, args[0]))
-                elif fn == "wait":
-                    res.append((_WAIT, args[0]))
-                elif fn == "mwait":
-                    res.append((_MWAIT, args[0]))
-                elif fn == "colsum":
-                    res.append((lib.pfr_colsum, tuple(args[:-1]) + (acc, 0)))
-                elif fn == "copy2d":
-                    res.append((lib.pfr_copy2d_f32, tuple(args[:-1]) + (acc,)))
-                elif fn == "s2dunpack":
-                    res.append((lib.pfr_s2d_wgrad, tuple(args[:-1]) + (acc,)))
-                elif fn is lib.pfr_bn_bwd_finalize or fn is lib.pfr_bn3_bwd_coef \
-                        or fn is lib.pfr_bn3_bwd_weights:
-                    res.append((fn, tuple(args[:-1]) + (acc,)))
-                else:
-                    res.append((fn, args))
-            plan.meta["bwd%d" % acc] = res
-            plan.meta.pop("c_bwd%d" % acc, None)
-        plan.meta["ws_ptr"] = self._ws_key()
+    def _resolve_op(self, fn, args, acc):
+        """the late-bound forms besides PlanEngine.resolve's own ("wgrad", "acc")"""
+        if fn == "wgrad_noacc":      # a weight-gradient GEMM into a buffer of its own (never accumulates)
+            a = list(args)
+            a[3] = self.ws.data_ptr()
+            return (SIDE, (lib.pfr_conv2d_wgrad, tuple(a)))
+        if fn == "wgrad_main":       # ... on the main stream, with the main stream's split-K workspace
+            a = list(args)
+            a[3] = self.ws_main.data_ptr() if self.ws_main is not None else 0
+            return (lib.pfr_conv2d_wgrad, tuple(a))
+        if fn == "colsum":
+            return (lib.pfr_colsum, tuple(args) + (acc, 0))
+        return super()._resolve_op(fn, args, acc)
 
     def _ws_key(self):
         """the split-K workspaces a resolved plan has baked in (side stream, main stream)"""
@@ -1174,10 +1014,10 @@ class FEEngine:
             x = x.float()
         x = x.contiguous()
         N, _, H, W = x.shape
-        plan = self.acquire_plan(N, H, W, train, with_backward, ticket if with_backward else None)
+        plan = self.acquire_plan(N, H, W, train, with_backward, ticket=ticket if with_backward else None)
         plan.meta["epoch"] = self._tuning_epoch     # the knobs this forward pass (and the launches its backward replays) ran under
-        if with_backward and plan.meta.get("ws_ptr", 0) != self._ws_key():
-            self._finalize_plan(plan)
+        if with_backward:
+            self._fresh(plan)
         if plan.meta.get("folded") and self.graph_eval and _TRACER[0] is None:
             return self._forward_graphed(plan, x)
         stream = torch.cuda.current_stream().cuda_stream
@@ -1194,25 +1034,11 @@ class FEEngine:
             if plan.meta.get("folded"):
                 lib.pfr_fold_bn(self.fold_desc.data_ptr(), self.fold_n, self.did, stream)
         self._input_layout(plan, x, stream)
-        if not self._run_list(plan, "fwd", stream):
-            for fn, args in plan.meta["fwd"]:
-                fn(*args, stream)
+        self._run_fwd(plan, stream)
         if train:
             self.nbt.add_(1)
         self._last_plan = plan
         return plan.meta["emb"]
-
-    def _run_list(self, plan, key, stream, side=0, hook=None, n_events=0):
-        """replays plan.meta[key] (a launch list) — through the C executor when possible"""
-        if self.c_plan and _TRACER[0] is None:
-            ck = "c_" + key
-            cp = plan.meta.get(ck, False)
-            if cp is False:
-                cp = plan.meta[ck] = CPlan.compile(plan.meta[key], n_events)
-            if cp is not None:
-                cp.run(stream, side, hook, self.hook_syncs_side)
-                return True
-        return False
 
     def _eval_launches(self, plan, xin):
         """weight refresh + BN fold + input layout + every launch of the inference plan, on the current stream"""
@@ -1221,9 +1047,7 @@ class FEEngine:
         self.refresh_weights(stream, for_backward=False)
         lib.pfr_fold_bn(self.fold_desc.data_ptr(), self.fold_n, self.did, stream)
         self._input_layout(plan, xin, stream)
-        if not self._run_list(plan, "fwd", stream):
-            for fn, args in plan.meta["fwd"]:
-                fn(*args, stream)
+        self._run_fwd(plan, stream)
 
     def _forward_graphed(self, plan, x):
         """Opt-in (PFR_GRAPH_EVAL=1): the inference plan replayed as ONE hipGraph, captured on the second call (the first
@@ -1252,42 +1076,6 @@ class FEEngine:
         self._last_plan = plan
         return m["emb"]
 
-    def _run_bwd_ops(self, plan, acc, hook):
-        main = torch.cuda.current_stream()
-        stream = main.cuda_stream
-        use_side = self._side_ok()
-        if use_side and self.side is None:
-            self.side = torch.cuda.Stream(device=self.device)
-        side_handle = self.side.cuda_stream if use_side else 0
-        if self._run_list(plan, "bwd%d" % acc, stream, side_handle,
-                          (lambda off: hook(off)) if hook is not None else None, 2 * plan.meta.get("n_side", 0)):
-            return
-        if use_side:
-            side, sptr = self.side, self.side.cuda_stream
-            ev = self.side_events
-            while len(ev) < 2 * plan.meta.get("n_side", 0):
-                ev.append(torch.cuda.Event())
-        for fn, args in plan.meta["bwd%d" % acc]:
-            if fn is None:
-                if hook is not None:
-                    hook(args[0])
-            elif fn.__class__ is int:
-                if not use_side:
-                    if fn == _SIDE:
-                        args[0](*args[1], stream)
-                elif fn == _SIDE:
-                    args[0](*args[1], sptr)
-                elif fn == _FORK:
-                    e = ev[2 * args]
-                    e.record(main)
-                    side.wait_event(e)
-                elif fn == _SREC:
-                    ev[2 * args + 1].record(side)
-                elif fn == _WAIT or (hook is not None and not self.hook_syncs_side):
-                    main.wait_event(ev[2 * args + 1])
-            else:
-                fn(*args, stream)
-
     def backward(self, demb, plan=None):
         plan = plan if plan is not None else self._last_plan
         if lib.pfr_tuning_epoch() != plan.meta.get("epoch", self._tuning_epoch):
@@ -1295,16 +1083,8 @@ class FEEngine:
             # sums, which blocks dropped conv3's output): replaying it under other knobs would compute wrong sums silently
             raise PfrError("a pfr_set_tuning call changed a kernel-selection knob between this forward pass and its backward pass "
                            "(another engine with a different PFR_FUSE_BNB mode, or a host sweep): run forward again")
-        stream = torch.cuda.current_stream().cuda_stream
-        demb = demb.contiguous()
-        if demb.numel() != plan.meta["demb"].numel():
-            raise PfrError(f"backward: gradient of {tuple(demb.shape)} does not match the plan's embedding buffer "
-                           f"{tuple(plan.meta['demb'].shape)}")
-        if plan.meta.get("ws_ptr", 0) != self._ws_key():
-            self._finalize_plan(plan)   # the shared weight-gradient workspace grew after this plan was resolved
-        lib.pfr_cast(demb.data_ptr(), dtype_id(demb.dtype), plan.meta["demb"].data_ptr(), self.did, demb.numel(), stream)
+        self._begin_backward(plan, demb)
         acc = 1 if self.first_param.grad is not None else 0
-        plan.meta["owner"] = None
         # gradients are final (DDP bucket hook) only when no other forward pass still waits for its backward
         hook = self.grad_ready_hook if not any(self._plan_busy(q) for q in self.plans.values()) else None
         if hook is None and self.grad_ready_hook is not None and not getattr(self, "_warned_hook", False):
@@ -1312,37 +1092,10 @@ class FEEngine:
             self._warned_hook = True
             warnings.warn("FEEngine.backward: another forward pass of this model still holds its activations (a retained autograd "
                           "graph?), so gradient buckets are reduced after the backward pass instead of overlapped with it")
-        main = torch.cuda.current_stream()
-        if self.wt_pending:
-            main.wait_event(self.wt_ready)
-            self.wt_pending = False
-        self._run_bwd_ops(plan, acc, hook)
+        self._run_bwd(plan, self.bwd_lists[acc], hook, self.grad_ready_hook)
         if not acc:
             self.attach_grads()
 
 
-class _FEFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        eng = model.hip_engine(x.device)
-        ctx.ticket = PlanTicket()
-        emb = eng.forward(x, model.training, True, ctx.ticket)  # only reached when a backward pass can follow (see fe_forward)
-        ctx.eng = eng
-        ctx.plan = eng._last_plan
-        ctx.nparams = len(params)
-        return emb.clone()
-
-    @staticmethod
-    def backward(ctx, demb):
-        if ctx.plan.meta.get("owner") is None or ctx.plan.meta["owner"]() is not ctx.ticket:
-            raise PfrError("backward: the activations of this forward pass were released (double backward?)")
-        ctx.eng.backward(demb, ctx.plan)
-        # parameter gradients are delivered by side effect into the flat gradient buffer (p.grad views)
-        return (None, None) + (None,) * ctx.nparams
-
-
 def fe_forward(model, x):
-    eng = model.hip_engine(x.device)
-    if torch.is_grad_enabled() and any(p.requires_grad for p in eng.param_list):
-        return _FEFunction.apply(x, model, *eng.param_list)
-    return eng.forward(x, model.training, False).clone()
+    return engine_forward(model, x, model.training)

@@ -2,7 +2,8 @@
 
 Counterpart of /root/reference/models/swin.py:196-225 (`SwinTransformer.forward`) + autograd for BASELINE config 4.
 Same design as models/_fe_engine.FEEngine: flat fp32 master / gradient buffers (the module's nn.Parameters become views,
-state-dict names unchanged), compute-dtype shadow, one pre-built plan of C-ABI calls per input shape.
+state-dict names unchanged), compute-dtype shadow, one pre-built plan of C-ABI calls per input shape; the plan runtime (plan
+cache, resolve, replay on two streams, autograd wrapper) is models/_plan_engine.PlanEngine.
 
 Mapping (tokens are kept NHWC = [B, H, W, C] end to end; the reference's NCHW↔NHWC permutes between stages vanish):
   PatchMerging (Unfold + Linear, swin.py:155-167)  → stride-f conv on NHWC (weights re-laid out per step)
@@ -11,16 +12,13 @@ Mapping (tokens are kept NHWC = [B, H, W, C] end to end; the reference's NCHW↔
                                                      pfr_conv2d_wgrad, data gradient through pfr_conv2d_fwd
   cyclic shift, window partition, masks            → addressing / analytic mask inside the attention kernel
 """
-import os
-import weakref
+import struct
 
 import torch
-import torch.nn as nn
 
 from .._hip import lib, dtype_id, PfrError
-from .._hip.lib import _TRACER
-from .._hip.cplan import CPlan
-from ._fe_engine import default_compute_dtype, _ALIGN, _SIDE, _FORK, _SREC, _WAIT, _MWAIT, _side_with_ddp, PlanTicket
+from .._hip.cplan import SIDE, FORK, SREC, WAIT, MWAIT
+from ._plan_engine import PlanEngine, Plan, engine_forward, flat_offsets
 
 
 class _Lin:
@@ -31,42 +29,23 @@ class _LN:
     pass
 
 
-class SwinEngine:
+class SwinEngine(PlanEngine):
+    max_plans = 6
+
     def __init__(self, model, device, compute_dtype=None):
-        if not str(device).startswith("cuda"):
-            raise PfrError("SwinEngine runs on the HIP device only (no CPU fallback)")
-        lib.pfr_version()
-        self.device = torch.device(device)
-        self.dtype = compute_dtype or default_compute_dtype()
-        self.did = dtype_id(self.dtype)
-        self.kp = 8 if self.dtype == torch.bfloat16 else 4
-        self.model_id = id(model)
-        self.plans = {}
-        self.side = None          # side stream of the weight-gradient / column-sum launches (see build_plan)
-        self.side_events = []
+        super().__init__(model, device, compute_dtype)
         self.fuse_gelu = True
-        self.wt_fork = self.wt_ready = None
-        self.wt_pending = False
-        self.hook_syncs_side = False
-        # replay the launch lists from C (csrc/pfr_plan.hip) instead of the interpreter loop (PFR_C_PLAN=0 keeps the loop; a launch
-        # tracer always uses it)
-        self.c_plan = os.environ.get("PFR_C_PLAN", "1") != "0"
         # buffers per (shape, dtype) class of the backward pool before one that a side-stream op still reads is re-used (HBM is
         # plentiful; a shallow pool makes the main stream wait for the side stream at almost every layer)
         self.pool_depth = 48
         self.ln_dxsum = True   # bias gradients from the LayerNorm-backward pass that produced their input
-        self.side_stream_enabled = os.environ.get("PFR_SIDE_STREAM", "1") != "0"
-        self.grad_ready_hook = None
         self._adopt(model)
 
     # ------------------------------------------------------------------------------------------ parameters
     def _adopt(self, model):
         dev = self.device
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
-        offs, total = {}, 0
-        for name, p in named:
-            offs[name] = total
-            total += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+        offs, total = flat_offsets(named)
         self.n_flat = total
         self.master = torch.zeros(total, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -156,15 +135,7 @@ class SwinEngine:
         self.head_fc = lin("mlp_head.1", model.mlp_head[1])
         self.emb_dim = self.head_fc.out
         self.cp = self.stages[0]["pm"].cinp
-        self.ws = None
         torch.cuda.synchronize(dev)
-
-    def matches(self, model):
-        return id(model) == self.model_id and self.first_param.data.data_ptr() == self.master.data_ptr()
-
-    def attach_grads(self):
-        for p, gv in self._views.values():
-            p.grad = gv
 
     def _all_lins(self):
         for st in self.stages:
@@ -181,48 +152,25 @@ class SwinEngine:
             if r.f is not None:   # Unfold order (c, kh, kw) → conv layout [out][kh][kw][c(padded)]
                 lib.pfr_nchw_to_nhwc(self.master.data_ptr() + 4 * r.off, r.w.data_ptr(), self.did, r.out, r.cin, r.f * r.f, 1,
                                      r.cinp, stream)
-        if not for_backward:
-            return
-        # data-gradient layouts are first needed by backward(): build them on the side stream, concurrent with forward
-        sptr = stream
-        use_side = self.side_stream_enabled and _TRACER[0] is None and (self.grad_ready_hook is None or _side_with_ddp())
-        if use_side:
-            if self.side is None:
-                self.side = torch.cuda.Stream(device=self.device)
-            if self.wt_fork is None:
-                self.wt_fork, self.wt_ready = torch.cuda.Event(), torch.cuda.Event()
-            self.wt_fork.record(torch.cuda.current_stream())
-            self.side.wait_event(self.wt_fork)
-            sptr = self.side.cuda_stream
-        # one launch for every layer's data-gradient weights (descriptor table built once: the pointers are fixed)
-        tab = getattr(self, "_wt_table", None)
-        if tab is None:
-            import struct
-            recs = []
-            for r in self._all_lins():
-                if r.f is not None:
-                    if r is not self.stages[0]["pm"]:
-                        recs.append((r.w.data_ptr(), r.wt.data_ptr(), r.out, r.f, r.f, r.cinp))
-                else:
-                    recs.append((r.w.data_ptr(), r.wt.data_ptr(), r.out, 1, 1, r.inp))
-            raw = b"".join(struct.pack("<QQiiii", *rec) for rec in recs)
-            tab = self._wt_table = (torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device), len(recs))
-        lib.pfr_weight_dgrad_layout_batch(tab[0].data_ptr(), tab[1], self.did, sptr)
-        self.wt_pending = use_side
-        if use_side:
-            self.wt_ready.record(self.side)
+        if for_backward:
+            self._refresh_dgrad_layouts(stream)
+
+    def _wt_records(self):
+        for r in self._all_lins():
+            if r.f is None:
+                yield (r.w.data_ptr(), r.wt.data_ptr(), r.out, 1, 1, r.inp)
+            elif r is not self.stages[0]["pm"]:      # (the first patch merging has no data gradient)
+                yield (r.w.data_ptr(), r.wt.data_ptr(), r.out, r.f, r.f, r.cinp)
 
     # ------------------------------------------------------------------------------------------ plan
     def build_plan(self, N, H, W, with_backward):
         T, dev, did = self.dtype, self.device, self.did
+        plan = Plan()
         fwd, bwd = [], []
-        bufs = []
         tab_recs = []
 
         def A(shape, dtype=None):
-            t = torch.empty(shape, dtype=dtype or T, device=dev)
-            bufs.append(t)
-            return t
+            return plan.keep(torch.empty(shape, dtype=dtype or T, device=dev))
 
         def gemm(ops, x, rows, cin, r, y, bias=True, residual=None, w=None):
             ops.append((lib.pfr_conv2d_fwd, (x.data_ptr(), (w if w is not None else r.w).data_ptr(), y.data_ptr(), did,
@@ -245,8 +193,6 @@ class SwinEngine:
             ops.append((lib.pfr_conv2d_fwd, (dy.data_ptr(), r.wt.data_ptr(), dx.data_ptr(), did, did, rows, 1, 1, r.out, r.inp, 1,
                                              1, 1, 0, 0, 1, 1, r.inp, 0, 0, 0, 0, 0, 0, 0, 0)))
 
-        cs_need = [0]
-
         pend_cs = []   # column sums whose final merge is deferred to the next flush: (partials, out, partial rows, C, tile height | 0, rows)
 
         def colsum(ops, x, rows, C, out, dt=None):
@@ -255,20 +201,18 @@ class SwinEngine:
             d = dt if dt is not None else did
             n = lib.pfr_colsum_parts(d, rows, C)
             if n <= 0:   # a few hundred rows: one small kernel does it all
-                side(ops, ("side", (lib.pfr_colsum, (x.data_ptr(), d, rows, C, out.data_ptr(), 0, 0))), x)
+                side(ops, (SIDE, (lib.pfr_colsum, (x.data_ptr(), d, rows, C, out.data_ptr(), 0, 0))), x)
                 return
             ws = A((lib.pfr_colsum_ws_floats(rows, C),), torch.float32)   # its own workspace: alive until the batched final
-            side(ops, ("side", (lib.pfr_colsum_partial, (x.data_ptr(), d, rows, C, ws.data_ptr()))), x)
+            side(ops, (SIDE, (lib.pfr_colsum_partial, (x.data_ptr(), d, rows, C, ws.data_ptr()))), x)
             pend_cs.append((ws, out, n, C, 0, 0))
 
         def flush_colsums(ops):
             if not pend_cs:
                 return
-            import struct
             raw = b"".join(struct.pack("<QQiiiiii", ws.data_ptr(), out.data_ptr(), n, C, 0, mt, rws, 0) for ws, out, n, C, mt, rws in pend_cs)
-            tab = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
-            bufs.append(tab)
-            side(ops, ("side", (lib.pfr_colsum_final_batch, (tab.data_ptr(), len(pend_cs), max(e[3] for e in pend_cs)))))
+            tab = plan.keep(torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev))
+            side(ops, (SIDE, (lib.pfr_colsum_final_batch, (tab.data_ptr(), len(pend_cs), max(e[3] for e in pend_cs)))))
             del pend_cs[:]
 
         x_nhwc = A((N, H, W, self.cp))
@@ -325,19 +269,19 @@ class SwinEngine:
         gemm(fwd, hln, N, Cf, self.head_fc, emb)
         # the bias(+mask) tables of every attention block in one launch at the head of the forward pass (their inputs, the relative-position
         # tables, only change in the optimiser step)
-        import struct
-        tabd = torch.frombuffer(bytearray(b"".join(struct.pack("<QQii", *r) for r in tab_recs)), dtype=torch.uint8).to(dev)
-        bufs.append(tabd)
+        tabd = plan.keep(torch.frombuffer(bytearray(b"".join(struct.pack("<QQii", *r) for r in tab_recs)), dtype=torch.uint8).to(dev))
         fwd.insert(0, (lib.pfr_window_bias_table_batch, (tabd.data_ptr(), len(tab_recs))))
-        plan = {"fwd": fwd, "bufs": bufs, "x_nhwc": x_nhwc, "emb": emb}
+        plan.ops = fwd
+        plan.meta.update(x_nhwc=x_nhwc, emb=emb, n_fwd=len(fwd))
         if not with_backward:
             return plan
 
         # ================================================================= backward
         # Weight gradients, bias / LayerNorm-parameter / position-table column sums feed nothing before the optimizer: they run on
-        # a SIDE stream (≈ 150 short launches per step that would otherwise sit in the dependency chain).  Symbolic ops:
-        # ("fork", k) side waits for main's current point; ("srec", k) side records "op k done"; ("wait", k) main waits
+        # a SIDE stream (≈ 150 short launches per step that would otherwise sit in the dependency chain).  Stream roles
+        # (_hip/cplan.py): (FORK, k) side waits for main's current point; (SREC, k) side records "op k done"; (WAIT, k) main waits
         # for op k — emitted before a pooled buffer that op k read is handed out again, before grad-ready marks and at the end.
+        # Only the weight gradients stay symbolic ("wgrad": PlanEngine.resolve fills the split-K workspace pointer in).
         pool = {}
         nalloc = {}
         pending = {}      # data_ptr of a pooled buffer -> last side op that reads it
@@ -354,7 +298,7 @@ class SwinEngine:
                 nalloc[key] = nalloc.get(key, 0) + 1
                 return A(shape, dtype)
             t = lst.pop(0)
-            bwd.append(("wait", (pending.pop(t.data_ptr()),)))
+            bwd.append((WAIT, pending.pop(t.data_ptr())))
             return t
 
         def release(t):
@@ -366,16 +310,16 @@ class SwinEngine:
             pool.setdefault((tuple(t.shape), t.dtype), []).append(t)
 
         def side(ops, op, *reads):
-            if ops and ops[-1][0] == "srec":
+            if ops and ops[-1][0] == SREC:
                 # no main-stream launch since the previous side op: it joins that op's fork (every fork is an event recorded on the
                 # main stream, i.e. a marker packet in front of the next kernel of the dependency chain)
-                k = ops.pop()[1][0]
+                k = ops.pop()[1]
             else:
                 k = nside[0]
                 nside[0] += 1
-                ops.append(("fork", (k,)))
+                ops.append((FORK, k))
             ops.append(op)
-            ops.append(("srec", (k,)))
+            ops.append((SREC, k))
             for r in reads:
                 side_reads.append((k, r.data_ptr()))
 
@@ -402,7 +346,7 @@ class SwinEngine:
                 colsum(ops, g, rows, C, dbias)
 
         demb = A((N, self.emb_dim))
-        plan["demb"] = demb
+        plan.meta["demb"] = demb
         hf = self.head_fc
         if hf.dbias is not None:
             colsum(bwd, demb, N, hf.out, hf.dbias)
@@ -416,7 +360,7 @@ class SwinEngine:
         dz = G(cshape)
         bwd.append((lib.pfr_avgpool_bwd, (dpooled.data_ptr(), dz.data_ptr(), did, N, Hh * Ww, Cf)))
         release(dpooled)
-        bwd.append((None, (offs_head := self.offs["mlp_head.0.weight"],)))
+        bwd.append((None, (self.offs["mlp_head.0.weight"],)))
         for si in range(len(self.stages) - 1, -1, -1):
             st, srec = self.stages[si], saved[si]
             Nn, OH, OW, C = srec["shape"]
@@ -485,7 +429,7 @@ class SwinEngine:
                 bias_grad(bwd, dz, rows, C, pm.dbias, dz_sum)
             g_conv = pm.g_conv
             wgrad(bwd, srec["in"], (Ni, Hi, Wi, Ci), dz, (N, OH, OW, C), pm, f, f, g_conv)
-            side(bwd, ("side", (lib.pfr_nhwc_to_nchw_f32, (g_conv.data_ptr(), pm.g.data_ptr(), pm.out, pm.cin, f * f, pm.cinp, 0))))
+            side(bwd, (SIDE, (lib.pfr_nhwc_to_nchw_f32, (g_conv.data_ptr(), pm.g.data_ptr(), pm.out, pm.cin, f * f, pm.cinp, 0))))
             if si > 0:
                 din = G((Ni, Hi, Wi, Ci))
                 bwd.append((lib.pfr_conv2d_fwd, (dz.data_ptr(), pm.wt.data_ptr(), din.data_ptr(), did, did, N, OH, OW, C, Ci, f, f, 1,
@@ -495,83 +439,12 @@ class SwinEngine:
             dz_sum = None
             flush_colsums(bwd)
             if nside[0]:   # everything the side stream was given so far is final (end of backward, or a DDP bucket boundary)
-                bwd.append(("wait" if si == 0 else "mwait", (nside[0] - 1,)))
+                bwd.append((WAIT if si == 0 else MWAIT, nside[0] - 1))
             bwd.append((None, (st["off"],)))
-        plan["n_side"] = nside[0]
+        plan.meta["n_side"] = nside[0]
         if self.ws is None or self.ws.numel() < ws_need[0]:
             self.ws = torch.empty(ws_need[0], dtype=torch.float32, device=dev)
-        if getattr(self, "cs_ws", None) is None or self.cs_ws.numel() < cs_need[0]:
-            self.cs_ws = torch.empty(max(1, cs_need[0]), dtype=torch.float32, device=dev)
-        plan["bwd_sym"] = bwd
-        return plan
-
-    def _finalize(self, plan):
-        res = []
-        for fn, args in plan["bwd_sym"]:
-            if fn == "wgrad":
-                a = list(args)
-                a[3] = self.ws.data_ptr()
-                res.append((_SIDE, (lib.pfr_conv2d_wgrad, tuple(a))))
-            elif fn == "colsum":
-                res.append((_SIDE, (lib.pfr_colsum, tuple(args[:-1]) + (self.cs_ws.data_ptr(),))))
-            elif fn == "side":
-                res.append((_SIDE, args))
-            elif fn == "fork":
-                res.append((_FORK, args[0]))
-            elif fn == "srec":
-                res.append((_SREC, args[0]))
-            elif fn == "wait":
-                res.append((_WAIT, args[0]))
-            elif fn == "mwait":
-                res.append((_MWAIT, args[0]))
-            else:
-                res.append((fn, args))
-        plan["bwd"] = res
-        plan.pop("c_bwd", None)
-        plan["ws_ptr"] = (self.ws.data_ptr(), self.cs_ws.data_ptr())
-
-    def get_plan(self, N, H, W, with_backward, slot=0):
-        ep = lib.pfr_tuning_epoch()
-        if ep != getattr(self, "_tuning_epoch", None):
-            # a pfr_set_tuning call changed a knob: the plans baked tile heights / kernel choices in — rebuild those not in flight
-            if hasattr(self, "_tuning_epoch"):
-                for k, q in list(self.plans.items()):
-                    if not self._plan_busy(q):
-                        self.plans.pop(k)
-            self._tuning_epoch = ep
-        key = (N, H, W, with_backward) + ((slot,) if slot else ())
-        p = self.plans.get(key)
-        if p is None:
-            if len(self.plans) >= 6:
-                for k, q in list(self.plans.items()):
-                    if not self._plan_busy(q):
-                        self.plans.pop(k)
-                        break
-            p = self.build_plan(N, H, W, with_backward)
-            if with_backward:
-                self._finalize(p)
-            self.plans[key] = p
-        elif with_backward and p["ws_ptr"] != (self.ws.data_ptr(), self.cs_ws.data_ptr()):
-            self._finalize(p)
-        return p
-
-    @staticmethod
-    def _plan_busy(plan):
-        own = plan.get("owner")
-        return own is not None and own() is not None
-
-    def acquire_plan(self, N, H, W, with_backward, ticket):
-        """one plan instance ("slot") per forward pass that still waits for its backward — see FEEngine.acquire_plan"""
-        slot = 0
-        while True:
-            plan = self.get_plan(N, H, W, with_backward, slot)
-            if ticket is None or not self._plan_busy(plan):
-                break
-            slot += 1
-            if slot >= 8:
-                raise PfrError("more than 8 forward passes of one shape are waiting for their backward pass")
-        if ticket is not None:
-            plan["owner"] = weakref.ref(ticket)
+        plan.ops = fwd + bwd
         return plan
 
     def forward(self, x, with_backward, ticket=None):
@@ -579,112 +452,31 @@ class SwinEngine:
             raise PfrError(f"expected NCHW input with {self.in_channels} channels, got {tuple(x.shape)}")
         x = x.float().contiguous()
         N, _, H, W = x.shape
-        plan = self.acquire_plan(N, H, W, with_backward, ticket if with_backward else None)
+        plan = self.acquire_plan(N, H, W, with_backward, ticket=ticket if with_backward else None)
+        if with_backward:
+            self._fresh(plan)
         stream = torch.cuda.current_stream().cuda_stream
         self.refresh_weights(stream, for_backward=with_backward)
-        lib.pfr_nchw_to_nhwc(x.data_ptr(), plan["x_nhwc"].data_ptr(), self.did, N, x.shape[1], H, W, self.cp, stream)
-        if not self._run_c(plan, "fwd", stream):
-            for fn, args in plan["fwd"]:
-                fn(*args, stream)
-        self._last = plan
-        return plan["emb"]
-
-    def _run_c(self, plan, key, stream, side=0, hook=None, n_events=0):
-        """replay plan[key] through the C executor when possible (same contract as FEEngine._run_list)"""
-        if not self.c_plan or _TRACER[0] is not None:
-            return False
-        ck = "c_" + key
-        cp = plan.get(ck, False)
-        if cp is False:
-            cp = plan[ck] = CPlan.compile(plan[key], n_events)
-        if cp is None:
-            return False
-        cp.run(stream, side, hook, self.hook_syncs_side)
-        return True
+        lib.pfr_nchw_to_nhwc(x.data_ptr(), plan.meta["x_nhwc"].data_ptr(), self.did, N, x.shape[1], H, W, self.cp, stream)
+        self._run_fwd(plan, stream)
+        self._last_plan = plan
+        return plan.meta["emb"]
 
     def backward(self, demb, plan=None):
-        plan = plan if plan is not None else self._last
-        stream = torch.cuda.current_stream().cuda_stream
-        demb = demb.contiguous()
-        if demb.numel() != plan["demb"].numel():
-            raise PfrError(f"backward: gradient of {tuple(demb.shape)} does not match the plan's embedding buffer "
-                           f"{tuple(plan['demb'].shape)}")
-        if plan["ws_ptr"] != (self.ws.data_ptr(), self.cs_ws.data_ptr()):
-            self._finalize(plan)
+        plan = plan if plan is not None else self._last_plan
+        self._begin_backward(plan, demb)
         # Every gradient kernel of this engine OVERWRITES its slice of the flat buffer.  When gradients are already present
         # (a second backward before zero_grad: gradient accumulation, list inputs) the previous sum is set aside and added
         # back afterwards — two extra passes over the 110 MB buffer, only on that path.
         prev = self.grad.clone() if self.first_param.grad is not None else None
-        plan["owner"] = None
-        lib.pfr_cast(demb.data_ptr(), dtype_id(demb.dtype), plan["demb"].data_ptr(), self.did, demb.numel(), stream)
         hook = self.grad_ready_hook
         if prev is not None or any(self._plan_busy(q) for q in self.plans.values()):
             hook = None   # not final yet (accumulating, or another forward pass still waits for its backward)
-        main = torch.cuda.current_stream()
-        if self.wt_pending:
-            main.wait_event(self.wt_ready)
-            self.wt_pending = False
-        # side stream off: PFR_SIDE_STREAM=0, a launch tracer is active, or gradients are all-reduced (see FEEngine._side_ok)
-        use_side = self.side_stream_enabled and _TRACER[0] is None and (hook is None or _side_with_ddp())
-        if use_side and self.side is None:
-            self.side = torch.cuda.Stream(device=self.device)
-        if self._run_c(plan, "bwd", stream, self.side.cuda_stream if use_side else 0,
-                       (lambda off: hook(off)) if hook is not None else None, 2 * plan.get("n_side", 0)):
-            if prev is not None:
-                self.grad.add_(prev)
-            self.attach_grads()
-            return
-        if use_side:
-            side, sptr = self.side, self.side.cuda_stream
-            ev = self.side_events
-            while len(ev) < 2 * plan.get("n_side", 0):
-                ev.append(torch.cuda.Event())
-        for fn, args in plan["bwd"]:
-            if fn is None:
-                if hook is not None:
-                    hook(args[0])
-            elif fn.__class__ is int:
-                if not use_side:
-                    if fn == _SIDE:
-                        args[0](*args[1], stream)
-                elif fn == _SIDE:
-                    args[0](*args[1], sptr)
-                elif fn == _FORK:
-                    e = ev[2 * args]
-                    e.record(main)
-                    side.wait_event(e)
-                elif fn == _SREC:
-                    ev[2 * args + 1].record(side)
-                elif fn == _WAIT or (hook is not None and not self.hook_syncs_side):
-                    main.wait_event(ev[2 * args + 1])
-            else:
-                fn(*args, stream)
+        # (the side-stream decision follows the hook IN EFFECT: no bucket is reduced during this pass when it is None)
+        self._run_bwd(plan, "bwd", hook, hook)
         if prev is not None:
             self.grad.add_(prev)
         self.attach_grads()
 
 
-class _SwinFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, model, *params):
-        eng = model.hip_engine(x.device)
-        ctx.ticket = PlanTicket()
-        emb = eng.forward(x, True, ctx.ticket)
-        ctx.eng = eng
-        ctx.plan = eng._last
-        ctx.nparams = len(params)
-        return emb.clone()
-
-    @staticmethod
-    def backward(ctx, demb):
-        if ctx.plan.get("owner") is None or ctx.plan["owner"]() is not ctx.ticket:
-            raise PfrError("backward: the activations of this forward pass were released (double backward?)")
-        ctx.eng.backward(demb, ctx.plan)
-        return (None, None) + (None,) * ctx.nparams
-
-
-def swin_forward(model, x):
-    eng = model.hip_engine(x.device)
-    if torch.is_grad_enabled() and any(p.requires_grad for p in eng.param_list):
-        return _SwinFunction.apply(x, model, *eng.param_list)
-    return eng.forward(x, False).clone()
+swin_forward = engine_forward
