@@ -23,12 +23,22 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('-c', '--config', required=True, type=Path)
     ap.add_argument('--checkpoint', type=Path, default=None, help='state_dict with keys model_loss.module.* (optional)')
+    ap.add_argument('--averaged', action='store_true',
+                    help="evaluate the checkpoint's averaged weights: `averaged_state_dict` of its .trainer sidecar (Trainer(ema_decay=))")
     args = ap.parse_args(argv)
     config = get_config(args.config)
     controller = Controller(config)
+    if args.averaged and args.checkpoint is None:
+        ap.error('--averaged needs --checkpoint')
     if args.checkpoint is not None:
-        sd = torch.load(args.checkpoint, map_location='cpu')
-        sd = sd.get('state_dict', sd)
+        if args.averaged:
+            side = torch.load(str(args.checkpoint) + '.trainer', map_location='cpu')
+            if 'averaged_state_dict' not in side:
+                raise SystemExit(f'{args.checkpoint}.trainer holds no averaged_state_dict (was the run trained with ema_decay?)')
+            sd = side['averaged_state_dict']
+        else:
+            sd = torch.load(args.checkpoint, map_location='cpu')
+            sd = sd.get('state_dict', sd)
         missing, unexpected = controller.load_state_dict(sd, strict=False)
         print('loaded', args.checkpoint, 'missing', len(missing), 'unexpected', len(unexpected))
     trainer = configure_trainer(config, None, None)

@@ -340,6 +340,22 @@ int pfr_sgd_step_clip(float* p, const float* g, float* mom, void* shadow, int sh
 int pfr_adamw_step_clip(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, size_t n, float lr,
                         float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                         const float* clip_coef, float clip_value, pfr_stream_t stream);
+/* the _clip steps with a weight average folded in (clip_coef == NULL and clip_value == 0: no clipping): after the update, in the same
+ * pass, avg <- lerp(avg, p_new, avg_weight), replacing torch.optim.swa_utils.AveragedModel.update_parameters' `torch._foreach_lerp_`
+ * after optimizer.step().  avg_weight 1 copies (an AveragedModel's first update), 1 - decay is an EMA, 1 / (n_averaged + 1) SWA's
+ * running mean.  torch.lerp's form: avg + w (p - avg) for w < 0.5, else p - (p - avg)(1 - w).  p, the optimizer state and the
+ * shadow come out as from the _clip steps (without clipping: as from the plain steps), bit for bit.  avg: fp32 [n], laid out like p.
+ * One launch each. */
+int pfr_sgd_step_avg(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
+                     float weight_decay, float grad_scale, int first_step, const float* clip_coef, float clip_value, float* avg,
+                     float avg_weight, pfr_stream_t stream);
+int pfr_adamw_step_avg(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, size_t n, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                       const float* clip_coef, float clip_value, float* avg, float avg_weight, pfr_stream_t stream);
+/* the same lerp on its own: avg <- lerp(avg, p, weight) over n floats (`avg.lerp_(p, weight)`; SWA's per-epoch update, parameters
+ * outside a flat run, BatchNorm's cumulative moving average).  Any n, any 4-byte-aligned pointers (16-byte accesses where avg and
+ * p share an alignment phase); nothing beyond n is read or written; no atomics. */
+int pfr_weight_avg(float* avg, const float* p, size_t n, float weight, pfr_stream_t stream);
 /* gradient norm over nseg dense fp32 segments (one per parameter), replacing torch.nn.utils.clip_grad_norm_'s
  * `torch._foreach_norm(grads, p)` + `vector_norm(stack(norms), p)` + clip coefficient, and PL's per-parameter grad_norm().
  * segs: device table [nseg] of {const float* ptr; int64 n; int64 first_chunk; int64 chunks} with chunks = ceil(n / chunk_elems),

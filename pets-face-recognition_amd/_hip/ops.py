@@ -373,3 +373,27 @@ def grad_norm(segs, chunk_seg, nseg, nchunks, norm_p, max_norm, ws, out):
 
 def grad_norm_chunk_elems():
     return lib.pfr_grad_norm_chunk_elems()
+
+
+# ------------------------------------------------------------------------------------------------ weight averaging (EMA / SWA)
+def sgd_step_avg(p, g, mom, shadow, lr, momentum, weight_decay, clip_coef, clip_value, avg, avg_weight, grad_scale=1.0,
+                 first_step=False):
+    """sgd_step_clip (clip_coef None and clip_value 0: no clipping) + avg <- lerp(avg, p_new, avg_weight) in the same pass"""
+    lib.pfr_sgd_step_avg(_p(p), _p(g), _p(mom), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),
+                         float(lr), float(momentum), float(weight_decay), float(grad_scale), int(first_step), _p(clip_coef),
+                         float(clip_value), _p(avg), float(avg_weight), _stream())
+
+
+def adamw_step_avg(p, g, m, v, shadow, lr, beta1, beta2, eps, weight_decay, step, clip_coef, clip_value, avg, avg_weight,
+                   grad_scale=1.0):
+    lib.pfr_adamw_step_avg(_p(p), _p(g), _p(m), _p(v), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype),
+                           p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+                           float(grad_scale), _p(clip_coef), float(clip_value), _p(avg), float(avg_weight), _stream())
+
+
+def weight_avg(avg, p, weight):
+    """avg <- lerp(avg, p, weight) in place: dense fp32 CUDA tensors of one size (any offset into their storage)"""
+    if avg.dtype != torch.float32 or p.dtype != torch.float32 or avg.numel() != p.numel():
+        raise PfrError("weight_avg: fp32 tensors of one size expected")
+    _chk(avg, "avg"); _chk(p, "p")
+    lib.pfr_weight_avg(_p(avg), _p(p), avg.numel(), float(weight), _stream())

@@ -32,7 +32,7 @@ def _live(key, default):
 def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs, device, n_epochs=1, seed=0,
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
          noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
-         ragged=False, pipeline='head'):
+         ragged=False, pipeline='head', trainer_extra=None):
     # pipeline: which of the reference's three Compose shapes runs on the device (data_loading/augment.py): 'head' (uniform frames),
     # 'simple' / 'body' (ragged frames: the detector's raw crops, each with its own size)
     if pipeline not in ('head', 'simple', 'body'):
@@ -139,7 +139,7 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         pair_generator=pair_generator, similarity_f=similarity_f, model=model, loss=loss, optimizer=optimizer,
         train_dataloader=train_dataloader, val_dataloader=val_dataloader,
         trainer_kwargs=dict(benchmark=True, limit_train_batches=limit_train_batches, limit_val_batches=limit_val_batches,
-                            **clip_kwargs),
+                            **clip_kwargs, **(trainer_extra or {})),
         output=output, experiment_name='Synthetic', run_name=f'{arch} synthetic',
         device=device, distributed_train=not isinstance(device, str),
         world_size=len(device) if not isinstance(device, str) else None))

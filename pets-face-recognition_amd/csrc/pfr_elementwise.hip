@@ -1825,14 +1825,22 @@ __device__ __forceinline__ float clip_grad(float gv, float c, float clipv) {
   return gv;
 }
 
-template <typename TS, bool CLIP = false>
+// AVG: an averaged copy of the parameters (EMA / SWA) follows the update in the same pass, a <- lerp(a, p_new, aw) in torch.lerp's
+// two-branch form (aw = 1 copies exactly; omw = 1 - aw); the AVG = false instantiations are the steps as they were
+__device__ __forceinline__ float wavg_lerp(float a, float w, float aw, float omw) {
+  const float d = w - a;
+  return aw < 0.5f ? fmaf(aw, d, a) : fmaf(-d, omw, w);
+}
+
+template <typename TS, bool CLIP = false, bool AVG = false>
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mom, TS* __restrict__ shadow,
                            size_t n, float lr, float momentum, float wd, float gscale, int first, const float* __restrict__ coef,
-                           float clipv) {
+                           float clipv, float* __restrict__ avg = nullptr, float aw = 0.f) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const float c = CLIP && coef ? *coef : 1.f;
+  const float omw = 1.f - aw;
   const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(mom) |
-                     reinterpret_cast<uintptr_t>(shadow)) & 15) == 0;
+                     reinterpret_cast<uintptr_t>(shadow) | (AVG ? reinterpret_cast<uintptr_t>(avg) : 0)) & 15) == 0;
   const size_t n4 = vec ? n / 4 : 0;
   const bool use_mom = momentum != 0.f;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -1849,6 +1857,12 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
     }
     if (use_mom) reinterpret_cast<f32x4*>(mom)[i] = b;
     reinterpret_cast<f32x4*>(p)[i] = w;
+    if constexpr (AVG) {
+      f32x4 a = reinterpret_cast<const f32x4*>(avg)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a[e] = wavg_lerp(a[e], w[e], aw, omw);
+      reinterpret_cast<f32x4*>(avg)[i] = a;
+    }
     if (shadow) {
       if constexpr (sizeof(TS) == 2) {
         bf16x4 v;
@@ -1870,6 +1884,7 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
     }
     w = fmaf(-lr, b, w);
     p[i] = w;
+    if constexpr (AVG) avg[i] = wavg_lerp(avg[i], w, aw, omw);
     if (shadow) shadow[i] = from_f32<TS>(w);
   }
 }
@@ -1959,6 +1974,119 @@ extern "C" int pfr_adamw_step_clip(float* p, const float* g, float* m, float* v,
   else
     hipLaunchKernelGGL((adamw_kernel<float, true>), dim3(blocks), dim3(256), 0, st, p, g, m, v, (float*)shadow, n, lr, beta1, beta2, eps, weight_decay, bc1,
                        bc2, grad_scale, clip_coef, clip_value);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// the _clip steps + the weight average in the same pass (torch.optim.swa_utils.AveragedModel.update_parameters after optimizer.step())
+extern "C" int pfr_sgd_step_avg(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr,
+                                float momentum, float weight_decay, float grad_scale, int first_step, const float* clip_coef,
+                                float clip_value, float* avg, float avg_weight, hipStream_t st) {
+  PFR_CHECK_ARG(p && g && avg && (momentum == 0.f || mom), "pfr_sgd_step_avg: null pointer");
+  PFR_CHECK_ARG(clip_value >= 0.f, "pfr_sgd_step_avg: clip_value must be >= 0 (0 = no clamp)");
+  PFR_CHECK_ARG(avg_weight >= 0.f && avg_weight <= 1.f, "pfr_sgd_step_avg: avg_weight must be in [0, 1]");
+  if (n == 0) return PFR_OK;
+  unsigned blocks = (unsigned)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  // no clipping asked for: the CLIP = false arithmetic, so that the update is pfr_sgd_step's bit for bit (not only pfr_sgd_step_clip's)
+  const bool clip = clip_coef != nullptr || clip_value > 0.f;
+  const bool bf = shadow && shadow_dtype == PFR_BF16;
+#define PFR_SGD_AVG(TS, CLIP)                                                                                                      \
+  hipLaunchKernelGGL((sgd_kernel<TS, CLIP, true>), dim3(blocks), dim3(256), 0, st, p, g, mom, (TS*)shadow, n, lr, momentum,         \
+                     weight_decay, grad_scale, first_step, clip_coef, clip_value, avg, avg_weight)
+  if (bf && clip) PFR_SGD_AVG(bf16_t, true);
+  else if (bf) PFR_SGD_AVG(bf16_t, false);
+  else if (clip) PFR_SGD_AVG(float, true);
+  else PFR_SGD_AVG(float, false);
+#undef PFR_SGD_AVG
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+// standalone weight average avg <- lerp(avg, p, weight) over n floats (no padding assumed): a scalar head up to avg's first 16-byte
+// boundary, 16-byte loads / stores while p shares avg's alignment phase, a scalar tail; all scalar when the phases differ
+__global__ void weight_avg_kernel(float* __restrict__ avg, const float* __restrict__ p, size_t n, float aw) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  const float omw = 1.f - aw;
+  size_t head = n;
+  if (((reinterpret_cast<uintptr_t>(avg) ^ reinterpret_cast<uintptr_t>(p)) & 15) == 0) {
+    head = ((16 - (reinterpret_cast<uintptr_t>(avg) & 15)) & 15) / 4;
+    if (head > n) head = n;
+  }
+  for (size_t i = tid; i < head; i += stride) avg[i] = wavg_lerp(avg[i], p[i], aw, omw);
+  const size_t n4 = (n - head) / 4;
+  f32x4* a4 = reinterpret_cast<f32x4*>(avg + head);
+  const f32x4* p4 = reinterpret_cast<const f32x4*>(p + head);
+  for (size_t i = tid; i < n4; i += stride) {
+    f32x4 a = a4[i];
+    const f32x4 w = p4[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] = wavg_lerp(a[e], w[e], aw, omw);
+    a4[i] = a;
+  }
+  for (size_t i = head + 4 * n4 + tid; i < n; i += stride) avg[i] = wavg_lerp(avg[i], p[i], aw, omw);
+}
+extern "C" int pfr_weight_avg(float* avg, const float* p, size_t n, float weight, hipStream_t st) {
+  PFR_CHECK_ARG(avg && p, "pfr_weight_avg: null pointer");
+  PFR_CHECK_ARG(((reinterpret_cast<uintptr_t>(avg) | reinterpret_cast<uintptr_t>(p)) & 3) == 0, "pfr_weight_avg: pointers must be 4-byte aligned");
+  PFR_CHECK_ARG(weight >= 0.f && weight <= 1.f, "pfr_weight_avg: weight must be in [0, 1]");
+  if (n == 0) return PFR_OK;
+  unsigned blocks = (unsigned)((n / 4 + 255) / 256 + 1);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(weight_avg_kernel, dim3(blocks), dim3(256), 0, st, avg, p, n, weight);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// AdamW + average in one pass.  adamw_kernel leaves its arithmetic to the compiler's FMA contraction, and an instantiation of it with
+// the lerp added was contracted differently (exp_avg_sq 1 ulp apart), so this kernel spells out, with contraction off, the
+// operations the compiler emits for adamw_kernel (all four instantiations alike): g' = clip(g * gscale); v = fma(b2, v, g' * ((1 - b2)
+// * g')); m = fma(b1, m, (1 - b1) * g'); p = fma(fma(-lr, wd, 1), p, -((lr / bc1) * m) / (sqrt(v) / sqrt(bc2) + eps)).  p, m, v and
+// the shadow are adamw_kernel's bit for bit (tests/test_weight_avg_gpu.py compares them).  If a compiler upgrade contracts adamw_kernel
+// differently that test fails although neither kernel is wrong: re-derive this spelled-out form from adamw_kernel's new ISA (or write
+// adamw_kernel itself with explicit fmaf, so that both share one definition).  Scalar accesses like adamw_kernel's; its cost is unmeasured.
+template <typename TS, bool CLIP>
+__global__ void adamw_avg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                 TS* __restrict__ shadow, size_t n, float lr, float b1, float b2, float eps, float wd,
+                                 float bc1, float bc2, float gscale, const float* __restrict__ coef, float clipv,
+                                 float* __restrict__ avg, float aw) {
+#pragma clang fp contract(off)
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const float c = CLIP && coef ? *coef : 1.f;
+  const float decay = fmaf(-lr, wd, 1.f), lrb = lr / bc1, sq2 = sqrtf(bc2), omb1 = 1.f - b1, omb2 = 1.f - b2, omw = 1.f - aw;
+  for (; i < n; i += stride) {
+    const float gr = clip_grad<CLIP>(g[i] * gscale, c, clipv);
+    const float vv = fmaf(b2, v[i], gr * (omb2 * gr));
+    const float mm = fmaf(b1, m[i], omb1 * gr);
+    m[i] = mm;
+    v[i] = vv;
+    const float denom = sqrtf(vv) / sq2 + eps;
+    const float w = fmaf(decay, p[i], -((lrb * mm) / denom));
+    p[i] = w;
+    avg[i] = wavg_lerp(avg[i], w, aw, omw);
+    if (shadow) shadow[i] = from_f32<TS>(w);
+  }
+}
+extern "C" int pfr_adamw_step_avg(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, size_t n,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                  const float* clip_coef, float clip_value, float* avg, float avg_weight, hipStream_t st) {
+  PFR_CHECK_ARG(p && g && m && v && avg && step >= 1, "pfr_adamw_step_avg: bad args");
+  PFR_CHECK_ARG(clip_value >= 0.f, "pfr_adamw_step_avg: clip_value must be >= 0 (0 = no clamp)");
+  PFR_CHECK_ARG(avg_weight >= 0.f && avg_weight <= 1.f, "pfr_adamw_step_avg: avg_weight must be in [0, 1]");
+  if (n == 0) return PFR_OK;
+  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+  unsigned blocks = (unsigned)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  const bool clip = clip_coef != nullptr || clip_value > 0.f;     // (as in pfr_sgd_step_avg)
+  const bool bf = shadow && shadow_dtype == PFR_BF16;
+#define PFR_ADAMW_AVG(TS, CLIP)                                                                                                    \
+  hipLaunchKernelGGL((adamw_avg_kernel<TS, CLIP>), dim3(blocks), dim3(256), 0, st, p, g, m, v, (TS*)shadow, n, lr, beta1, beta2,    \
+                     eps, weight_decay, bc1, bc2, grad_scale, clip_coef, clip_value, avg, avg_weight)
+  if (bf && clip) PFR_ADAMW_AVG(bf16_t, true);
+  else if (bf) PFR_ADAMW_AVG(bf16_t, false);
+  else if (clip) PFR_ADAMW_AVG(float, true);
+  else PFR_ADAMW_AVG(float, false);
+#undef PFR_ADAMW_AVG
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }

@@ -12,6 +12,32 @@ step (loops/train_loop.py:13-38); evaluation outputs are handed over as List[dat
 `gradient_clip_val` / `gradient_clip_algorithm` / `track_grad_norm` as in PL 1.5 (trainer.py:73-74,87,481-505), in the order of
 its OptimizerLoop._track_and_norm_grad: backward -> gradient all-reduce -> track -> clip -> optimizer.step.
 
+Weight averaging (off by default; the two modes exclude each other; both average the parameters of `optims[0]`):
+
+`ema_decay=d`, 0 < d < 1: avg <- d * avg + (1 - d) * p after every optimizer step (the first step copies), inside the fused
+optimizer's update kernel on the HIP path, `torch._foreach_lerp_` on the CPU path.  Validation and `test()` run on the averaged
+parameters (inside `swap_averaged()`) with the LIVE BatchNorm running statistics, the usual EMA practice: an EMA follows the live
+weights closely enough for their statistics.  The checkpoint holds the live weights as before; its `.trainer` sidecar also holds
+`averaged_state_dict`, a state dict with the reference's key names made of the averaged parameters and the live buffers
+(`eval_fe.py --averaged` loads it).
+
+`stochastic_weight_avg=True` with `swa_epoch_start=0.8`, `swa_lrs=None`, `annealing_epochs=10`, `annealing_strategy='cos'`
+(PL 1.5's names and defaults).  The contract is torch.optim.swa_utils' own:
+  1. from epoch s = int(swa_epoch_start * max_epochs) on (an int swa_epoch_start is s itself) the config's schedulers no longer
+     step; a `SWALR(optims[0], swa_lr, anneal_epochs=annealing_epochs, anneal_strategy=annealing_strategy)` is built at the start of
+     epoch s and steps at the end of every epoch from s on; swa_lr per group is `swa_lrs` (a float or one per group) or the group's
+     lr at that moment;
+  2. `update_average()` (running mean, AveragedModel's default) runs at the end of every epoch from s on, before SWALR's step;
+  3. after the last epoch the average is swapped in, `utils.update_bn` re-estimates the BatchNorm statistics over the train
+     loader (limit_train_batches applies) and the result stays as the model's weights (and is what the last checkpoint holds).
+Where this may differ from PL's StochasticWeightAveraging callback: the epoch bookkeeping around s (PL starts its SWALR and takes
+its first average one epoch apart, and skips the BatchNorm pass's batches differently); the arithmetic of each piece is torch's.
+The per-epoch learning rates of the last fit() are kept in `lr_history`.
+Resume: `n_averaged` and the average travel in the optimizer's state dict (fused) or the sidecar's `weight_average` (torch
+optimizers), SWALR's state in the sidecar's `swa_lr`; `resume_from_checkpoint` continues the average.  Under DDP every rank
+averages its own, identical weights: no collective for the average.  SWA's final BatchNorm pass runs on each rank's shard of the
+train loader; the buffers are then synchronised once (rank 0's statistics, as before every evaluation).
+
 Distributed = one process per GPU started by torchrun (RANK / LOCAL_RANK / WORLD_SIZE), RCCL all-reduce of the flat
 gradient buffer in buckets overlapped with backward (engine/ddp.py)."""
 import os
@@ -46,7 +72,8 @@ class Trainer:
                  callbacks=None, num_sanity_val_steps=0, limit_train_batches=None, limit_val_batches=None,
                  check_val_every_n_epoch=1, log_every_n_steps=50, benchmark=None, fast_dev_run=False, prefetch_batches=2,
                  resume_from_checkpoint=None, resume_weights_only=False, gradient_clip_val=None, gradient_clip_algorithm=None,
-                 track_grad_norm=-1, **_ignored):
+                 track_grad_norm=-1, ema_decay=None, stochastic_weight_avg=False, swa_epoch_start=0.8, swa_lrs=None,
+                 annealing_epochs=10, annealing_strategy='cos', **_ignored):
         # PL 1.5's checks (reference engine/trainer.py:481-505; its MisconfigurationException is a ValueError here)
         if gradient_clip_val is not None and not isinstance(gradient_clip_val, (int, float)):
             raise TypeError(f"`gradient_clip_val` should be an int or a float. Got {gradient_clip_val}.")
@@ -58,6 +85,26 @@ class Trainer:
         if track_grad_norm != -1 and not ((isinstance(track_grad_norm, (int, float)) or track_grad_norm == 'inf')
                                           and float(track_grad_norm) > 0):
             raise ValueError(f"`track_grad_norm` must be a positive number or 'inf' (infinity norm). Got {track_grad_norm}.")
+        if ema_decay is not None and not (isinstance(ema_decay, (int, float)) and not isinstance(ema_decay, bool)
+                                          and 0.0 < float(ema_decay) < 1.0):
+            raise ValueError(f"`ema_decay` must be a float in (0, 1). Got {ema_decay}.")
+        if ema_decay is not None and stochastic_weight_avg:
+            raise ValueError("`ema_decay` and `stochastic_weight_avg` are two weight averages of the same parameters: set one of them.")
+        if stochastic_weight_avg:
+            if isinstance(swa_epoch_start, bool) or not ((isinstance(swa_epoch_start, int) and swa_epoch_start >= 1)
+                                                         or (isinstance(swa_epoch_start, float) and 0.0 <= swa_epoch_start <= 1.0)):
+                raise ValueError(f"`swa_epoch_start` should be a positive integer or a float between 0 and 1. Got {swa_epoch_start}.")
+            if annealing_strategy not in ('cos', 'linear'):
+                raise ValueError(f"`annealing_strategy` should be 'cos' or 'linear'. Got {annealing_strategy}.")
+            if not (isinstance(annealing_epochs, int) and annealing_epochs >= 0):
+                raise ValueError(f"`annealing_epochs` should be a non-negative integer. Got {annealing_epochs}.")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.stochastic_weight_avg = bool(stochastic_weight_avg)
+        self.swa_epoch_start, self.swa_lrs = swa_epoch_start, swa_lrs
+        self.annealing_epochs, self.annealing_strategy = annealing_epochs, annealing_strategy
+        self.lr_history = []          # [lr of every param group of optims[0]] during each epoch of the last fit()
+        self._averager = None         # the fused optimizer itself or an optim.WeightAverage (set by fit())
+        self._loop_state = {}
         self.gradient_clip_val = gradient_clip_val
         self.gradient_clip_algorithm = 'norm' if gradient_clip_algorithm is None else gradient_clip_algorithm.lower()
         self.track_grad_norm = float(track_grad_norm)
@@ -124,13 +171,64 @@ class Trainer:
         return device
 
     # ------------------------------------------------------------------ checkpoint / resume
-    def _save_checkpoint(self, controller, optims, scheds, epoch):
+    def _save_checkpoint(self, controller, optims, scheds, epoch, swalr=None):
         root = Path(self.root)
         root.mkdir(parents=True, exist_ok=True)
         torch.save(controller.state_dict(), root / f'epoch={epoch}.ckpt')
-        torch.save({'epoch': epoch + 1, 'global_step': self.global_step,
-                    'optimizer_states': [o.state_dict() for o in optims],
-                    'lr_schedulers': [s.state_dict() for s in scheds]}, root / f'epoch={epoch}.ckpt.trainer')
+        loop = {'epoch': epoch + 1, 'global_step': self.global_step,
+                'optimizer_states': [o.state_dict() for o in optims],
+                'lr_schedulers': [s.state_dict() for s in scheds]}
+        avg = self._averager
+        if avg is not None:
+            from ..optim.fused import WeightAverage
+            if isinstance(avg, WeightAverage):
+                loop['weight_average'] = avg.state_dict()
+            loop['swa_lr'] = None if swalr is None else swalr.state_dict()
+            if self.ema_decay is not None and avg.n_averaged > 0:
+                with avg.swap_averaged():
+                    loop['averaged_state_dict'] = {k: v.detach().cpu().clone() for k, v in controller.state_dict().items()}
+        torch.save(loop, root / f'epoch={epoch}.ckpt.trainer')
+
+    def _attach_average(self, optim):
+        """-> the object that averages optims[0]'s parameters (the fused optimizer itself, or an optim.WeightAverage), or None"""
+        if self.ema_decay is None and not self.stochastic_weight_avg:
+            return None
+        from ..optim.fused import _FusedBase, WeightAverage
+        kind, decay = ('ema', self.ema_decay) if self.ema_decay is not None else ('swa', None)
+        if isinstance(optim, _FusedBase):
+            optim.attach_average(kind, decay)
+            return optim
+        return WeightAverage([p for g in optim.param_groups for p in g['params']], kind, decay)
+
+    def _swa_start(self):
+        s = self.swa_epoch_start
+        return int(s * self.max_epochs) if isinstance(s, float) else int(s)
+
+    def _make_swalr(self, optim, resumed=False):
+        from torch.optim.swa_utils import SWALR
+        groups = optim.param_groups
+        if resumed:      # the groups' swa_lr came back with the optimizer state
+            lrs = [g['swa_lr'] for g in groups]
+        elif self.swa_lrs is None:
+            lrs = [g['lr'] for g in groups]
+        else:
+            lrs = list(self.swa_lrs) if isinstance(self.swa_lrs, (list, tuple)) else [self.swa_lrs] * len(groups)
+        return SWALR(optim, swa_lr=lrs if len(lrs) > 1 else lrs[0], anneal_epochs=self.annealing_epochs,
+                     anneal_strategy=self.annealing_strategy)
+
+    def _finish_swa(self, controller, device):
+        """contract step 3: the average becomes the model, with BatchNorm statistics of its own"""
+        from ..utils import update_bn
+        self._averager.swap_averaged_()
+
+        def images():
+            for bi, batch in enumerate(controller.train_dataloader()):
+                if self.limit_train_batches is not None and bi >= self.limit_train_batches:
+                    break
+                yield controller._images(_to_device(batch, device)['x'], True)
+        update_bn(images(), controller.model_loss)
+        if self.ddp is not None:
+            self.ddp.sync_buffers()   # each rank saw its own shard: every rank keeps rank 0's statistics
 
     def _resume(self, controller, optims, scheds, path, device):
         """→ first epoch to run.  `path`: an `epoch=N.ckpt` of this trainer (state dict; loop state in its `.trainer` sidecar) or a
@@ -180,6 +278,7 @@ class Trainer:
             for s_, st in zip(scheds, lst):
                 s_.load_state_dict(st)
         self.global_step = int(loop.get('global_step', 0))
+        self._loop_state = {k: loop[k] for k in ('weight_average', 'swa_lr') if k in loop}   # what fit() still reads
         if 'epoch' not in loop:
             print(f'resume_from_checkpoint: {path.name} carries no loop state — weights only, starting at epoch 0')
         return int(loop.get('epoch', 0))
@@ -191,17 +290,33 @@ class Trainer:
         optims, scheds = (opt if isinstance(opt, (tuple, list)) and len(opt) == 2 and isinstance(opt[0], (list, tuple))
                           else ([opt], []))
         optim = optims[0]
+        averager = self._averager = self._attach_average(optim)
+        ema = averager if self.ema_decay is not None else None
+        ema_by_hand = ema is not None and ema is not optim     # a torch optimizer: the average is updated after its step
+        swa = averager if self.stochastic_weight_avg else None
+        swa_start = self._swa_start() if swa is not None else None
+        swalr = None
+        self._loop_state = {}
+        lr_history = []
         history = []
         gn_history = []
         first_epoch = 0
         ckpt_path = ckpt_path or self.resume_from_checkpoint
         if ckpt_path is not None:
             first_epoch = self._resume(controller, optims, scheds, ckpt_path, device)
+            if averager is not None and 'weight_average' in self._loop_state and averager is not optim:
+                averager.load_state_dict(self._loop_state['weight_average'])
+            if swa is not None and self._loop_state.get('swa_lr') is not None:
+                swalr = self._make_swalr(optim, resumed=True)
+                swalr.load_state_dict(self._loop_state['swa_lr'])
             if self.ddp is not None and hasattr(self.ddp, 'broadcast_parameters'):
                 self.ddp.broadcast_parameters()
         for epoch in range(first_epoch, self.max_epochs):
             controller.current_epoch = epoch
             controller.train()
+            if swa is not None and epoch >= swa_start and swalr is None:
+                swalr = self._make_swalr(optim)
+            lr_history.append([g['lr'] for g in optim.param_groups])
             loader = controller.train_dataloader()
             if device.type == 'cuda' and self.prefetch_batches > 0:
                 from ..data_loading.prefetch import DevicePrefetcher
@@ -228,6 +343,8 @@ class Trainer:
                         self.logger.log_metrics(norms, step=self.global_step)
                 self._clip_gradients(optim)
                 optim.step()
+                if ema_by_hand:
+                    ema.update_average()
                 self.global_step += 1
                 if self.global_step % self.log_every_n_steps == 0 or bi == 0:
                     lv = float(loss.detach())
@@ -245,10 +362,17 @@ class Trainer:
             if self.is_distributed_run:
                 import torch.distributed as dist
                 dist.barrier()
-            for s in scheds:
-                s.step()
+            if swalr is not None:
+                swa.update_average()
+                swalr.step()
+                if epoch == self.max_epochs - 1:
+                    self._finish_swa(controller, device)
+            else:
+                for s in scheds:
+                    s.step()
             if self.enable_checkpointing and self.root is not None and self.rank == 0:
-                self._save_checkpoint(controller, optims, scheds, epoch)
+                self._save_checkpoint(controller, optims, scheds, epoch, swalr)
+        self.lr_history = lr_history
         self.loss_history = history
         self.grad_norm_history = gn_history
         return controller
@@ -296,6 +420,13 @@ class Trainer:
         return {k: round(v, 4) for k, v in norms.items()}
 
     def _run_eval(self, controller, device, kind):
+        avg = self._averager
+        if self.ema_decay is not None and avg is not None and avg.n_averaged > 0:
+            with avg.swap_averaged():      # EMA: evaluate the averaged parameters (live BatchNorm statistics)
+                return self._eval_loop(controller, device, kind)
+        return self._eval_loop(controller, device, kind)
+
+    def _eval_loop(self, controller, device, kind):
         if self.ddp is not None:
             self.ddp.sync_buffers()   # every rank evaluates with rank 0's BN statistics (torch DDP's broadcast_buffers)
         controller.eval()

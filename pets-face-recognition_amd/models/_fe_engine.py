@@ -158,7 +158,7 @@ class FEEngine(PlanEngine):
             m.num_batches_tracked = self.nbt[i]
             so += C
             b = _BN()
-            b.C, b.eps, b.momentum = C, m.eps, (m.momentum if m.momentum is not None else 0.1)
+            b.C, b.eps, b.so = C, m.eps, so - C
             b.gamma = self.master[offs[n + ".weight"]:offs[n + ".weight"] + C]
             b.beta = self.master[offs[n + ".bias"]:offs[n + ".bias"] + C]
             b.dgamma = self.grad[offs[n + ".weight"]:offs[n + ".weight"] + C]
@@ -169,6 +169,14 @@ class FEEngine(PlanEngine):
             b.bcoef = torch.zeros((3, C), dtype=torch.float32, device=dev)  # backward coefficients
             self._bn_of[id(m)] = b
         self.bn_list = [self._bn_of[id(m)] for _, m in bns]
+        # the momenta are baked into the plans as floats: _sync_momenta re-reads them from the modules before every training
+        # forward pass, and the plan cache is keyed on them (_plan_tag) once they differ from the adopted ones
+        self._bn_mods = [m for _, m in bns]
+        self.nstat = nstat
+        self.cma = None             # momentum=None: the running statistics before the pass (see forward)
+        self._mom_sig = self._mom_sig0 = None
+        self._sync_momenta()
+        self._mom_sig0 = self._mom_sig
         maxc = max(m.num_features for _, m in bns)
         self.bn_ws = torch.empty(max(1, lib.pfr_bn_finalize_ws_floats(1 << 20, maxc)), dtype=torch.float32, device=dev)
 
@@ -251,6 +259,35 @@ class FEEngine(PlanEngine):
 
     def matches(self, model):
         return super().matches(model) and id(model.fc) == self.fc_id
+
+    def _sync_momenta(self):
+        """nn.BatchNorm2d.momentum of every BN -> the float its finalize launches take.  momentum=None (torch's cumulative moving
+        average, what torch.optim.swa_utils.update_bn sets) runs with momentum 1, which leaves the batch statistics in the
+        running buffers; forward() then folds them into the running average with weight 1 / num_batches_tracked."""
+        sig = tuple([m.momentum for m in self._bn_mods])
+        if sig != self._mom_sig:
+            for b, mom in zip(self.bn_list, sig):
+                b.cumulative = mom is None
+                b.momentum = 1.0 if mom is None else float(mom)
+            self._mom_sig = sig
+            self._any_cumulative = any(b.cumulative for b in self.bn_list)
+
+    def _plan_tag(self):
+        return () if self._mom_sig == self._mom_sig0 else (("bn_momentum",) + self._mom_sig,)
+
+    def _cumulative_average(self, counts, stream):
+        """after a training pass of a model with momentum=None BNs: self.stats holds their batch statistics, self.cma what the
+        running buffers held before; running = before + (batch - before) / num_batches_tracked (pfr_weight_avg), copied back"""
+        cma, stats, ns = self.cma, self.stats, self.nstat
+        if all(b.cumulative for b in self.bn_list) and len(set(counts)) == 1:
+            lib.pfr_weight_avg(cma.data_ptr(), stats.data_ptr(), 2 * ns, 1.0 / counts[0], stream)
+            stats.copy_(cma)
+            return
+        for b, t in zip(self.bn_list, counts):
+            if b.cumulative:
+                for o in (b.so, ns + b.so):
+                    lib.pfr_weight_avg(cma.data_ptr() + 4 * o, stats.data_ptr() + 4 * o, b.C, 1.0 / t, stream)
+                    stats[o:o + b.C].copy_(cma[o:o + b.C])
 
     def flat_ranges(self, params):
         """Contiguous [lo, hi) ranges of the flat buffers covered by `params` (for fused optimizers / buckets)."""
@@ -1014,6 +1051,15 @@ class FEEngine(PlanEngine):
             x = x.float()
         x = x.contiguous()
         N, _, H, W = x.shape
+        counts = None
+        if train:
+            self._sync_momenta()
+            if self._any_cumulative:
+                # the factor 1 / num_batches_tracked is a host value, as it is in torch (F.batch_norm's exponential_average_factor)
+                counts = (self.nbt + 1).tolist()
+                if self.cma is None:
+                    self.cma = torch.empty_like(self.stats)
+                self.cma.copy_(self.stats)
         plan = self.acquire_plan(N, H, W, train, with_backward, ticket=ticket if with_backward else None)
         plan.meta["epoch"] = self._tuning_epoch     # the knobs this forward pass (and the launches its backward replays) ran under
         if with_backward:
@@ -1037,6 +1083,8 @@ class FEEngine(PlanEngine):
         self._run_fwd(plan, stream)
         if train:
             self.nbt.add_(1)
+            if counts is not None:
+                self._cumulative_average(counts, stream)
         self._last_plan = plan
         return plan.meta["emb"]
 

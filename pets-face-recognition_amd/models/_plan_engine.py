@@ -216,9 +216,13 @@ class PlanEngine:
         self.resolve(plan)
         return plan
 
+    def _plan_tag(self):
+        """engine hook of get_plan: whatever a plan bakes in besides its key and the tuning knobs, as extra key elements"""
+        return ()
+
     def get_plan(self, *key, slot=0):
         self._check_tuning()
-        k = key + ((slot,) if slot else ())
+        k = key + self._plan_tag() + ((slot,) if slot else ())
         p = self.plans.get(k)
         if p is None:
             if len(self.plans) >= self.max_plans:

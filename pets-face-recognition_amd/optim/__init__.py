@@ -1,1 +1,1 @@
-from .fused import FusedSGD, FusedAdamW  # noqa: F401
+from .fused import FusedSGD, FusedAdamW, WeightAverage  # noqa: F401

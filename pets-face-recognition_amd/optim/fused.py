@@ -7,7 +7,15 @@ Gradient clipping (`clip_grad_norm_` / `clip_grad_value_`, torch.nn.utils' argum
 `step()`: the norm is reduced on the device (pfr_grad_norm) and the update kernels read its clip coefficient from device
 memory, so there is no host sync and no extra pass that rewrites the gradients.  The gradients themselves are NOT scaled in
 place; only the update uses the clipped values (PL steps right after clipping and zeroes the gradients before the next
-backward, so a trainer cannot tell the difference)."""
+backward, so a trainer cannot tell the difference).
+
+Weight averaging (`attach_average('ema', decay)` / `attach_average('swa')`, torch.optim.swa_utils.AveragedModel's arithmetic): the
+average is one more flat state buffer per run (`state[p]['avg']`).  An EMA is updated by the step kernel itself, which has the new
+parameter in registers (pfr_*_step_avg: one more read and write of the average, no launch); SWA's running mean is updated by
+`update_average()` (pfr_weight_avg per run).  `swap_averaged()` exchanges master and average; the engines re-derive everything
+they compute with (compute-dtype shadow, weight layouts, folded inference weights) from the master at the next forward pass."""
+import contextlib
+
 import torch
 
 from .._hip import ops, PfrError
@@ -25,6 +33,89 @@ class _FusedBase(torch.optim.Optimizer):
         self._clip_coef = None     # armed by clip_grad_norm_: 1-element device tensor, consumed by the next step()
         self._clip_value = 0.0     # armed by clip_grad_value_ (0 = off), consumed by the next step()
         self._norm = SegmentNorm()
+        self._avg = None           # attach_average: (kind, decay)
+        self.n_averaged = 0        # updates the average has seen (AveragedModel.n_averaged); saved in state_dict()
+
+    # ------------------------------------------------------------------------------------------ weight averaging
+    def attach_average(self, kind, decay=None):
+        """Keep an averaged copy of every parameter this optimizer updates, as `state[p]['avg']`.  'ema': avg <- decay * avg +
+        (1 - decay) * p after every step(), inside the update kernel; 'swa': avg <- running mean of the parameters at the calls
+        of update_average().  The first update copies the parameters (torch's AveragedModel)."""
+        self._avg = _check_average(kind, decay)
+        self._runs = {}            # re-pack with the extra state buffer at the next step
+
+    def _state_keys(self):
+        return self._STATE_KEYS + ("avg",) if self._avg is not None else self._STATE_KEYS
+
+    def _avg_weight(self):
+        return _average_weight(self._avg, self.n_averaged)
+
+    def _ema(self):
+        return self._avg is not None and self._avg[0] == "ema"
+
+    def _avg_pairs(self):
+        """[(avg, p)] flat fp32 tensors covering every averaged parameter: the run buffers where the cached runs are current,
+        any other parameter (no step since attach / load_state_dict, or not in a flat run) on its own"""
+        pairs = []
+        for gi, group in enumerate(self.param_groups):
+            done = set()
+            cached = self._runs.get(gi)
+            if cached is not None and cached[0] == tuple((id(p), p.data_ptr()) for p in group["params"] if p.grad is not None) \
+                    and all("avg" in r["state"] for r in cached[1]):
+                for r in cached[1]:
+                    pairs.append((r["state"]["avg"], r["pf"]))
+                    done.update(id(p) for p, _ in r["members"])
+            for p in group["params"]:
+                st = self.state[p] if p in self.state else {}
+                a = st.get("avg")
+                if a is None or id(p) in done:
+                    continue
+                if a.device != p.device or a.stride() != p.stride():
+                    a = st["avg"] = torch.empty_like(p.data).copy_(a)
+                pairs.append((_flat_alias(a), _flat_alias(p.data)))
+        return pairs
+
+    @torch.no_grad()
+    def update_average(self):
+        """One update of the average from the current parameters (pfr_weight_avg per run): SWA's per-epoch call.  A parameter
+        that has no average yet (never stepped: frozen, or unused so far) gets one here, starting from its current value, so
+        that every parameter of the groups is averaged from this call on; one that joins after the first update therefore
+        counts its current value for the updates it missed."""
+        if self._avg is None:
+            raise PfrError("update_average: attach_average() first")
+        for group in self.param_groups:
+            for p in group["params"]:
+                if "avg" not in self.state[p]:
+                    if not p.is_cuda or p.dtype != torch.float32:
+                        raise PfrError("fused optimizers need fp32 CUDA parameters (use optim.WeightAverage on the CPU path)")
+                    self.state[p]["avg"] = torch.empty_like(p.data).copy_(p.data)
+        w = self._avg_weight()
+        for a, p in self._avg_pairs():
+            ops.weight_avg(a, p, w)
+        self.n_averaged += 1
+
+    @contextlib.contextmanager
+    def swap_averaged(self):
+        """Inside the block the parameters hold the average and `state[p]['avg']` the live weights; leaving it swaps back, bit
+        for bit.  The engines read the master buffer at every forward pass (cast to the compute dtype, stem / data-gradient
+        layouts; the folded inference weights are keyed on a checksum of it), so they follow without a call."""
+        self.swap_averaged_()
+        try:
+            yield self
+        finally:
+            self.swap_averaged_()
+
+    @torch.no_grad()
+    def swap_averaged_(self):
+        """the explicit half of swap_averaged(): exchanges parameters and average once"""
+        _swap([(p.data, self.state[p]["avg"]) for g in self.param_groups for p in g["params"]
+               if p in self.state and "avg" in self.state[p]])
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self._avg is not None:
+            sd["weight_average"] = {"kind": self._avg[0], "decay": self._avg[1], "n_averaged": self.n_averaged}
+        return sd
 
     def _grads(self):
         return [p.grad for group in self.param_groups for p in group["params"] if p.grad is not None]
@@ -58,6 +149,11 @@ class _FusedBase(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._runs = {}      # loaded tensors are private copies: re-pack them into flat run buffers at the next step
+        wa = state_dict.get("weight_average")
+        if wa is not None:
+            if self._avg is None:
+                self._avg = _check_average(wa["kind"], wa["decay"])
+            self.n_averaged = int(wa["n_averaged"])
 
     def _group_runs(self, gi, group):
         params = [p for p in group["params"] if p.grad is not None]
@@ -80,14 +176,16 @@ class _FusedBase(torch.optim.Optimizer):
         for r in runs:
             n = r["n"]
             dev = r["pf"].device
-            r["state"] = {k: torch.zeros(n, dtype=torch.float32, device=dev) for k in self._STATE_KEYS}
+            r["state"] = {k: torch.zeros(n, dtype=torch.float32, device=dev) for k in self._state_keys()}
             for p, off in r["members"]:
                 st = self.state[p]
-                for k in self._STATE_KEYS:
+                for k in self._state_keys():
                     view = torch.as_strided(r["state"][k], p.shape, p.stride(), off)
                     old = st.get(k)
                     if old is not None:
                         view.copy_(old.to(dev))     # carried over (loaded checkpoint, or a previous buffer layout)
+                    elif k == "avg":
+                        view.copy_(p.data)          # a parameter that joins a running average starts from its own value
                     st[k] = view
         self._runs[gi] = (sig, runs, gsig)
         return runs
@@ -169,6 +267,85 @@ class _FusedBase(torch.optim.Optimizer):
         return (t.data_ptr(), n)
 
 
+def _check_average(kind, decay):
+    if kind not in ("ema", "swa"):
+        raise ValueError(f"weight average kind must be 'ema' or 'swa', got {kind!r}")
+    if kind == "ema":
+        if decay is None or not 0.0 < float(decay) < 1.0:
+            raise ValueError(f"an 'ema' average needs 0 < decay < 1, got {decay}")
+        return ("ema", float(decay))
+    if decay is not None:
+        raise ValueError("an 'swa' average takes no decay")
+    return ("swa", None)
+
+
+def _average_weight(avg, n_averaged):
+    """lerp weight of the next update: 1 (copy) for the first one, then 1 - decay (EMA) or 1 / (n_averaged + 1) (SWA)"""
+    if n_averaged == 0:
+        return 1.0
+    return 1.0 - avg[1] if avg[0] == "ema" else 1.0 / (n_averaged + 1)
+
+
+def _flat_alias(t):
+    """the memory of a dense tensor (any permutation of a contiguous one) as a flat tensor"""
+    if _FusedBase._storage_span(t) is None:
+        raise PfrError("weight averaging needs parameters that are dense in memory")
+    return torch.as_strided(t, (t.numel(),), (1,), t.storage_offset())
+
+
+def _swap(pairs):
+    if not pairs:
+        return
+    a, b = [x for x, _ in pairs], [y for _, y in pairs]
+    tmp = [x.clone() for x in a]
+    torch._foreach_copy_(a, b)
+    torch._foreach_copy_(b, tmp)
+
+
+class WeightAverage:
+    """The averaging interface of the fused optimizers (update_average / swap_averaged / n_averaged / state_dict) for
+    parameters stepped by a torch optimizer (the CPU path): `torch._foreach_lerp_`, torch.optim.swa_utils.AveragedModel's
+    arithmetic.  With kind 'ema' the caller runs update_average() after every optimizer step."""
+
+    def __init__(self, params, kind, decay=None):
+        self._avg = _check_average(kind, decay)
+        self.params = [p for p in params]
+        self.avg = [p.detach().clone() for p in self.params]
+        self.n_averaged = 0
+
+    @torch.no_grad()
+    def update_average(self):
+        cur = [p.detach() for p in self.params]
+        if self.n_averaged == 0:
+            torch._foreach_copy_(self.avg, cur)
+        else:
+            torch._foreach_lerp_(self.avg, cur, _average_weight(self._avg, self.n_averaged))
+        self.n_averaged += 1
+
+    @contextlib.contextmanager
+    def swap_averaged(self):
+        self.swap_averaged_()
+        try:
+            yield self
+        finally:
+            self.swap_averaged_()
+
+    @torch.no_grad()
+    def swap_averaged_(self):
+        _swap([(p.data, a) for p, a in zip(self.params, self.avg)])
+
+    def state_dict(self):
+        return {"kind": self._avg[0], "decay": self._avg[1], "n_averaged": self.n_averaged, "avg": [a.clone() for a in self.avg]}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        if len(sd["avg"]) != len(self.avg):
+            raise ValueError(f"WeightAverage: the state holds {len(sd['avg'])} tensors, this average {len(self.avg)}")
+        for a, v in zip(self.avg, sd["avg"]):
+            a.copy_(v)
+        self.n_averaged = int(sd["n_averaged"])
+
+
 def norm_order(norm_type):
     """torch norm_type -> pfr_grad_norm's norm_p: any p > 0, math.inf for the max norm"""
     p = float(norm_type)
@@ -238,15 +415,22 @@ class FusedSGD(_FusedBase):
         loss = closure() if closure is not None else None
         coef, clip_value = self._take_clip()
         clip = coef is not None or clip_value > 0
+        ema = self._ema()
+        avg_w = self._avg_weight() if ema else 0.0
         for gi, group in enumerate(self.param_groups):
             for r in self._group_runs(gi, group):
                 # a zero-initialised buffer makes torch's "first step: buf = d" the general rule buf = momentum*buf + d
                 buf = r["state"]["momentum_buffer"] if group["momentum"] != 0 else None
-                if clip:
+                if ema:
+                    ops.sgd_step_avg(r["pf"], r["gf"], buf, None, group["lr"], group["momentum"], group["weight_decay"], coef,
+                                     clip_value, r["state"]["avg"], avg_w, first_step=False)
+                elif clip:
                     ops.sgd_step_clip(r["pf"], r["gf"], buf, None, group["lr"], group["momentum"], group["weight_decay"], coef,
                                       clip_value, first_step=False)
                 else:
                     ops.sgd_step(r["pf"], r["gf"], buf, None, group["lr"], group["momentum"], group["weight_decay"], first_step=False)
+        if ema:
+            self.n_averaged += 1
         return loss
 
 
@@ -275,13 +459,21 @@ class FusedAdamW(_FusedBase):
         self._t += 1
         coef, clip_value = self._take_clip()
         clip = coef is not None or clip_value > 0
+        ema = self._ema()
+        avg_w = self._avg_weight() if ema else 0.0
         for gi, group in enumerate(self.param_groups):
             for r in self._group_runs(gi, group):
-                if clip:
+                if ema:
+                    ops.adamw_step_avg(r["pf"], r["gf"], r["state"]["exp_avg"], r["state"]["exp_avg_sq"], None, group["lr"],
+                                       group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"], self._t, coef,
+                                       clip_value, r["state"]["avg"], avg_w)
+                elif clip:
                     ops.adamw_step_clip(r["pf"], r["gf"], r["state"]["exp_avg"], r["state"]["exp_avg_sq"], None, group["lr"],
                                         group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"], self._t, coef,
                                         clip_value)
                 else:
                     ops.adamw_step(r["pf"], r["gf"], r["state"]["exp_avg"], r["state"]["exp_avg_sq"], None, group["lr"],
                                    group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"], self._t)
+        if ema:
+            self.n_averaged += 1
         return loss

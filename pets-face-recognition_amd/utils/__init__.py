@@ -132,3 +132,34 @@ def find_optimal_init_lr(trainer, model):
     new_lr = lr_find(trainer, model, **model.config.get('find_optimal_init_lr_kwargs', {})).suggestion()
     print(f'Computed new init lr = {new_lr}')
     return new_lr
+
+
+@torch.no_grad()
+def update_bn(loader, model, device=None):
+    """torch.optim.swa_utils.update_bn: re-estimates the BatchNorm running statistics of `model` (SWA's averaged weights) as the
+    plain average over one pass of `loader` — every BatchNorm is reset, runs the pass in train mode with momentum=None (the
+    cumulative moving average; on the HIP engines pfr_weight_avg with weight 1 / num_batches_tracked, models/_fe_engine.py)
+    and gets its momentum back.  Batches are tensors, or lists / tuples whose first element is the input; no gradient is
+    kept.  The reset and the restore queue device work only (no host sync).  A model without BatchNorm returns at once."""
+    momenta = {}
+    for module in model.modules():
+        if isinstance(module, torch.nn.modules.batchnorm._BatchNorm):
+            module.reset_running_stats()
+            momenta[module] = module.momentum
+    if not momenta:
+        return
+    was_training = model.training
+    model.train()
+    for module in momenta:
+        module.momentum = None
+    try:
+        for batch in loader:
+            if isinstance(batch, (list, tuple)):
+                batch = batch[0]
+            if device is not None:
+                batch = batch.to(device)
+            model(batch)
+    finally:
+        for module, momentum in momenta.items():
+            module.momentum = momentum
+        model.train(was_training)
