@@ -536,6 +536,29 @@ int pfr_gemm_act_colsum_parts(long M, int K, int N, int dtype);
 int pfr_gemm_act_colsums(const void* x, const void* w, void* y, int dtype, long M, int K, int N, void* y2, float* sums_part,
                          pfr_stream_t stream);
 
+/* ---- depthwise K x K convolution and layer scale of the ConvNeXt block (csrc/pfr_dwconv.hip; torchvision convnext.py CNBlock)
+ * NHWC, stride 1, padding K/2, groups = C.  Only K = 7 is built: any other K returns PFR_ERR_UNSUPPORTED; C must be a multiple of the
+ * 16-byte chunk (4 fp32 / 8 bf16); host pointers are refused with an error code.  w: tap-major [K*K][C] in the compute dtype (engine:
+ * pfr_nchw_to_nhwc of the [C][1][K][K] parameter); bias fp32 [C] or NULL; fp32 accumulation.  flip = 1 reads the taps mirrored: the same
+ * call is the data gradient, dx = pfr_dwconv2d_fwd(dy, w, NULL, dx, ..., flip = 1). */
+int pfr_dwconv2d_fwd(const void* x, const void* w, const float* bias, void* y, int dtype, int N, int H, int W, int C, int K,
+                     int flip, pfr_stream_t stream);
+/* dw[c][kh][kw] = sum_{n,h,w} dy[n,h,w,c] * x[n,h+kh-K/2,w+kw-K/2,c] written in the parameter's own [C][1][K][K] order, dbias[c] = sum dy
+ * (dbias may be NULL), both fp32; accumulate = 1 adds to what dw / dbias hold.  part_ws: fp32 [pfr_dwconv2d_wgrad_parts(...)][K*K+1][C]
+ * per-workgroup partial sums, merged by a second launch of the same call (0 parts: geometry not supported). */
+int pfr_dwconv2d_wgrad_parts(int dtype, int N, int H, int W, int C, int K);
+int pfr_dwconv2d_wgrad(const void* x, const void* dy, float* part_ws, float* dw, float* dbias, int dtype, int N, int H, int W, int C,
+                       int K, int accumulate, pfr_stream_t stream);
+/* y = residual + row_scale[n] * gamma[c] * u over [N][HW][C]: layer scale with per-sample ("row" mode) stochastic depth; gamma fp32 [C],
+ * row_scale fp32 [N] (0 or 1/(1-p)) or NULL = all ones */
+int pfr_layer_scale_fwd(const void* u, const float* gamma, const float* row_scale, const void* residual, void* y, int dtype, int N,
+                        int HW, int C, pfr_stream_t stream);
+/* du = row_scale * gamma * dz; dgamma[c] = sum row_scale * dz * u through dgamma_part (fp32 [pfr_layer_scale_bwd_parts(N, HW, C)][C]).
+ * dgamma != NULL: merged here (accumulate = 1 adds to dgamma); NULL: the caller merges the partial rows (pfr_colsum_final_batch). */
+int pfr_layer_scale_bwd_parts(int N, int HW, int C);
+int pfr_layer_scale_bwd(const void* dz, const void* u, const float* gamma, const float* row_scale, void* du, float* dgamma_part,
+                        float* dgamma, int dtype, int N, int HW, int C, int accumulate, pfr_stream_t stream);
+
 /* ---- gradient all-reduce over RCCL / xGMI (csrc/pfr_comm.hip) ---------------------------------------------
  * For hosts that bind this library directly; replaces DistributedDataParallel's bucket all-reduce (utils/__init__.py:114-119).
  * RCCL is resolved with dlopen at first use (no load-time dependency).  pfr_comm_unique_id: rank 0 fills a 128-byte id, the

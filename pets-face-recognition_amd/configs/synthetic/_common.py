@@ -32,7 +32,10 @@ def _live(key, default):
 def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs, device, n_epochs=1, seed=0,
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
          noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
-         ragged=False, pipeline='head', trainer_extra=None):
+         ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd'):
+    # optimizer_kind: 'sgd' (the reference's SGD + MultiStepLR) or 'adamw' (FusedAdamW on the device, torch.optim.AdamW on the CPU)
+    if optimizer_kind not in ('sgd', 'adamw'):
+        raise ValueError(f"optimizer_kind must be 'sgd' or 'adamw', got {optimizer_kind!r}")
     # pipeline: which of the reference's three Compose shapes runs on the device (data_loading/augment.py): 'head' (uniform frames),
     # 'simple' / 'body' (ragged frames: the detector's raw crops, each with its own size)
     if pipeline not in ('head', 'simple', 'body'):
@@ -72,6 +75,10 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         kw = {} if compute_dtype is None else {'compute_dtype': compute_dtype}
         if arch.startswith('swin'):   # the reference's own backbone (models/swin.py:228-241): `mlp_head` IS the 512-d embedding layer
             return getattr(models, arch)(num_classes=512, **kw)
+        if arch.startswith('convnext'):   # masked_head_dog.py:105-106: `model_.classifier[2] = torch.nn.Linear(768, 512)`
+            model_ = getattr(models, arch)(**kw, **(model_kwargs or {}))
+            model_.classifier[2] = torch.nn.Linear(model_.classifier[2].in_features, 512)
+            return model_
         model_ = getattr(models, arch)(**kw)
         model_.fc = torch.nn.Linear(model_.fc.in_features, 512)
         return model_
@@ -84,14 +91,21 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
                                           loss_kwargs=loss_kwargs, arc_margin=True)
 
     def optimizer(model_):
-        params1 = [p for i, p in model_.module.named_parameters() if 'fc' not in i]
-        params2 = [p for i, p in model_.module.named_parameters() if 'fc' in i]
-        base = _live('init_lr', 10 ** -2)
+        head = 'classifier' if arch.startswith('convnext') else 'fc'   # the reference's backbone / embedding-layer split
+        params1 = [p for i, p in model_.module.named_parameters() if head not in i]
+        params2 = [p for i, p in model_.module.named_parameters() if head in i]
+        base = _live('init_lr', 10 ** -2 if optimizer_kind == 'sgd' else 10 ** -3)
         d = [{'lr': base / 2, 'params': params1},
              {'lr': base, 'params': params2},
              {'lr': base, 'params': list(model_.add_margin.parameters()), 'weight_decay': 1 * (10 ** -4)}]
         d = [g for g in d if len(g['params'])]   # (a backbone without an `fc` layer — Swin's embedding layer is `mlp_head` — has no second group)
-        if fused_optimizer and device != 'cpu':
+        if optimizer_kind == 'adamw':
+            if fused_optimizer and device != 'cpu':
+                from optim import FusedAdamW
+                optim = FusedAdamW(d, base, weight_decay=0.05)
+            else:
+                optim = torch.optim.AdamW(d, base, weight_decay=0.05)
+        elif fused_optimizer and device != 'cpu':
             from optim import FusedSGD
             optim = FusedSGD(d, 0.01, momentum=0.9)
         else:
