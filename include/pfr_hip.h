@@ -559,6 +559,45 @@ int pfr_layer_scale_bwd_parts(int N, int HW, int C);
 int pfr_layer_scale_bwd(const void* dz, const void* u, const float* gamma, const float* row_scale, void* du, float* dgamma_part,
                         float* dgamma, int dtype, int N, int HW, int C, int accumulate, pfr_stream_t stream);
 
+/* ---- depthwise 3x3 convolution of the MobileNetV2 inverted-residual block (csrc/pfr_dwconv3.hip; torchvision mobilenetv2.py
+ * InvertedResidual: Conv2d(hidden, hidden, 3, stride, 1, groups=hidden, bias=False) between BatchNorm + ReLU6 pairs)
+ * NHWC, padding 1, stride 1 or 2 (any other stride returns PFR_ERR_UNSUPPORTED), no bias, OH = (H - 1) / stride + 1 (OW likewise); C must
+ * be a multiple of the 16-byte chunk (4 fp32 / 8 bf16); fp32 accumulation; host pointers are refused with an error code and an argument
+ * error never launches.  w: tap-major [9][C] in the compute dtype (engine: pfr_nchw_to_nhwc of the [C][1][3][3] parameter).
+ *   pro_scale / pro_shift fp32 [C] or both NULL: the operand is a = min(max(scale[c]*x + shift[c], 0), pro_hi), computed in fp32 from the
+ *   stored x (the producer's BatchNorm apply + ReLU6; pro_hi = 6) — pro_hi <= 0: no upper clamp.  Taps outside the image contribute 0:
+ *   the padding is of the ACTIVATED tensor, not of x.
+ *   stats_part or NULL: fp32 [ceil(N*OH*OW / rpp)][2][C] per-channel (mean, M2) of the row groups [t*rpp, (t+1)*rpp) of the stored
+ *   (rounded) y, rpp = pfr_dwconv3_rows_per_part(...) — the input of pfr_bn_finalize(part, nparts, rpp, ...); deterministic, no atomics. */
+long pfr_dwconv3_rows_per_part(int dtype, int N, int H, int W, int C, int stride);
+int pfr_dwconv3_fwd(const void* x, const void* w, void* y, int dtype, int N, int H, int W, int C, int stride, const float* pro_scale,
+                    const float* pro_shift, float pro_hi, float* stats_part, pfr_stream_t stream);
+/* dx [N][H][W][C] from dy [N][OH][OW][C]: a gather per dx pixel over the taps whose parity meets an output pixel (no atomics, no
+ * zero-fill pass; every dx element is written) */
+int pfr_dwconv3_dgrad(const void* dy, const void* w, void* dx, int dtype, int N, int H, int W, int C, int stride, pfr_stream_t stream);
+/* dw[c][kh][kw] = sum_{n,oh,ow} dy[n,oh,ow,c] * a[n, oh*stride - 1 + kh, ow*stride - 1 + kw, c] in the parameter's own [C][1][3][3]
+ * order, fp32; a = the activated operand recomputed with the forward's prologue (so the forward need not store it); accumulate = 1 adds
+ * to what dw holds.  part_ws: fp32 [pfr_dwconv3_wgrad_parts(...)][9][C] per-workgroup partial sums, merged by a second launch of the
+ * same call (0 parts: geometry not supported). */
+int pfr_dwconv3_wgrad_parts(int dtype, int N, int H, int W, int C, int stride);
+int pfr_dwconv3_wgrad(const void* x, const void* dy, float* part_ws, float* dw, int dtype, int N, int H, int W, int C, int stride,
+                      const float* pro_scale, const float* pro_shift, float pro_hi, int accumulate, pfr_stream_t stream);
+/* ReLU6 forms of the BatchNorm apply / backward (csrc/pfr_elementwise.hip; nn.ReLU6 = hardtanh(., 0, 6) after nn.BatchNorm2d).  The
+ * entry points above are unchanged; these carry the upper bound `hi` (hi <= 0: none) and check every pointer to be device memory.
+ *   pfr_bn_act_clamp:         y = min(max(a*x + b, 0), hi)                  (hi <= 0: pfr_bn_act(relu = 1), bit for bit)
+ *   pfr_bn_bwd_reduce_clamp:  g = dout * [0 < scale*x + shift < hi], both strict (torch's hardtanh_backward), recomputed from the
+ *                             BatchNorm input x (mask_mode 2; hi <= 0: pfr_bn_bwd_reduce's mask_mode 2, bit for bit) or g = dout
+ *                             (mask_mode 0: a BatchNorm without activation); partials of (Σg, Σg·x̂) in pfr_bn_bwd_reduce's layout
+ *                             ([pfr_colreduce_blocks(C, dtype, rows)][2][C]) for pfr_bn_bwd_finalize
+ *   pfr_bn_bwd_apply_clamp:   dx = coef0*g + coef1*x + coef2 with the same g (dx may alias dout) */
+int pfr_bn_act_clamp(const void* x, const float* a, const float* b, void* y, float hi, int dtype, long rows, int C,
+                     pfr_stream_t stream);
+int pfr_bn_bwd_reduce_clamp(const void* dout, const void* x, const float* mean, const float* invstd, const float* scale,
+                            const float* shift, float hi, int mask_mode, int dtype, long rows, int C, float* part,
+                            pfr_stream_t stream);
+int pfr_bn_bwd_apply_clamp(const void* dout, const void* x, const float* coef, const float* scale, const float* shift, float hi,
+                           int mask_mode, void* dx, int dtype, long rows, int C, pfr_stream_t stream);
+
 /* ---- gradient all-reduce over RCCL / xGMI (csrc/pfr_comm.hip) ---------------------------------------------
  * For hosts that bind this library directly; replaces DistributedDataParallel's bucket all-reduce (utils/__init__.py:114-119).
  * RCCL is resolved with dlopen at first use (no load-time dependency).  pfr_comm_unique_id: rank 0 fills a 128-byte id, the

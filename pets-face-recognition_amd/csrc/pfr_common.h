@@ -97,6 +97,21 @@ extern thread_local hipEvent_t pfr_tls_stop_event;
     }                                       \
   } while (0)
 
+// every non-NULL pointer of a call must be device memory: a host pointer is an argument error, never a launch
+#include <initializer_list>
+static inline bool pfr_all_dev(std::initializer_list<const void*> ps) {
+  for (const void* p : ps) {
+    if (!p) continue;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    if (a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged) return false;
+  }
+  return true;
+}
+
 #define PFR_CHECK_LAUNCH()                                            \
   do {                                                                \
     hipError_t e_ = hipGetLastError();                                \

@@ -12,22 +12,6 @@
 #define DW_CC 32   // channels per workgroup
 #define DW_RS 8    // row slots per workgroup (256 threads / 32 channels)
 
-static bool dw_dev_ptr(const void* p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
-// every non-NULL pointer of a call must be device memory: a host pointer is an argument error, never a launch
-static bool dw_all_dev(std::initializer_list<const void*> ps) {
-  for (const void* p : ps)
-    if (p && !dw_dev_ptr(p)) return false;
-  return true;
-}
-
 // stage a PH x PW pixel window (top-left at (gh0, gw0) of image n) of DW_CC channels from c0 into LDS [pixel][32]
 template <typename T>
 __device__ __forceinline__ void dw_stage(const T* __restrict__ src, T* __restrict__ dst, int n, int gh0, int gw0, int PH, int PW, int H,
@@ -179,7 +163,7 @@ static int dw_check(const char* fn, std::initializer_list<const void*> ptrs, int
   const int kp = dtype == PFR_BF16 ? 8 : 4;
   PFR_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0, "%s: empty tensor", fn);
   PFR_CHECK_ARG(C % kp == 0, "%s: C = %d is not a multiple of %d (16-byte channel chunks)", fn, C, kp);
-  PFR_CHECK_ARG(dw_all_dev(ptrs), "%s: not a device pointer (no CPU fallback)", fn);
+  PFR_CHECK_ARG(pfr_all_dev(ptrs), "%s: not a device pointer (no CPU fallback)", fn);
   return PFR_OK;
 }
 
@@ -317,7 +301,7 @@ static int ls_check(const char* fn, std::initializer_list<const void*> ptrs, int
   const int kp = dtype == PFR_BF16 ? 8 : 4;
   PFR_CHECK_ARG(N > 0 && HW > 0 && C > 0, "%s: empty tensor", fn);
   PFR_CHECK_ARG(C % kp == 0 && C / kp <= 256, "%s: C = %d must be a multiple of %d and at most %d", fn, C, kp, 256 * kp);
-  PFR_CHECK_ARG(dw_all_dev(ptrs), "%s: not a device pointer (no CPU fallback)", fn);
+  PFR_CHECK_ARG(pfr_all_dev(ptrs), "%s: not a device pointer (no CPU fallback)", fn);
   return PFR_OK;
 }
 

@@ -11,6 +11,7 @@
 // partials → LDS across the row-lanes of a block → one deterministic partial row per block (no atomics).
 #include "pfr_common.h"
 #include <hip/hip_ext.h>
+#include <initializer_list>
 
 // ------------------------------------------------------------------------------------------------
 // layout / dtype conversion
@@ -934,6 +935,217 @@ extern "C" int pfr_bn_bwd_apply(const void* dout, const void* out, const void* x
   if (dtype == PFR_BF16) PFR_BNA4(bf16_t); else PFR_BNA4(float);
 #undef PFR_BNA4
 #undef PFR_BNA
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// ---- ReLU6 forms (MobileNetV2: nn.ReLU6 after BatchNorm = hardtanh(., 0, 6)): y = min(max(a*x + b, 0), hi) and, backward,
+// g = dout * [0 < scale*x + shift < hi] recomputed from the BatchNorm input (both strict: torch's hardtanh_backward).  hi <= 0: no upper
+// bound; the kernels take it as +inf, and with that the same geometry, loads and order of operations as bn_act_kernel /
+// bn_bwd_reduce_kernel<2> / bn_bwd_apply_kernel<2> give their results bit for bit.  MASK 0: g = dout (a BatchNorm without activation).
+// New entry points: every non-NULL pointer is checked to be device memory before the launch.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_act_clamp_kernel(const T* __restrict__ x, const float* __restrict__ a, const float* __restrict__ b,
+                                                           T* __restrict__ y, float hi, size_t rows, int C, int cw, int rl, int cpr) {
+  constexpr int KP = DT<T>::KPACK;
+  const int col = threadIdx.x % cw, rlane = threadIdx.x / cw;
+  const int cglob = blockIdx.y * cw + col;
+  if (cglob >= cpr) return;
+  float A[KP], B[KP];
+#pragma unroll
+  for (int e = 0; e < KP; ++e) {
+    A[e] = a[cglob * KP + e];
+    B[e] = b[cglob * KP + e];
+  }
+  auto body = [&](u32x4 v, size_t row) {
+    float f[KP];
+    Chunk<T>::unpack(v, f);
+#pragma unroll
+    for (int e = 0; e < KP; ++e) f[e] = fminf(fmaxf(fmaf(f[e], A[e], B[e]), 0.f), hi);
+    st16(y + row * C + cglob * KP, Chunk<T>::pack(f));
+  };
+  const size_t step = (size_t)gridDim.x * rl;
+  size_t r = (size_t)blockIdx.x * rl + rlane;
+  for (; r + 3 * step < rows; r += 4 * step) {   // four rows per thread in flight (see bn_act_kernel)
+    u32x4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = ld16_nt(x + (r + u * step) * C + cglob * KP);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) body(v[u], r + u * step);
+  }
+  for (; r < rows; r += step) body(ld16(x + r * C + cglob * KP), r);
+}
+
+extern "C" int pfr_bn_act_clamp(const void* x, const float* a, const float* b, void* y, float hi, int dtype, long rows, int C,
+                                hipStream_t st) {
+  PFR_CHECK_ARG(x && a && b && y, "pfr_bn_act_clamp: null pointer");
+  PFR_CHECK_ARG(dtype == PFR_F32 || dtype == PFR_BF16, "pfr_bn_act_clamp: dtype must be fp32 or bf16");
+  const int kp = dtype == PFR_BF16 ? 8 : 4;
+  PFR_CHECK_ARG(rows > 0 && C > 0 && C % kp == 0, "pfr_bn_act_clamp: C %% %d != 0 or empty tensor", kp);
+  PFR_CHECK_ARG(pfr_all_dev({x, a, b, y}), "pfr_bn_act_clamp: not a device pointer (no CPU fallback)");
+  ColGeom g = col_geom(C, kp, (size_t)rows, 512);
+  const float h = hi > 0.f ? hi : __builtin_inff();
+  if (dtype == PFR_BF16)
+    hipLaunchKernelGGL(bn_act_clamp_kernel<bf16_t>, dim3(g.gx, g.gy), dim3(256), 0, st, (const bf16_t*)x, a, b, (bf16_t*)y, h, (size_t)rows, C, g.cw, g.rl, g.cpr);
+  else
+    hipLaunchKernelGGL(bn_act_clamp_kernel<float>, dim3(g.gx, g.gy), dim3(256), 0, st, (const float*)x, a, b, (float*)y, h, (size_t)rows, C, g.cw, g.rl, g.cpr);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+template <typename T, int MASK>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_clamp_kernel(const T* __restrict__ dout, const T* __restrict__ x,
+                                                                  const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                  const float* __restrict__ scale, const float* __restrict__ shift, float hi,
+                                                                  float* __restrict__ part, size_t rows, int C, int cw, int rl, int cpr) {
+  constexpr int KP = DT<T>::KPACK;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int col = threadIdx.x % cw, rlane = threadIdx.x / cw;
+  const int cglob = blockIdx.y * cw + col;
+  float v[2][KP];
+#pragma unroll
+  for (int e = 0; e < KP; ++e) { v[0][e] = 0.f; v[1][e] = 0.f; }
+  if (cglob < cpr) {
+    float mu[KP], is[KP], sc[KP], sh[KP];
+#pragma unroll
+    for (int e = 0; e < KP; ++e) {
+      mu[e] = mean[cglob * KP + e];
+      is[e] = invstd[cglob * KP + e];
+      sc[e] = MASK == 2 ? scale[cglob * KP + e] : 0.f;
+      sh[e] = MASK == 2 ? shift[cglob * KP + e] : 0.f;
+    }
+    auto body = [&](u32x4 vg, u32x4 vx) {
+      float g[KP], xv[KP];
+      Chunk<T>::unpack(vg, g);
+      Chunk<T>::unpack(vx, xv);
+#pragma unroll
+      for (int e = 0; e < KP; ++e) {
+        float gg = g[e];
+        if (MASK == 2) {
+          const float z = fmaf(xv[e], sc[e], sh[e]);
+          gg = (z > 0.f && z < hi) ? gg : 0.f;
+        }
+        v[0][e] += gg;
+        v[1][e] = fmaf(gg, (xv[e] - mu[e]) * is[e], v[1][e]);
+      }
+    };
+    const size_t step = (size_t)gridDim.x * rl;
+    size_t r = (size_t)blockIdx.x * rl + rlane;
+    constexpr int UB = PFR_BNR_ROWS;
+    for (; r + (UB - 1) * step < rows; r += UB * step) {
+      u32x4 vg[UB], vx[UB];
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const size_t off = (r + u * step) * C + cglob * KP;
+        vg[u] = ld16_nt(dout + off);
+        vx[u] = ld16_nt(x + off);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < UB; ++u) body(vg[u], vx[u]);
+    }
+    for (; r < rows; r += step) {
+      const size_t off = r * C + cglob * KP;
+      body(ld16(dout + off), ld16(x + off));
+    }
+  }
+  col_block_reduce<2, KP>(v, lds, cw, rl, col, rlane, cglob, cpr, part + (size_t)blockIdx.x * 2 * C, C);
+}
+
+static int bnc_bwd_check(const char* fn, int mask_mode, int dtype, long rows, int C, const float* scale, const float* shift) {
+  PFR_CHECK_ARG(dtype == PFR_F32 || dtype == PFR_BF16, "%s: dtype must be fp32 or bf16", fn);
+  PFR_CHECK_ARG(mask_mode == 0 || mask_mode == 2, "%s: mask_mode is 0 (none) or 2 (recomputed from scale*x + shift)", fn);
+  PFR_CHECK_ARG(mask_mode != 2 || (scale && shift), "%s: mask_mode 2 needs scale/shift", fn);
+  const int kp = dtype == PFR_BF16 ? 8 : 4;
+  PFR_CHECK_ARG(rows > 0 && C > 0 && C % kp == 0, "%s: C %% %d != 0 or empty tensor", fn, kp);
+  return PFR_OK;
+}
+
+extern "C" int pfr_bn_bwd_reduce_clamp(const void* dout, const void* x, const float* mean, const float* invstd, const float* scale,
+                                       const float* shift, float hi, int mask_mode, int dtype, long rows, int C, float* part,
+                                       hipStream_t st) {
+  PFR_CHECK_ARG(dout && x && mean && invstd && part, "pfr_bn_bwd_reduce_clamp: null pointer");
+  if (int rc = bnc_bwd_check("pfr_bn_bwd_reduce_clamp", mask_mode, dtype, rows, C, scale, shift)) return rc;
+  PFR_CHECK_ARG(pfr_all_dev({dout, x, mean, invstd, scale, shift, part}), "pfr_bn_bwd_reduce_clamp: not a device pointer (no CPU fallback)");
+  const int kp = dtype == PFR_BF16 ? 8 : 4;
+  ColGeom g = col_geom(C, kp, (size_t)rows);
+  const size_t shb = (size_t)256 * 2 * kp * sizeof(float);
+  const float h = hi > 0.f ? hi : __builtin_inff();
+#define PFR_BNRC(TT, M) hipLaunchKernelGGL((bn_bwd_reduce_clamp_kernel<TT, M>), dim3(g.gx, g.gy), dim3(256), shb, st, (const TT*)dout, (const TT*)x, mean, invstd, scale, shift, h, part, (size_t)rows, C, g.cw, g.rl, g.cpr)
+  if (dtype == PFR_BF16) { if (mask_mode == 2) PFR_BNRC(bf16_t, 2); else PFR_BNRC(bf16_t, 0); }
+  else { if (mask_mode == 2) PFR_BNRC(float, 2); else PFR_BNRC(float, 0); }
+#undef PFR_BNRC
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+template <typename T, int MASK>
+__global__ __launch_bounds__(256) void bn_bwd_apply_clamp_kernel(const T* __restrict__ dout, const T* __restrict__ x,
+                                                                 const float* __restrict__ coef, const float* __restrict__ scale,
+                                                                 const float* __restrict__ shift, float hi, T* __restrict__ dx, size_t rows,
+                                                                 int C, int cw, int rl, int cpr) {
+  constexpr int KP = DT<T>::KPACK;
+  const int col = threadIdx.x % cw, rlane = threadIdx.x / cw;
+  const int cglob = blockIdx.y * cw + col;
+  if (cglob >= cpr) return;
+  float cg[KP], cx[KP], c0[KP], sc[KP], sh[KP];
+#pragma unroll
+  for (int e = 0; e < KP; ++e) {
+    const int c = cglob * KP + e;
+    cg[e] = coef[c];
+    cx[e] = coef[C + c];
+    c0[e] = coef[2 * C + c];
+    sc[e] = MASK == 2 ? scale[c] : 0.f;
+    sh[e] = MASK == 2 ? shift[c] : 0.f;
+  }
+  auto body = [&](u32x4 vg, u32x4 vx, size_t off) {
+    float g[KP], xv[KP];
+    Chunk<T>::unpack(vg, g);
+    Chunk<T>::unpack(vx, xv);
+#pragma unroll
+    for (int e = 0; e < KP; ++e) {
+      float gg = g[e];
+      if (MASK == 2) {
+        const float z = fmaf(xv[e], sc[e], sh[e]);
+        gg = (z > 0.f && z < hi) ? gg : 0.f;
+      }
+      xv[e] = fmaf(cg[e], gg, fmaf(cx[e], xv[e], c0[e]));
+    }
+    st16(dx + off, Chunk<T>::pack(xv));
+  };
+  const size_t step = (size_t)gridDim.x * rl;
+  size_t r = (size_t)blockIdx.x * rl + rlane;
+  for (; r + 3 * step < rows; r += 4 * step) {   // four rows per thread in flight (dx may alias dout: loads precede stores)
+    u32x4 vg[4], vx[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t off = (r + u * step) * C + cglob * KP;
+      vg[u] = ld16_nt(dout + off);
+      vx[u] = ld16_nt(x + off);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) body(vg[u], vx[u], (r + u * step) * C + cglob * KP);
+  }
+  for (; r < rows; r += step) {
+    const size_t off = r * C + cglob * KP;
+    body(ld16(dout + off), ld16(x + off), off);
+  }
+}
+
+extern "C" int pfr_bn_bwd_apply_clamp(const void* dout, const void* x, const float* coef, const float* scale, const float* shift, float hi,
+                                      int mask_mode, void* dx, int dtype, long rows, int C, hipStream_t st) {
+  PFR_CHECK_ARG(dout && x && coef && dx, "pfr_bn_bwd_apply_clamp: null pointer");
+  if (int rc = bnc_bwd_check("pfr_bn_bwd_apply_clamp", mask_mode, dtype, rows, C, scale, shift)) return rc;
+  PFR_CHECK_ARG(pfr_all_dev({dout, x, coef, scale, shift, dx}), "pfr_bn_bwd_apply_clamp: not a device pointer (no CPU fallback)");
+  const int kp = dtype == PFR_BF16 ? 8 : 4;
+  ColGeom g = col_geom(C, kp, (size_t)rows, 256);
+  const float h = hi > 0.f ? hi : __builtin_inff();
+#define PFR_BNAC(TT, M) hipLaunchKernelGGL((bn_bwd_apply_clamp_kernel<TT, M>), dim3(g.gx, g.gy), dim3(256), 0, st, (const TT*)dout, (const TT*)x, coef, scale, shift, h, (TT*)dx, (size_t)rows, C, g.cw, g.rl, g.cpr)
+  if (dtype == PFR_BF16) { if (mask_mode == 2) PFR_BNAC(bf16_t, 2); else PFR_BNAC(bf16_t, 0); }
+  else { if (mask_mode == 2) PFR_BNAC(float, 2); else PFR_BNAC(float, 0); }
+#undef PFR_BNAC
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }
