@@ -598,6 +598,67 @@ int pfr_bn_bwd_reduce_clamp(const void* dout, const void* x, const float* mean, 
 int pfr_bn_bwd_apply_clamp(const void* dout, const void* x, const float* coef, const float* scale, const float* shift, float hi,
                            int mask_mode, void* dx, int dtype, long rows, int C, pfr_stream_t stream);
 
+/* ---- depthwise K x K convolution of the EfficientNet MBConv block (csrc/pfr_dwconvk.hip; torchvision efficientnet.py MBConv:
+ * Conv2dNormActivation(expanded, expanded, kernel_size=k, stride=s, groups=expanded, activation_layer=SiLU), i.e.
+ * Conv2d(C, C, k, s, (k - 1) // 2, groups=C, bias=False) between BatchNorm + SiLU pairs)
+ * The contract of pfr_dwconv3_* plus `int K` (3 or 5, padding K/2; any other K or a stride other than 1 | 2 returns
+ * PFR_ERR_UNSUPPORTED) and `int pro_act`, the producer's BatchNorm apply + activation as a prologue computed in fp32 from the stored x:
+ *   0  the operand is x itself (pro_scale / pro_shift are not read)
+ *   1  min(max(scale[c]*x + shift[c], 0), pro_hi)  (pro_hi <= 0: no upper clamp) — at K = 3 bit for bit pfr_dwconv3_fwd
+ *   2  silu(scale[c]*x + shift[c]), the sigmoid in fp32
+ * The padding is of the ACTIVATED tensor.  w: tap-major [K*K][C] in the compute dtype.  stats_part or NULL: fp32
+ * [ceil(N*OH*OW / rpp)][2][C] (mean, M2) partials of the stored, rounded y, rpp = pfr_dwconvk_rows_per_part(...), the input of
+ * pfr_bn_finalize.  OH = (H - 1) / stride + 1.  Deterministic, no atomics; an argument error never launches. */
+long pfr_dwconvk_rows_per_part(int dtype, int N, int H, int W, int C, int K, int stride);
+int pfr_dwconvk_fwd(const void* x, const void* w, void* y, int dtype, int N, int H, int W, int C, int K, int stride, int pro_act,
+                    const float* pro_scale, const float* pro_shift, float pro_hi, float* stats_part, pfr_stream_t stream);
+/* dx [N][H][W][C] from dy [N][OH][OW][C]: a gather per dx pixel (no atomics, no zero-fill pass; every dx element is written) */
+int pfr_dwconvk_dgrad(const void* dy, const void* w, void* dx, int dtype, int N, int H, int W, int C, int K, int stride,
+                      pfr_stream_t stream);
+/* dw in the parameter's own [C][1][K][K] order, fp32, from the activated operand recomputed with the forward's prologue; accumulate = 1
+ * adds to what dw holds.  part_ws: fp32 [pfr_dwconvk_wgrad_parts(...)][K*K][C] (0 parts: geometry not supported). */
+int pfr_dwconvk_wgrad_parts(int dtype, int N, int H, int W, int C, int K, int stride);
+int pfr_dwconvk_wgrad(const void* x, const void* dy, float* part_ws, float* dw, int dtype, int N, int H, int W, int C, int K, int stride,
+                      int pro_act, const float* pro_scale, const float* pro_shift, float pro_hi, int accumulate, pfr_stream_t stream);
+/* SiLU forms of the BatchNorm apply / backward (csrc/pfr_elementwise.hip; torchvision efficientnet.py: activation_layer=nn.SiLU after
+ * nn.BatchNorm2d), beside the _clamp forms and with their layouts:
+ *   pfr_bn_act_silu:         y = silu(a*x + b) = u * sigmoid(u), sigmoid in fp32
+ *   pfr_bn_bwd_reduce_silu:  g = dout * sigmoid(u) * (1 + u * (1 - sigmoid(u))), u = scale*x + shift recomputed from the BatchNorm input x
+ *                            (no mask, no stored activation); partials of (Σg, Σg·x̂) for pfr_bn_bwd_finalize
+ *   pfr_bn_bwd_apply_silu:   dx = coef0*g + coef1*x + coef2 with the same g (dx may alias dout) */
+int pfr_bn_act_silu(const void* x, const float* a, const float* b, void* y, int dtype, long rows, int C, pfr_stream_t stream);
+int pfr_bn_bwd_reduce_silu(const void* dout, const void* x, const float* mean, const float* invstd, const float* scale,
+                           const float* shift, int dtype, long rows, int C, float* part, pfr_stream_t stream);
+int pfr_bn_bwd_apply_silu(const void* dout, const void* x, const float* coef, const float* scale, const float* shift, void* dx, int dtype,
+                          long rows, int C, pfr_stream_t stream);
+
+/* ---- squeeze-and-excitation of the MBConv block (csrc/pfr_se.hip; torchvision ops/misc.py SqueezeExcitation.forward:
+ * `scale = scale_activation(fc2(activation(fc1(avgpool(input))))); return scale * input` with activation = SiLU, scale_activation =
+ * Sigmoid).  Activations NHWC [N][HW][C] in `dtype`, C a multiple of the 16-byte chunk; the squeeze is pfr_avgpool_fwd (pooled [N][C] in
+ * `dtype`).  w1 = fc1.weight fp32 [S][C], b1 = fc1.bias [S], w2 = fc2.weight fp32 [C][S], b2 = fc2.bias [C], read from the fp32 master
+ * parameters as they stand; S is any positive integer.  pre / gate / dgate / dpooled are fp32.  Deterministic, no atomics.
+ *   pfr_se_gate_fwd:          pre[n][s] = b1[s] + Σ_c w1[s][c] pooled[n][c];  gate[n][c] = sigmoid(b2[c] + Σ_s w2[c][s] silu(pre[n][s]))
+ *   pfr_se_scale_fwd:         y = a * gate[n][c]
+ *   pfr_se_scale_bwd_reduce:  dgate[n][c] = Σ_hw dy * a
+ *   pfr_se_gate_bwd:          dpooled [N][C] and the gradients of fc1 / fc2 (sums over N in ascending order; accumulate = 1 adds to what
+ *                             dw1 / db1 / dw2 / db2 hold); dpre_ws: fp32 [N][S] workspace
+ *   pfr_se_bwd_apply:         da = dy * gate[n][c] + dpooled[n][c] / HW */
+int pfr_se_gate_fwd(const void* pooled, const float* w1, const float* b1, const float* w2, const float* b2, float* pre, float* gate,
+                    int dtype, int N, int C, int S, pfr_stream_t stream);
+int pfr_se_scale_fwd(const void* a, const float* gate, void* y, int dtype, int N, int HW, int C, pfr_stream_t stream);
+int pfr_se_scale_bwd_reduce(const void* dy, const void* a, float* dgate, int dtype, int N, int HW, int C, pfr_stream_t stream);
+int pfr_se_gate_bwd(const float* dgate, const void* pooled, const float* pre, const float* gate, const float* w1, const float* w2,
+                    float* dpre_ws, float* dpooled, float* dw1, float* db1, float* dw2, float* db2, int dtype, int N, int C, int S,
+                    int accumulate, pfr_stream_t stream);
+int pfr_se_bwd_apply(const void* dy, const float* gate, const float* dpooled, void* da, int dtype, int N, int HW, int C,
+                     pfr_stream_t stream);
+/* per-sample ("row" mode) stochastic depth on the project BatchNorm (torchvision efficientnet.py MBConv.forward:
+ * `result = self.stochastic_depth(result); result += input`): y = residual + row_scale[n] * (a[c]*z + b[c]), row_scale fp32 [N] of 0 or
+ * 1/(1-p); backward: pfr_row_scale (y = row_scale[n] * x) in front of the linear pfr_bn_bwd_* path */
+int pfr_bn_residual_rows(const void* z, const float* a, const float* b, const void* residual, const float* row_scale, void* y, int dtype,
+                         int N, int HW, int C, pfr_stream_t stream);
+int pfr_row_scale(const void* x, const float* row_scale, void* y, int dtype, int N, int HW, int C, pfr_stream_t stream);
+
 /* ---- gradient all-reduce over RCCL / xGMI (csrc/pfr_comm.hip) ---------------------------------------------
  * For hosts that bind this library directly; replaces DistributedDataParallel's bucket all-reduce (utils/__init__.py:114-119).
  * RCCL is resolved with dlopen at first use (no load-time dependency).  pfr_comm_unique_id: rank 0 fills a 128-byte id, the

@@ -83,6 +83,10 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
             model_ = getattr(models, arch)(**kw, **(model_kwargs or {}))
             model_.classifier = torch.nn.Sequential(torch.nn.Linear(model_.last_channel, 512))
             return model_
+        if arch.startswith('efficientnet'):   # fe_dogs_config.py:105-106: `model_.classifier = torch.nn.Linear(1408, 512)` (1408 = B2's last width)
+            model_ = getattr(models, arch)(**kw, **(model_kwargs or {}))
+            model_.classifier = torch.nn.Linear(model_.classifier[1].in_features, 512)
+            return model_
         model_ = getattr(models, arch)(**kw)
         model_.fc = torch.nn.Linear(model_.fc.in_features, 512)
         return model_
@@ -95,7 +99,7 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
                                           loss_kwargs=loss_kwargs, arc_margin=True)
 
     def optimizer(model_):
-        head = 'classifier' if arch.startswith(('convnext', 'mobilenet')) else 'fc'   # the reference's backbone / embedding-layer split
+        head = 'classifier' if arch.startswith(('convnext', 'mobilenet', 'efficientnet')) else 'fc'   # the reference's backbone / embedding-layer split
         params1 = [p for i, p in model_.module.named_parameters() if head not in i]
         params2 = [p for i, p in model_.module.named_parameters() if head in i]
         base = _live('init_lr', 10 ** -2 if optimizer_kind == 'sgd' else 10 ** -3)

@@ -939,12 +939,21 @@ extern "C" int pfr_bn_bwd_apply(const void* dout, const void* out, const void* x
   return PFR_OK;
 }
 
+// SiLU forms (EfficientNet: nn.SiLU after BatchNorm): silu(u) = u σ(u) and its derivative σ(u)(1 + u(1 - σ(u))), the sigmoid in fp32.
+// They are the MASK 3 / SILU instantiations of the kernels below (the MASK 0 / 2 instantiations are unchanged by them).
+__device__ __forceinline__ float bn_sigmoid(float u) { return __builtin_amdgcn_rcpf(1.f + __expf(-u)); }
+__device__ __forceinline__ float bn_silu(float u) { return u * bn_sigmoid(u); }
+__device__ __forceinline__ float bn_silu_grad(float u) {
+  const float s = bn_sigmoid(u);
+  return s * fmaf(u, 1.f - s, 1.f);
+}
+
 // ---- ReLU6 forms (MobileNetV2: nn.ReLU6 after BatchNorm = hardtanh(., 0, 6)): y = min(max(a*x + b, 0), hi) and, backward,
 // g = dout * [0 < scale*x + shift < hi] recomputed from the BatchNorm input (both strict: torch's hardtanh_backward).  hi <= 0: no upper
 // bound; the kernels take it as +inf, and with that the same geometry, loads and order of operations as bn_act_kernel /
 // bn_bwd_reduce_kernel<2> / bn_bwd_apply_kernel<2> give their results bit for bit.  MASK 0: g = dout (a BatchNorm without activation).
 // New entry points: every non-NULL pointer is checked to be device memory before the launch.
-template <typename T>
+template <typename T, bool SILU = false>
 __global__ __launch_bounds__(256) void bn_act_clamp_kernel(const T* __restrict__ x, const float* __restrict__ a, const float* __restrict__ b,
                                                            T* __restrict__ y, float hi, size_t rows, int C, int cw, int rl, int cpr) {
   constexpr int KP = DT<T>::KPACK;
@@ -961,7 +970,10 @@ __global__ __launch_bounds__(256) void bn_act_clamp_kernel(const T* __restrict__
     float f[KP];
     Chunk<T>::unpack(v, f);
 #pragma unroll
-    for (int e = 0; e < KP; ++e) f[e] = fminf(fmaxf(fmaf(f[e], A[e], B[e]), 0.f), hi);
+    for (int e = 0; e < KP; ++e) {
+      if constexpr (SILU) f[e] = bn_silu(fmaf(f[e], A[e], B[e]));
+      else f[e] = fminf(fmaxf(fmaf(f[e], A[e], B[e]), 0.f), hi);
+    }
     st16(y + row * C + cglob * KP, Chunk<T>::pack(f));
   };
   const size_t step = (size_t)gridDim.x * rl;
@@ -1012,8 +1024,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_clamp_kernel(const T* __res
     for (int e = 0; e < KP; ++e) {
       mu[e] = mean[cglob * KP + e];
       is[e] = invstd[cglob * KP + e];
-      sc[e] = MASK == 2 ? scale[cglob * KP + e] : 0.f;
-      sh[e] = MASK == 2 ? shift[cglob * KP + e] : 0.f;
+      sc[e] = MASK >= 2 ? scale[cglob * KP + e] : 0.f;
+      sh[e] = MASK >= 2 ? shift[cglob * KP + e] : 0.f;
     }
     auto body = [&](u32x4 vg, u32x4 vx) {
       float g[KP], xv[KP];
@@ -1026,6 +1038,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_clamp_kernel(const T* __res
           const float z = fmaf(xv[e], sc[e], sh[e]);
           gg = (z > 0.f && z < hi) ? gg : 0.f;
         }
+        if (MASK == 3) gg *= bn_silu_grad(fmaf(xv[e], sc[e], sh[e]));
         v[0][e] += gg;
         v[1][e] = fmaf(gg, (xv[e] - mu[e]) * is[e], v[1][e]);
       }
@@ -1096,8 +1109,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_clamp_kernel(const T* __rest
     cg[e] = coef[c];
     cx[e] = coef[C + c];
     c0[e] = coef[2 * C + c];
-    sc[e] = MASK == 2 ? scale[c] : 0.f;
-    sh[e] = MASK == 2 ? shift[c] : 0.f;
+    sc[e] = MASK >= 2 ? scale[c] : 0.f;
+    sh[e] = MASK >= 2 ? shift[c] : 0.f;
   }
   auto body = [&](u32x4 vg, u32x4 vx, size_t off) {
     float g[KP], xv[KP];
@@ -1110,6 +1123,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_clamp_kernel(const T* __rest
         const float z = fmaf(xv[e], sc[e], sh[e]);
         gg = (z > 0.f && z < hi) ? gg : 0.f;
       }
+      if (MASK == 3) gg *= bn_silu_grad(fmaf(xv[e], sc[e], sh[e]));
       xv[e] = fmaf(cg[e], gg, fmaf(cx[e], xv[e], c0[e]));
     }
     st16(dx + off, Chunk<T>::pack(xv));
@@ -1146,6 +1160,54 @@ extern "C" int pfr_bn_bwd_apply_clamp(const void* dout, const void* x, const flo
   if (dtype == PFR_BF16) { if (mask_mode == 2) PFR_BNAC(bf16_t, 2); else PFR_BNAC(bf16_t, 0); }
   else { if (mask_mode == 2) PFR_BNAC(float, 2); else PFR_BNAC(float, 0); }
 #undef PFR_BNAC
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// ---- SiLU forms (EfficientNet): y = silu(a*x + b); backward g = dout * silu'(scale*x + shift), the derivative recomputed from the
+// BatchNorm input x and the coefficients (no mask, no stored activation); partials / coefficients as the forms above
+extern "C" int pfr_bn_act_silu(const void* x, const float* a, const float* b, void* y, int dtype, long rows, int C, hipStream_t st) {
+  PFR_CHECK_ARG(x && a && b && y, "pfr_bn_act_silu: null pointer");
+  PFR_CHECK_ARG(dtype == PFR_F32 || dtype == PFR_BF16, "pfr_bn_act_silu: dtype must be fp32 or bf16");
+  const int kp = dtype == PFR_BF16 ? 8 : 4;
+  PFR_CHECK_ARG(rows > 0 && C > 0 && C % kp == 0, "pfr_bn_act_silu: C %% %d != 0 or empty tensor", kp);
+  PFR_CHECK_ARG(pfr_all_dev({x, a, b, y}), "pfr_bn_act_silu: not a device pointer (no CPU fallback)");
+  ColGeom g = col_geom(C, kp, (size_t)rows, 512);
+  if (dtype == PFR_BF16)
+    hipLaunchKernelGGL((bn_act_clamp_kernel<bf16_t, true>), dim3(g.gx, g.gy), dim3(256), 0, st, (const bf16_t*)x, a, b, (bf16_t*)y, 0.f, (size_t)rows, C, g.cw, g.rl, g.cpr);
+  else
+    hipLaunchKernelGGL((bn_act_clamp_kernel<float, true>), dim3(g.gx, g.gy), dim3(256), 0, st, (const float*)x, a, b, (float*)y, 0.f, (size_t)rows, C, g.cw, g.rl, g.cpr);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+extern "C" int pfr_bn_bwd_reduce_silu(const void* dout, const void* x, const float* mean, const float* invstd, const float* scale,
+                                      const float* shift, int dtype, long rows, int C, float* part, hipStream_t st) {
+  PFR_CHECK_ARG(dout && x && mean && invstd && scale && shift && part, "pfr_bn_bwd_reduce_silu: null pointer");
+  if (int rc = bnc_bwd_check("pfr_bn_bwd_reduce_silu", 2, dtype, rows, C, scale, shift)) return rc;
+  PFR_CHECK_ARG(pfr_all_dev({dout, x, mean, invstd, scale, shift, part}), "pfr_bn_bwd_reduce_silu: not a device pointer (no CPU fallback)");
+  const int kp = dtype == PFR_BF16 ? 8 : 4;
+  ColGeom g = col_geom(C, kp, (size_t)rows);
+  const size_t shb = (size_t)256 * 2 * kp * sizeof(float);
+  if (dtype == PFR_BF16)
+    hipLaunchKernelGGL((bn_bwd_reduce_clamp_kernel<bf16_t, 3>), dim3(g.gx, g.gy), dim3(256), shb, st, (const bf16_t*)dout, (const bf16_t*)x, mean, invstd, scale, shift, 0.f, part, (size_t)rows, C, g.cw, g.rl, g.cpr);
+  else
+    hipLaunchKernelGGL((bn_bwd_reduce_clamp_kernel<float, 3>), dim3(g.gx, g.gy), dim3(256), shb, st, (const float*)dout, (const float*)x, mean, invstd, scale, shift, 0.f, part, (size_t)rows, C, g.cw, g.rl, g.cpr);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+extern "C" int pfr_bn_bwd_apply_silu(const void* dout, const void* x, const float* coef, const float* scale, const float* shift, void* dx,
+                                     int dtype, long rows, int C, hipStream_t st) {
+  PFR_CHECK_ARG(dout && x && coef && scale && shift && dx, "pfr_bn_bwd_apply_silu: null pointer");
+  if (int rc = bnc_bwd_check("pfr_bn_bwd_apply_silu", 2, dtype, rows, C, scale, shift)) return rc;
+  PFR_CHECK_ARG(pfr_all_dev({dout, x, coef, scale, shift, dx}), "pfr_bn_bwd_apply_silu: not a device pointer (no CPU fallback)");
+  const int kp = dtype == PFR_BF16 ? 8 : 4;
+  ColGeom g = col_geom(C, kp, (size_t)rows, 256);
+  if (dtype == PFR_BF16)
+    hipLaunchKernelGGL((bn_bwd_apply_clamp_kernel<bf16_t, 3>), dim3(g.gx, g.gy), dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)x, coef, scale, shift, 0.f, (bf16_t*)dx, (size_t)rows, C, g.cw, g.rl, g.cpr);
+  else
+    hipLaunchKernelGGL((bn_bwd_apply_clamp_kernel<float, 3>), dim3(g.gx, g.gy), dim3(256), 0, st, (const float*)dout, (const float*)x, coef, scale, shift, 0.f, (float*)dx, (size_t)rows, C, g.cw, g.rl, g.cpr);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }

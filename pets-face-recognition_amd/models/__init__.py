@@ -1,8 +1,9 @@
 """Model registry — mirrors /root/reference/models/__init__.py (swin_t/s/b/l, SwinTransformer) and adds the
 torchvision-compatible ResNets the reference's FE configs build (configs/dog_fe/fe_dogs_config.py:102-103) and the
-torchvision-compatible ConvNeXt-T/S and MobileNetV2 of their alternative backbone lines (configs/dog_fe/masked_head_dog.py:105-106,
-configs/dog_fe/fe_dogs_config.py:104-105)."""
+torchvision-compatible ConvNeXt-T/S, MobileNetV2 and EfficientNet-B0..B3 of their alternative backbone lines
+(configs/dog_fe/masked_head_dog.py:105-106, configs/dog_fe/fe_dogs_config.py:104-106)."""
 from .resnet import ResNet, BasicBlock, Bottleneck, resnet18, resnet34, resnet50, resnet101  # noqa: F401
 from .swin import SwinTransformer, swin_t, swin_s, swin_b, swin_l  # noqa: F401
 from .convnext import ConvNeXt, convnext_tiny, convnext_small  # noqa: F401
 from .mobilenet import MobileNetV2, InvertedResidual, mobilenet_v2  # noqa: F401
+from .efficientnet import EfficientNet, MBConv, SqueezeExcitation, efficientnet_b0, efficientnet_b1, efficientnet_b2, efficientnet_b3  # noqa: F401
