@@ -324,6 +324,18 @@ int pfr_alpha_grad(const float* cosv, const int64_t* label, const float* alpha, 
  * out_inv_denom (or NULL) = 1 / d; reduction 0: d = n, 1 ('sum'): d = 1, 2 (weighted 'mean'): d = sum_i row_stats[i][3] = sum_i w_{t_i} */
 int pfr_loss_reduce(const float* loss_rows, const float* row_stats, int n, int reduction, float* out_loss, float* out_inv_denom,
                     pfr_stream_t stream);
+/* Sub-centre heads (K centres per class, 1 <= K <= 16; weight row c*K + k, so a class's K sub-cosines are contiguous in a cosine row).
+ * pfr_subcenter_pool replaces `cos, arg = cos_sub[:, :C*K].view(B, C, K).max(2)`: cos [B][ldc] fp32 with columns C..ldc-1 written as 0,
+ *   arg [B][C] the LOWEST k that attains the maximum (strict > scan).  Columns C*K..ld_sub-1 of cos_sub are never read.
+ *   label / count: both or neither; count [C*K] int32 is incremented (integer atomics) at label[b]*K + arg[b][label[b]] for every row:
+ *   `count += torch.bincount(label*K + arg[range(B), label], minlength=C*K)`.
+ * pfr_subcenter_scatter replaces the autograd of that max: dcos_sub[b][c*K+k] = (k == arg[b][c]) ? dcos[b][c] : 0 in the dtype of dcos
+ *   (f32 or bf16), `torch.zeros(B, ld_sub).view(...).scatter_(2, arg[..., None], dcos[:, :C, None])`.  EVERY element of [B][ld_sub] is
+ *   written, the pad columns as 0: no memset precedes it. */
+int pfr_subcenter_pool(const float* cos_sub, int B, int C, int K, int ld_sub, float* cos, int ldc, uint8_t* arg, const int64_t* label,
+                       int32_t* count, pfr_stream_t stream);
+int pfr_subcenter_scatter(const void* dcos, int dtype, const uint8_t* arg, int B, int C, int K, int ldc, void* dcos_sub, int ld_sub,
+                          pfr_stream_t stream);
 
 /* ---- optimiser steps over flat fp32 master buffers (configs/dog_fe/fe_dogs_config.py:123-133; body_dog_fe.py:121-131) */
 int pfr_sgd_step(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,

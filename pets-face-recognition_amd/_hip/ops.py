@@ -339,6 +339,56 @@ def loss_reduce(loss_rows, row_stats, reduction):
     return out, inv
 
 
+def _chk_sub(ok, what):
+    if not ok:
+        raise PfrError(what)
+
+
+def subcenter_pool(cos_sub, C, K, ldc=None, label=None, count=None, cos=None, arg=None):
+    """cos_sub [B, ld_sub] f32 (class-major sub-cosines, c*K + k) -> (cos [B, ldc] f32 = max over k with columns C.. zeroed,
+    arg [B, C] uint8 = the lowest k attaining it); with `count` ([C*K] or [C, K] int32) the histogram of the label's sub-centre is added"""
+    _chk(cos_sub, "subcenter_pool: cos_sub")
+    _chk_sub(cos_sub.dim() == 2 and cos_sub.dtype == torch.float32, "subcenter_pool: cos_sub must be a 2-d fp32 tensor")
+    B, ld_sub = cos_sub.shape
+    _chk_sub(1 <= K <= 16 and C >= 1 and ld_sub >= C * K, f"subcenter_pool: {ld_sub} columns do not hold C={C} classes of K={K} (1..16) sub-centres")
+    _chk_sub((count is None) == (label is None), "subcenter_pool: label and count go together")
+    if count is not None:
+        _chk(count, "subcenter_pool: count")
+        _chk(label, "subcenter_pool: label")
+        _chk_sub(count.dtype == torch.int32 and count.numel() == C * K and label.dtype == torch.int64 and label.numel() == B,
+                 f"subcenter_pool: expected an int32 [{C * K}] count and an int64 [{B}] label")
+    if cos is None:
+        cos = torch.empty((B, C if ldc is None else ldc), dtype=torch.float32, device=cos_sub.device)
+    if arg is None:
+        arg = torch.empty((B, C), dtype=torch.uint8, device=cos_sub.device)
+    _chk(cos, "subcenter_pool: cos")
+    _chk(arg, "subcenter_pool: arg")
+    _chk_sub(cos.dtype == torch.float32 and cos.dim() == 2 and cos.shape[0] == B and cos.shape[1] >= C,
+             f"subcenter_pool: cos must be fp32 [{B}, >= {C}]")
+    _chk_sub(arg.dtype == torch.uint8 and arg.shape == (B, C), f"subcenter_pool: arg must be uint8 [{B}, {C}]")
+    lib.pfr_subcenter_pool(_p(cos_sub), B, C, K, ld_sub, _p(cos), cos.shape[1], _p(arg), _p(label), _p(count), _stream())
+    return cos, arg
+
+
+def subcenter_scatter(dcos, arg, K, ld_sub=None, out=None):
+    """dcos [B, ldc], arg [B, C] uint8 -> dcos_sub [B, ld_sub] (dtype of dcos): dcos on each class's selected sub-centre, 0 elsewhere,
+    pad columns included (the buffer needs no clearing)"""
+    _chk(dcos, "subcenter_scatter: dcos")
+    _chk(arg, "subcenter_scatter: arg")
+    _chk_sub(dcos.dim() == 2 and arg.dim() == 2 and arg.dtype == torch.uint8 and arg.shape[0] == dcos.shape[0],
+             "subcenter_scatter: expected dcos [B, ldc] and a uint8 arg [B, C]")
+    B, ldc = dcos.shape
+    C = arg.shape[1]
+    _chk_sub(1 <= K <= 16 and ldc >= C, f"subcenter_scatter: K={K} outside 1..16 or dcos has {ldc} < C={C} columns")
+    if out is None:
+        out = torch.empty((B, C * K if ld_sub is None else ld_sub), dtype=dcos.dtype, device=dcos.device)
+    _chk(out, "subcenter_scatter: out")
+    _chk_sub(out.dtype == dcos.dtype and out.dim() == 2 and out.shape[0] == B and out.shape[1] >= C * K,
+             f"subcenter_scatter: out must be {dcos.dtype} [{B}, >= {C * K}]")
+    lib.pfr_subcenter_scatter(_p(dcos), dtype_id(dcos.dtype), _p(arg), B, C, K, ldc, _p(out), out.shape[1], _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ optimisers
 def sgd_step(p, g, mom, shadow, lr, momentum, weight_decay, grad_scale=1.0, first_step=False):
     lib.pfr_sgd_step(_p(p), _p(g), _p(mom), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),

@@ -32,7 +32,8 @@ def _live(key, default):
 def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs, device, n_epochs=1, seed=0,
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
          noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
-         ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd'):
+         ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd', sub_centers=1):
+    # sub_centers: K centres per class in the margin head (losses/large_margin.py); 1 = the reference's head
     # optimizer_kind: 'sgd' (the reference's SGD + MultiStepLR) or 'adamw' (FusedAdamW on the device, torch.optim.AdamW on the CPU)
     if optimizer_kind not in ('sgd', 'adamw'):
         raise ValueError(f"optimizer_kind must be 'sgd' or 'adamw', got {optimizer_kind!r}")
@@ -96,7 +97,7 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         # loss_kwargs go to FocalLoss (is_focal) or nn.CrossEntropyLoss as in the reference (losses/__init__.py:28-33).  A learnable
         # FocalLoss alpha is in no optimizer group below, as in the reference's configs: it stays at its initial ones unless a config adds it.
         return SoftmaxBasedMetricLearning(model=model_, num_class=n_train_ids, embedding_size=512, is_focal=is_focal,
-                                          loss_kwargs=loss_kwargs, arc_margin=True)
+                                          loss_kwargs=loss_kwargs, arc_margin=True, sub_centers=sub_centers)
 
     def optimizer(model_):
         head = 'classifier' if arch.startswith(('convnext', 'mobilenet', 'efficientnet')) else 'fc'   # the reference's backbone / embedding-layer split

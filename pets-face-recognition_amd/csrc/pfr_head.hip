@@ -590,3 +590,135 @@ extern "C" int pfr_margin_bwd(const float* cosv, const int64_t* label, int B, in
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }
+
+// ---- sub-centre heads (Deng et al., ECCV 2020): K centres per class, weight row c*K + k, so the K sub-cosines of a class are
+// contiguous in a cosine row.  Two streaming passes around the unchanged row kernel: the pool takes the class cosine as the maximum
+// of its K sub-cosines (and remembers which one), the scatter routes d loss / d cos back to that sub-centre alone.
+// A lane owns whole classes: K contiguous floats in, K contiguous elements out; with K = 2 or 4 and aligned rows those are one
+// 8- / 16-byte access.  grid.y = rows, grid.x = class chunks, sized so that B = 256 alone gives ~2048 workgroups.
+template <typename T, int N>
+struct alignas(sizeof(T) * N) SubPack {
+  T v[N];
+};
+
+// KT: compile-time K (0 = run-time K, 1..16); VEC: the lane's K elements move as one SubPack (host checked the alignment)
+template <int KT, bool VEC>
+__global__ __launch_bounds__(256) void subcenter_pool_kernel(const float* __restrict__ cos_sub, int C, int Krt, int ld_sub,
+                                                             float* __restrict__ cosv, int ldc, uint8_t* __restrict__ arg,
+                                                             const int64_t* __restrict__ label, int32_t* __restrict__ count) {
+  const int K = KT ? KT : Krt;
+  const int row = blockIdx.y;
+  const float* src = cos_sub + (size_t)row * ld_sub;
+  float* dst = cosv + (size_t)row * ldc;
+  uint8_t* adst = arg + (size_t)row * C;
+  const int t = label ? (int)label[row] : -1;
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < ldc; c += gridDim.x * 256) {
+    if (c >= C) {   // the GEMMs of the backward read the padded width
+      dst[c] = 0.f;
+      continue;
+    }
+    float best;
+    int a = 0;
+    if constexpr (VEC) {
+      const SubPack<float, KT> p = *reinterpret_cast<const SubPack<float, KT>*>(src + (size_t)c * KT);
+      best = p.v[0];
+#pragma unroll
+      for (int k = 1; k < KT; ++k)
+        if (p.v[k] > best) { best = p.v[k]; a = k; }
+    } else {
+      const float* s = src + (size_t)c * K;
+      best = s[0];
+      for (int k = 1; k < K; ++k) {
+        const float v = s[k];
+        if (v > best) { best = v; a = k; }   // strict: the lowest k wins a tie
+      }
+    }
+    dst[c] = best;
+    adst[c] = (uint8_t)a;
+    if (count && c == t) atomicAdd(&count[(size_t)c * K + a], 1);   // one lane per row; integer adds: the same bits every run
+  }
+}
+
+extern "C" int pfr_subcenter_pool(const float* cos_sub, int B, int C, int K, int ld_sub, float* cosv, int ldc, uint8_t* arg,
+                                  const int64_t* label, int32_t* count, hipStream_t st) {
+  PFR_CHECK_ARG(cos_sub && cosv && arg, "pfr_subcenter_pool: null pointer");
+  PFR_CHECK_ARG(K >= 1 && K <= 16, "pfr_subcenter_pool: K=%d outside 1..16", K);
+  PFR_CHECK_ARG(B > 0 && C > 0 && ldc >= C && (long long)ld_sub >= (long long)C * K, "pfr_subcenter_pool: bad shape B=%d C=%d K=%d ld_sub=%d ldc=%d",
+                B, C, K, ld_sub, ldc);
+  PFR_CHECK_ARG(B <= 65535, "pfr_subcenter_pool: B=%d above 65535 rows", B);
+  PFR_CHECK_ARG(!count == !label, "pfr_subcenter_pool: count and label go together");
+  const int chunks = (ldc + 255) / 256;
+  const int per_row = 2048 / B > 1 ? 2048 / B : 1;
+  const dim3 grid(chunks < per_row ? chunks : per_row, B), block(256);
+  const bool al = ((uintptr_t)cos_sub % (4 * (size_t)K)) == 0 && ld_sub % K == 0;
+#define SCP(KT, VEC) hipLaunchKernelGGL((subcenter_pool_kernel<KT, VEC>), grid, block, 0, st, cos_sub, C, K, ld_sub, cosv, ldc, arg, label, count)
+  if (K == 2 && al) SCP(2, true);
+  else if (K == 4 && al) SCP(4, true);
+  else if (K == 2) SCP(2, false);
+  else if (K == 3) SCP(3, false);
+  else if (K == 4) SCP(4, false);
+  else SCP(0, false);
+#undef SCP
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// dcos_sub[b][c*K + k] = (k == arg[b][c]) ? dcos[b][c] : 0 over the whole [B, ld_sub] buffer: lanes past the last class write the pad
+// columns, so nothing clears the buffer first
+template <typename TG, int KT, bool VEC>
+__global__ __launch_bounds__(256) void subcenter_scatter_kernel(const TG* __restrict__ dcos, const uint8_t* __restrict__ arg, int C, int Krt,
+                                                                int ldc, TG* __restrict__ dcos_sub, int ld_sub) {
+  const int K = KT ? KT : Krt;
+  const int row = blockIdx.y;
+  const TG* src = dcos + (size_t)row * ldc;
+  const uint8_t* asrc = arg + (size_t)row * C;
+  TG* dst = dcos_sub + (size_t)row * ld_sub;
+  const int nc = (ld_sub + K - 1) / K;   // classes, then whole or partial groups of pad columns
+  const TG zero = from_f32<TG>(0.f);
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < nc; c += gridDim.x * 256) {
+    const bool live = c < C;
+    const TG d = live ? src[c] : zero;
+    const int a = live ? (int)asrc[c] : -1;
+    if constexpr (VEC) {   // ld_sub is a multiple of K: every group is whole
+      SubPack<TG, KT> p;
+#pragma unroll
+      for (int k = 0; k < KT; ++k) p.v[k] = k == a ? d : zero;
+      *reinterpret_cast<SubPack<TG, KT>*>(dst + (size_t)c * KT) = p;
+    } else {
+      const size_t col0 = (size_t)c * K;
+      for (int k = 0; k < K; ++k)
+        if (col0 + k < (size_t)ld_sub) dst[col0 + k] = k == a ? d : zero;
+    }
+  }
+}
+
+template <typename TG>
+static void launch_subcenter_scatter(const void* dcos, const uint8_t* arg, int B, int C, int K, int ldc, void* dcos_sub, int ld_sub,
+                                     hipStream_t st) {
+  const int chunks = ((ld_sub + K - 1) / K + 255) / 256;
+  const int per_row = 2048 / B > 1 ? 2048 / B : 1;
+  const dim3 grid(chunks < per_row ? chunks : per_row, B), block(256);
+  const bool al = ((uintptr_t)dcos_sub % (sizeof(TG) * (size_t)K)) == 0 && ld_sub % K == 0;
+#define SCS(KT, VEC) hipLaunchKernelGGL((subcenter_scatter_kernel<TG, KT, VEC>), grid, block, 0, st, (const TG*)dcos, arg, C, K, ldc, (TG*)dcos_sub, ld_sub)
+  if (K == 2 && al) SCS(2, true);
+  else if (K == 4 && al) SCS(4, true);
+  else if (K == 2) SCS(2, false);
+  else if (K == 3) SCS(3, false);
+  else if (K == 4) SCS(4, false);
+  else SCS(0, false);
+#undef SCS
+}
+
+extern "C" int pfr_subcenter_scatter(const void* dcos, int dtype, const uint8_t* arg, int B, int C, int K, int ldc, void* dcos_sub,
+                                     int ld_sub, hipStream_t st) {
+  PFR_CHECK_ARG(dcos && arg && dcos_sub, "pfr_subcenter_scatter: null pointer");
+  PFR_CHECK_ARG(K >= 1 && K <= 16, "pfr_subcenter_scatter: K=%d outside 1..16", K);
+  PFR_CHECK_ARG(B > 0 && C > 0 && ldc >= C && (long long)ld_sub >= (long long)C * K, "pfr_subcenter_scatter: bad shape B=%d C=%d K=%d ldc=%d ld_sub=%d",
+                B, C, K, ldc, ld_sub);
+  PFR_CHECK_ARG(B <= 65535, "pfr_subcenter_scatter: B=%d above 65535 rows", B);
+  PFR_CHECK_ARG(dtype == PFR_F32 || dtype == PFR_BF16, "pfr_subcenter_scatter: bad dtype %d", dtype);
+  if (dtype == PFR_BF16) launch_subcenter_scatter<bf16_t>(dcos, arg, B, C, K, ldc, dcos_sub, ld_sub, st);
+  else launch_subcenter_scatter<float>(dcos, arg, B, C, K, ldc, dcos_sub, ld_sub, st);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}

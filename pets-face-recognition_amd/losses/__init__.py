@@ -11,12 +11,13 @@ from .losses import FocalLoss, describe_criterion
 
 class SoftmaxBasedMetricLearning(nn.Module):
     def __init__(self, model, num_class, embedding_size=512, s=64.0, m=0.5, is_focal=False, loss_kwargs=None,
-                 arc_margin=False, easy_margin=False):
+                 arc_margin=False, easy_margin=False, sub_centers=1):
         super().__init__()
+        # sub_centers (not in the reference): K centres per class in the head, see losses/large_margin.py; `logits` stay [B, num_class]
         if arc_margin:
-            self.add_margin = ArcMarginProduct(embedding_size, num_class, s=s, m=m, easy_margin=easy_margin)
+            self.add_margin = ArcMarginProduct(embedding_size, num_class, s=s, m=m, easy_margin=easy_margin, sub_centers=sub_centers)
         else:
-            self.add_margin = AddMarginProduct(embedding_size, num_class, s=s, m=m)
+            self.add_margin = AddMarginProduct(embedding_size, num_class, s=s, m=m, sub_centers=sub_centers)
         loss_kwargs = loss_kwargs or {}
         self.focal_loss = FocalLoss(num_class=num_class, **loss_kwargs) if is_focal else nn.CrossEntropyLoss(**loss_kwargs)
         self.module = model
@@ -28,9 +29,12 @@ class SoftmaxBasedMetricLearning(nn.Module):
         the fused HIP path for this embedding, else None (then: the margin-logit kernels, then `self.focal_loss` on the logits).
         Fused: FocalLoss with a fixed or an adaptive (learnable) alpha; nn.CrossEntropyLoss with `weight`, `label_smoothing` and
         reduction 'mean' / 'sum'.  Left unfused on purpose: reduction='none', a non-default ignore_index, a weight / alpha that is not an
-        fp32 [num_class] tensor on the embedding's device, CPU tensors, anything but a [B, in_features] embedding."""
+        fp32 [num_class] tensor on the embedding's device, CPU tensors, anything but a [B, in_features] embedding, a head weight that
+        is not [out_features * sub_centers, in_features]."""
         head = self.add_margin
         if not emb.is_cuda or not isinstance(head, _MarginHead) or emb.dim() != 2 or emb.shape[1] != head.in_features:
+            return None
+        if head.weight.shape[0] != head.out_features * head.sub_centers:
             return None
         return describe_criterion(self.focal_loss, head.out_features, emb.device)
 
@@ -52,8 +56,12 @@ class SoftmaxBasedMetricLearning(nn.Module):
         from ._head_hip import MarginCEFunction, resolve_dtype
         head = self.add_margin
         dt = head.compute_dtype or getattr(self.module, "compute_dtype", None)
-        loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
-                                              resolve_dtype(dt), self.return_logits, crit.alpha)
+        if head.sub_centers == 1:
+            loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
+                                                  resolve_dtype(dt), self.return_logits, crit.alpha)
+        else:
+            loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
+                                                  resolve_dtype(dt), self.return_logits, crit.alpha, head.sub_centers, head._count())
         return {'loss': loss, 'emb': tensor, 'logits': logits if self.return_logits else None}
 
 

@@ -56,20 +56,38 @@ def _cosine_bwd(dcos, emb, weight, saved, T):
     return demb, dw
 
 
+def _pool_fwd(cos_sub, C, K, T, label, count):
+    """sub-cosines [B, Cpad(C*K)] → class cosines [B, Cpad(C)] (pad columns 0) and the selected sub-centre per (row, class); with
+    `count` ([C, K] int32) the histogram of the labels' sub-centres is updated in the same pass"""
+    return ops.subcenter_pool(cos_sub, C, K, ldc=_cpad(C, T), label=None if count is None else label, count=count)
+
+
+def _split_classes(w, K):
+    if not 1 <= K <= 16 or w.shape[0] % K:
+        raise PfrError(f"sub-centre head: a [{w.shape[0]}, {w.shape[1]}] weight does not hold K={K} centres per class (1 <= K <= 16)")
+    return w.shape[0] // K
+
+
 class MarginCEFunction(torch.autograd.Function):
     """(emb, weight, label[, alpha]) → (loss, logits): normalise → cosine GEMM → margin → scale → criterion, fused.  `crit` is the
     losses.losses.Criterion description of the loss (gamma, adaptive alpha, class weight, label smoothing, reduction); `alpha` is the
     criterion's learnable [C] vector passed as an input so that autograd hands its gradient back (None when crit.alpha is None).
-    Every criterion is the same launches: only the row kernel's instantiation differs, plus one column kernel for d loss / d alpha."""
+    Every criterion is the same launches: only the row kernel's instantiation differs, plus one column kernel for d loss / d alpha.
+    K > 1 (sub-centre head, weight [C*K, D]): the cosine GEMM runs over all C*K centres, one pooling pass takes the maximum per class
+    before the row kernel, one scatter pass routes dcos to the selected centres after it; `count` ([C, K] int32 or None) collects which
+    centre each sample's own class selected.  K == 1 launches neither."""
 
     @staticmethod
-    def forward(ctx, emb, weight, label, mode, s, m, crit, T, want_logits, alpha=None):
+    def forward(ctx, emb, weight, label, mode, s, m, crit, T, want_logits, alpha=None, K=1, count=None):
         emb = emb.contiguous().float()
         w = weight.detach().contiguous()
         label = label.contiguous().long()
-        C = w.shape[0]
+        C = w.shape[0] if K == 1 else _split_classes(w, K)
         B = emb.shape[0]
         cos, saved = _cosine_fwd(emb, w, T)
+        arg = None
+        if K > 1:
+            cos, arg = _pool_fwd(cos, C, K, T, label, count)
         stats = inv_denom = None
         if crit.is_plain:
             logits, loss_rows, _ = ops.margin_ce(cos, label, C, mode, s, m, gamma=crit.gamma, want_logits=want_logits)
@@ -84,8 +102,8 @@ class MarginCEFunction(torch.autograd.Function):
                 loss, _ = ops.loss_reduce(loss_rows, None, "sum")
             else:   # F.cross_entropy's 'mean' divides by the sum of the targets' weights (= B without weights)
                 loss, inv_denom = ops.loss_reduce(loss_rows, stats, "weighted_mean")
-        ctx.save_for_backward(emb, w, label, cos, alpha, crit.weight, stats, inv_denom, *saved)
-        ctx.cfg = (mode, s, m, crit, T, C)
+        ctx.save_for_backward(emb, w, label, cos, alpha, crit.weight, stats, inv_denom, arg, *saved)
+        ctx.cfg = (mode, s, m, crit, T, C, K)
         if logits is None:
             logits = torch.empty(0, device=emb.device)
         ctx.mark_non_differentiable(logits)
@@ -93,8 +111,8 @@ class MarginCEFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dlogits):
-        emb, w, label, cos, alpha, cweight, stats, inv_denom, *saved = ctx.saved_tensors
-        mode, s, m, crit, T, C = ctx.cfg
+        emb, w, label, cos, alpha, cweight, stats, inv_denom, arg, *saved = ctx.saved_tensors
+        mode, s, m, crit, T, C, K = ctx.cfg
         B = emb.shape[0]
         dloss = dloss.contiguous().float()
         dalpha = None
@@ -109,37 +127,44 @@ class MarginCEFunction(torch.autograd.Function):
                                              want_logits=False, want_stats=False, dcos_dtype=T)
             if alpha is not None and ctx.needs_input_grad[9]:
                 dalpha = ops.alpha_grad(cos, label, alpha, stats, C, s, grad_scale=gs, grad_scale_dev=dloss)
+        if K > 1:
+            dcos = ops.subcenter_scatter(dcos, arg, K, ld_sub=_cpad(C * K, T))
         demb, dw = _cosine_bwd(dcos, emb, w, saved, T)
-        return demb, dw, None, None, None, None, None, None, None, dalpha
+        return demb, dw, None, None, None, None, None, None, None, dalpha, None, None
 
 
 class MarginFunction(torch.autograd.Function):
-    """(emb, weight, label) → logits; standalone ArcMarginProduct / AddMarginProduct."""
+    """(emb, weight, label) → logits; standalone ArcMarginProduct / AddMarginProduct (K, count: as in MarginCEFunction)."""
 
     @staticmethod
-    def forward(ctx, emb, weight, label, mode, s, m, T):
+    def forward(ctx, emb, weight, label, mode, s, m, T, K=1, count=None):
         emb = emb.contiguous().float()
         w = weight.detach().contiguous()
         label = label.contiguous().long()
-        C = w.shape[0]
+        C = w.shape[0] if K == 1 else _split_classes(w, K)
         cos, saved = _cosine_fwd(emb, w, T)
+        arg = None
+        if K > 1:
+            cos, arg = _pool_fwd(cos, C, K, T, label, count)
         logits, _, _ = ops.margin_ce(cos, label, C, mode, s, m, want_logits=True)
-        ctx.save_for_backward(emb, w, label, cos, *saved)
-        ctx.cfg = (mode, s, m, T, C)
+        ctx.save_for_backward(emb, w, label, cos, arg, *saved)
+        ctx.cfg = (mode, s, m, T, C, K)
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         from .._hip import lib, dtype_id
-        emb, w, label, cos, *saved = ctx.saved_tensors
-        mode, s, m, T, C = ctx.cfg
+        emb, w, label, cos, arg, *saved = ctx.saved_tensors
+        mode, s, m, T, C, K = ctx.cfg
         B, Cp = cos.shape
         dlogits = dlogits.contiguous().float()
         dcos = torch.zeros((B, Cp), dtype=T, device=emb.device)
         lib.pfr_margin_bwd(cos.data_ptr(), label.data_ptr(), B, C, Cp, ops.MARGIN_MODES[mode], float(s), float(m),
                            dlogits.data_ptr(), dcos.data_ptr(), dtype_id(T), torch.cuda.current_stream().cuda_stream)
+        if K > 1:
+            dcos = ops.subcenter_scatter(dcos, arg, K, ld_sub=_cpad(C * K, T))
         demb, dw = _cosine_bwd(dcos, emb, w, saved, T)
-        return demb, dw, None, None, None, None, None
+        return demb, dw, None, None, None, None, None, None, None
 
 
 class FocalCEFunction(torch.autograd.Function):
