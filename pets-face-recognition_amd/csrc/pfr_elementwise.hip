@@ -300,9 +300,10 @@ extern "C" int pfr_bn_stats(const void* x, int dtype, long rows, int C, float* p
 //      mean, invstd, scale = γ·invstd, shift = β − mean·scale, running stats.
 // Two-pass Chan merge about the group / grand mean.  Level 1 (only when there are many parts) merges groups of parts
 // in parallel (grid = C/16 x groups) into a small [groups][2][C] (+ counts) buffer, level 2 finishes.
+// (pfr_bn_stats rounds rows / gx up, so its last parts can start behind the last row: they hold (0, 0) and count 0 rows, not `left` < 0)
 __device__ __forceinline__ float part_rows(long total, long rpp, int i) {
   const long left = total - (long)i * rpp;
-  return (float)(left < rpp ? left : rpp);
+  return (float)(left < rpp ? (left > 0 ? left : 0) : rpp);
 }
 
 // merges parts [pbeg, pend) for 16 channels; returns (via lane pl==0) n, mean, M2.  counts: optional per-part row counts.
@@ -1642,7 +1643,9 @@ __global__ void avgpool_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx,
 extern "C" int pfr_avgpool_fwd(const void* x, void* y, int dtype, int N, int HW, int C, hipStream_t st) {
   PFR_CHECK_ARG(x && y, "pfr_avgpool_fwd: null pointer");
   const int kp = dtype == PFR_BF16 ? 8 : 4;
+  PFR_CHECK_ARG(N >= 0 && HW > 0 && C >= 0 && C % kp == 0, "pfr_avgpool_fwd: C %% %d != 0 or bad extents", kp);
   const size_t n = (size_t)N * (C / kp);
+  if (n == 0) return PFR_OK;
   const unsigned blocks = (unsigned)((n + 63) / 64);
   if (dtype == PFR_BF16)
     hipLaunchKernelGGL(avgpool_fwd_kernel<bf16_t>, dim3(blocks), dim3(64), 0, st, (const bf16_t*)x, (bf16_t*)y, N, HW, C);
@@ -1654,7 +1657,9 @@ extern "C" int pfr_avgpool_fwd(const void* x, void* y, int dtype, int N, int HW,
 extern "C" int pfr_avgpool_bwd(const void* dy, void* dx, int dtype, int N, int HW, int C, hipStream_t st) {
   PFR_CHECK_ARG(dy && dx, "pfr_avgpool_bwd: null pointer");
   const int kp = dtype == PFR_BF16 ? 8 : 4;
+  PFR_CHECK_ARG(N >= 0 && HW > 0 && C >= 0 && C % kp == 0, "pfr_avgpool_bwd: C %% %d != 0 or bad extents", kp);
   const size_t nch = (size_t)N * HW * (C / kp);
+  if (nch == 0) return PFR_OK;
   unsigned blocks = (unsigned)((nch + 255) / 256);
   if (blocks > 8192) blocks = 8192;
   if (dtype == PFR_BF16)
@@ -1899,7 +1904,12 @@ __global__ __launch_bounds__(256) void colsum_final_batch_kernel(const ColsumDes
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int r = r0 + 16 * k;
-        if (r < d.n) acc[k] = d.mt > 0 ? fmaf(v[k], (float)min(d.mt, d.rows - r * d.mt), acc[k]) : acc[k] + v[k];
+        if (r >= d.n) continue;
+        if (d.mt > 0) acc[k] = fmaf(v[k], (float)min(d.mt, d.rows - r * d.mt), acc[k]);
+        // plain partial rows: colsum_final_kernel's order of additions, so that the deferred merge gives pfr_colsum's sums bit for bit —
+        // four accumulators over rows r, r+16, r+32, r+48 while a whole group of four is left, the last rows all into the first
+        else if (r0 + 64 * (k >> 2) + 48 < d.n) acc[k & 3] += v[k];
+        else acc[0] += v[k];
       }
     }
   }
