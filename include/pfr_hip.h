@@ -671,6 +671,33 @@ int pfr_bn_residual_rows(const void* z, const float* a, const float* b, const vo
                          int N, int HW, int C, pfr_stream_t stream);
 int pfr_row_scale(const void* x, const float* row_scale, void* y, int dtype, int N, int HW, int C, pfr_stream_t stream);
 
+/* ---- fused multi-head self-attention over the whole token sequence (csrc/pfr_mha.hip; torchvision vision_transformer.py
+ * EncoderBlock: `self.self_attention(x, x, x, need_weights=False)` between in_proj and out_proj) ----------------------------------
+ * qkv [B][S][3*heads*head_dim] (q|k|v, each (head, d)): the row layout nn.MultiheadAttention's in_proj produces and pfr_window_attn_*
+ * already uses.  out [B][S][heads*head_dim]; lse fp32 [B][heads][S] (log-sum-exp of the scaled scores, saved for the backward; may be
+ * NULL in inference).  head_dim == 64 and 1 <= S <= 257, fp32 or bf16: pfr_mha_supported (host arithmetic only) is 1 when a kernel
+ * takes the shape, and any other shape is an argument error of pfr_mha_fwd / pfr_mha_bwd, never a different computation.
+ * The B*heads*S*S scores are never written to memory.  bf16: one workgroup per (batch, head), K / V (backward: Q, K, V, dout) rows
+ * in LDS with zero-filled padding rows, MFMA products, fp32 softmax with a running maximum, P rounded to bf16.  Backward = the
+ * recompute form (P = exp(s - lse), D = rowsum(dout * out)); dqkv [B][S][3*heads*head_dim] is OVERWRITTEN, complete per workgroup:
+ * no atomics, bit-reproducible.  Rows at or beyond S are never stored. */
+int pfr_mha_fwd(const void* qkv, void* out, float* lse, int dtype, int B, int S, int heads, int head_dim, float scale, pfr_stream_t stream);
+int pfr_mha_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int dtype, int B, int S, int heads,
+                int head_dim, float scale, pfr_stream_t stream);
+int pfr_mha_supported(int dtype, int S, int heads, int head_dim);
+/* token assembly of the Vision Transformer (activations in `dtype`, D a multiple of the 16-byte chunk; class_token [D] and pos [S][D]
+ * are the fp32 master parameters, their gradients fp32 and OVERWRITTEN, sums over b in ascending order):
+ *   pfr_vit_tokens_fwd:  tok[b][0] = class_token + pos[0];  tok[b][s] = patches[b][s-1] + pos[s]     (patches [B][S-1][D], tok [B][S][D])
+ *   pfr_vit_tokens_bwd:  dpatches[b][s-1] = dtok[b][s];  dpos[s] = sum_b dtok[b][s];  dclass_token = sum_b dtok[b][0]
+ *   pfr_vit_cls_fwd:     y[b] = x[b][0]                          (the class-token rows, [B][D], that encoder.ln and the head read)
+ *   pfr_vit_cls_bwd:     dx[b][0] = dy[b], dx[b][s > 0] = 0 */
+int pfr_vit_tokens_fwd(const void* patches, const float* class_token, const float* pos, void* tok, int dtype, int B, int S, int D,
+                       pfr_stream_t stream);
+int pfr_vit_tokens_bwd(const void* dtok, void* dpatches, float* dpos, float* dclass_token, int dtype, int B, int S, int D,
+                       pfr_stream_t stream);
+int pfr_vit_cls_fwd(const void* x, void* y, int dtype, int B, int S, int D, pfr_stream_t stream);
+int pfr_vit_cls_bwd(const void* dy, void* dx, int dtype, int B, int S, int D, pfr_stream_t stream);
+
 /* ---- gradient all-reduce over RCCL / xGMI (csrc/pfr_comm.hip) ---------------------------------------------
  * For hosts that bind this library directly; replaces DistributedDataParallel's bucket all-reduce (utils/__init__.py:114-119).
  * RCCL is resolved with dlopen at first use (no load-time dependency).  pfr_comm_unique_id: rank 0 fills a 128-byte id, the

@@ -88,6 +88,10 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
             model_ = getattr(models, arch)(**kw, **(model_kwargs or {}))
             model_.classifier = torch.nn.Linear(model_.classifier[1].in_features, 512)
             return model_
+        if arch.startswith('vit'):   # the FE line of a ViT backbone: `model_ = models.vit_b_16(); model_.heads = torch.nn.Linear(768, 512)`
+            model_ = getattr(models, arch)(**kw, **(model_kwargs or {}))
+            model_.heads = torch.nn.Linear(model_.hidden_dim, 512)
+            return model_
         model_ = getattr(models, arch)(**kw)
         model_.fc = torch.nn.Linear(model_.fc.in_features, 512)
         return model_
@@ -100,7 +104,8 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
                                           loss_kwargs=loss_kwargs, arc_margin=True, sub_centers=sub_centers)
 
     def optimizer(model_):
-        head = 'classifier' if arch.startswith(('convnext', 'mobilenet', 'efficientnet')) else 'fc'   # the reference's backbone / embedding-layer split
+        # the reference's backbone / embedding-layer split ('fc'); the embedding layer of the torchvision-style backbones is `classifier` / `heads`
+        head = 'classifier' if arch.startswith(('convnext', 'mobilenet', 'efficientnet')) else ('heads' if arch.startswith('vit') else 'fc')
         params1 = [p for i, p in model_.module.named_parameters() if head not in i]
         params2 = [p for i, p in model_.module.named_parameters() if head in i]
         base = _live('init_lr', 10 ** -2 if optimizer_kind == 'sgd' else 10 ** -3)
