@@ -510,6 +510,33 @@ long pfr_augment_geo_ws_bytes(int N, int out_h, int out_w);
 int pfr_augment_train_geo(const unsigned char* x, int N, int H, int W, int crop_h, int crop_w, int out_h, int out_w,
                           const int* records, float* y, void* ws, pfr_stream_t stream);
 
+/* ---- flip, ColorJitter, grayscale and erasing on the device (csrc/pfr_augment_color.hip), bit-exact with the Pillow arithmetic
+ * torchvision's PIL-image transforms run (tools/color_augment_np.py is the restatement the tests pin against Pillow):
+ * RandomHorizontalFlip = Image.transpose(FLIP_LEFT_RIGHT); ColorJitter = randperm(4) order of ImageEnhance.Brightness / Contrast /
+ * Color (.enhance(f) = Image.blend(degenerate, img, f)) and adjust_hue (convert('HSV'), H += uint8(hue * 255), convert('RGB'));
+ * RandomGrayscale = convert('L') on three channels; RandomErasing = tensor[..., i:i+h, j:j+w] = value after ToTensor.
+ * pfr_augment_color_params (HOST arrays; no device work): per sample flip / gray flags int32 [N], order int32 [N][4] (a permutation of
+ * the op ids 0 brightness, 1 contrast, 2 saturation, 3 hue, in the order they run), factors float32 [N][3] (brightness, contrast,
+ * saturation), hue float32 [N] in [-0.5, 0.5]; ops_mask bit k = op k is on in this pipeline (an op that is off is dropped from the
+ * order) → records int32 [N][12] = flip, gray, order[4] (-1 = none), the three factors' bit patterns, the hue shift byte, pad[2];
+ * *mask_out = 1 (a sample flips) | 2 (jitter or grayscale runs) | 4 (Contrast runs: the per-image mean pass is needed).
+ * pfr_augment_color: x uint8 [N][H][W][3] → out (same shape): flip → jitter → grayscale per the uploaded records; `mask` selects
+ * the parts to honour (bits as above; 2 alone or 6 may run in place, out == x).  ws: pfr_augment_color_ws_bytes(N) (int64 L sums).
+ * pfr_augment_erase_params (HOST): rects int32 [N][5] = (erase, i, j, h, w), value float32 [3] → records int32 [N][8] and the largest
+ * rectangle's area; a rectangle outside the H x W image is refused.  pfr_augment_erase: y float32 [N][3][H][W] in place.
+ * pfr_augment_train_geo_color: pfr_augment_train_geo with the pre-pass in the body order (flip → crop → resize → rotate →
+ * ColorJitter → grayscale → sharpness → autocontrast → ToTensor); ws: pfr_augment_geo_color_ws_bytes. */
+int pfr_augment_color_params(const int* flip, const int* gray, const int* order, const float* factors, const float* hue, int ops_mask,
+                             int N, int* records, int* mask_out);
+long pfr_augment_color_ws_bytes(int N);
+int pfr_augment_color(const unsigned char* x, int N, int H, int W, const int* color_records, int mask, unsigned char* out, void* ws,
+                      pfr_stream_t stream);
+int pfr_augment_erase_params(const int* rects, const float* value, int N, int H, int W, int* records, int* max_area);
+int pfr_augment_erase(float* y, int N, int H, int W, const int* erase_records, int max_area, pfr_stream_t stream);
+long pfr_augment_geo_color_ws_bytes(int N, int H, int W, int out_h, int out_w, int color_mask);
+int pfr_augment_train_geo_color(const unsigned char* x, int N, int H, int W, int crop_h, int crop_w, int out_h, int out_w,
+                                const int* records, const int* color_records, int color_mask, float* y, void* ws, pfr_stream_t stream);
+
 /* ---- fit stage: a ragged batch of uint8 HWC frames → one uniform uint8 canvas, bit-exact with Pillow (csrc/pfr_augment_fit.hip).
  * mode 0 RESIZE: Image.resize((canvas_w, canvas_h), BILINEAR) (simple / no-align configs, simple_fe_dog.py:17-31), with the
  * per-image sharpness / autocontrast pre-ops applied to the raw frame; mode 1 THUMBNAIL_PAD: Image.thumbnail((canvas_w, canvas_h),

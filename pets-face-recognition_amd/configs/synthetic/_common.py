@@ -32,7 +32,10 @@ def _live(key, default):
 def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs, device, n_epochs=1, seed=0,
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
          noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
-         ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd', sub_centers=1):
+         ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd', sub_centers=1, augment_extra=None):
+    # augment_extra: further DeviceAugmentation keywords of the train pipeline (p_hflip, color_jitter, p_grayscale, erasing); None = the reference's pipeline
+    if augment_extra and not device_augment:
+        raise ValueError("augment_extra configures the device pipeline (device_augment=True)")
     # sub_centers: K centres per class in the margin head (losses/large_margin.py); 1 = the reference's head
     # optimizer_kind: 'sgd' (the reference's SGD + MultiStepLR) or 'adamw' (FusedAdamW on the device, torch.optim.AdamW on the CPU)
     if optimizer_kind not in ('sgd', 'adamw'):
@@ -144,13 +147,13 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         gen = torch.Generator().manual_seed(seed + _rank())
         hw, crop = (image_size, image_size), (image_size - 4, image_size - 4)
         fit, order = (('resize', hw), 'color_first') if pipeline == 'simple' else (('thumbnail_pad', hw), 'geometry_first')
-        ns['device_train_augmentation'] = DeviceAugmentation(crop, hw, 0.1, 0.3, 5.0, gen, fit=fit, order=order)
+        ns['device_train_augmentation'] = DeviceAugmentation(crop, hw, 0.1, 0.3, 5.0, gen, fit=fit, order=order, **(augment_extra or {}))
         ns['device_val_augmentation'] = DeviceAugmentation(None, None, 0.0, 0.0, 0.0, fit=fit)
     elif device_augment:
         # the reference's train/val Compose pipelines (fe_dogs_config.py:17-32) applied on the device to uint8 batches
         from data_loading import DeviceAugmentation, val_augmentation
         ns['device_train_augmentation'] = DeviceAugmentation((image_size - 4, image_size - 4), (image_size, image_size), 0.1, 0.3,
-                                                             5.0, torch.Generator().manual_seed(seed + _rank()))
+                                                             5.0, torch.Generator().manual_seed(seed + _rank()), **(augment_extra or {}))
         ns['device_val_augmentation'] = val_augmentation()
     # the reference's commented-out `gradient_clip_val=1, gradient_clip_algorithm='norm'` trainer_kwargs (fe_dogs_config.py:146-147):
     # passed on only when set, so that the other configs build exactly the trainer they did

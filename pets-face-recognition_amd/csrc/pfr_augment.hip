@@ -334,28 +334,60 @@ extern "C" long pfr_augment_geo_ws_bytes(int N, int out_h, int out_w) {
   return (((long)N * out_h * out_w * 3 + 255) & ~255L) + pfr_augment_ws_bytes(N, out_h, out_w);
 }
 
-extern "C" int pfr_augment_train_geo(const unsigned char* x, int N, int H, int W, int crop_h, int crop_w, int out_h, int out_w,
-                                     const int* records, float* y, void* ws, hipStream_t st) {
-  PFR_CHECK_ARG(x && records && y && ws, "pfr_augment_train_geo: null pointer");
+// crec / cmask: the colour pre-pass of pfr_augment_train_geo_color (csrc/pfr_augment_color.hip); crec = nullptr → none
+static int train_geo_impl(const char* who, const unsigned char* x, int N, int H, int W, int crop_h, int crop_w, int out_h, int out_w,
+                          const int* records, const int* crec, int cmask, float* y, void* ws, hipStream_t st) {
+  PFR_CHECK_ARG(x && records && y && ws, "%s: null pointer", who);
   PFR_CHECK_ARG(N > 0 && N <= 65535 && crop_h > 0 && crop_w > 0 && crop_h <= H && crop_w <= W && out_h > 0 && out_w > 0,
-                "pfr_augment_train_geo: bad sizes (N=%d %dx%d crop %dx%d out %dx%d)", N, H, W, crop_h, crop_w, out_h, out_w);
+                "%s: bad sizes (N=%d %dx%d crop %dx%d out %dx%d)", who, N, H, W, crop_h, crop_w, out_h, out_w);
   CoefTable tx, ty;
   if (!get_coef(crop_w, out_w, &tx) || !get_coef(crop_h, out_h, &ty)) {
-    pfr_set_error("pfr_augment_train_geo: resize %dx%d -> %dx%d needs more than %d taps or table allocation failed", crop_h, crop_w,
-                  out_h, out_w, AUG_MAXK);
+    pfr_set_error("%s: resize %dx%d -> %dx%d needs more than %d taps or table allocation failed", who, crop_h, crop_w, out_h, out_w,
+                  AUG_MAXK);
     return PFR_ERR_UNSUPPORTED;
   }
   const size_t img = (size_t)N * out_h * out_w * 3;
   uint8_t* geo = (uint8_t*)ws;
   uint8_t* blur = geo + ((img + 255) & ~(size_t)255);
   int* lohi = (int*)(blur + ((img + 255) & ~(size_t)255));
+  uint8_t* cws = (uint8_t*)ws + ((pfr_augment_geo_ws_bytes(N, out_h, out_w) + 255) & ~255L);   // colour: per-image sums, then the flipped source
+  if (crec && (cmask & 1)) {
+    // RandomHorizontalFlip sits in front of the crop: a mirrored copy of the source
+    uint8_t* flipped = cws + pfr_augment_color_ws_bytes(N);
+    const int rc = pfr_augment_color(x, N, H, W, crec, 1, flipped, cws, st);
+    if (rc != PFR_OK) return rc;
+    x = flipped;
+  }
   const dim3 grid((out_h * out_w + 255) / 256, N);
   hipLaunchKernelGGL(aug_geo_kernel, grid, dim3(256), 0, st, x, H, W, crop_h, crop_w, out_h, out_w, records, tx.dev, tx.ksize, ty.dev,
                      ty.ksize, geo);
   PFR_CHECK_LAUNCH();
+  if (crec && (cmask & 2)) {
+    // ColorJitter / grayscale on the rotated image, in place (pointwise)
+    const int rc = pfr_augment_color(geo, N, out_h, out_w, crec, cmask & 6, geo, cws, st);
+    if (rc != PFR_OK) return rc;
+  }
   hipLaunchKernelGGL(aug_pre_kernel, dim3(N, AUG_SLABS), dim3(1024), 0, st, geo, out_h, out_w, records, blur, lohi);
   PFR_CHECK_LAUNCH();
   hipLaunchKernelGGL(aug_tensor_kernel, grid, dim3(256), 0, st, geo, blur, out_h, out_w, records, lohi, y);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
+}
+
+extern "C" int pfr_augment_train_geo(const unsigned char* x, int N, int H, int W, int crop_h, int crop_w, int out_h, int out_w,
+                                     const int* records, float* y, void* ws, hipStream_t st) {
+  return train_geo_impl("pfr_augment_train_geo", x, N, H, W, crop_h, crop_w, out_h, out_w, records, nullptr, 0, y, ws, st);
+}
+
+// geometry-first with the colour pre-pass: flip → crop → resize → rotate → ColorJitter → grayscale → sharpness → autocontrast → ToTensor
+extern "C" long pfr_augment_geo_color_ws_bytes(int N, int H, int W, int out_h, int out_w, int color_mask) {
+  return ((pfr_augment_geo_ws_bytes(N, out_h, out_w) + 255) & ~255L) + pfr_augment_color_ws_bytes(N) + ((color_mask & 1) ? (long)N * H * W * 3 : 0);
+}
+
+extern "C" int pfr_augment_train_geo_color(const unsigned char* x, int N, int H, int W, int crop_h, int crop_w, int out_h, int out_w,
+                                           const int* records, const int* color_records, int color_mask, float* y, void* ws,
+                                           hipStream_t st) {
+  PFR_CHECK_ARG(color_records && color_mask > 0 && color_mask < 8, "pfr_augment_train_geo_color: no colour records or mask %d outside [1, 7]",
+                color_mask);
+  return train_geo_impl("pfr_augment_train_geo_color", x, N, H, W, crop_h, crop_w, out_h, out_w, records, color_records, color_mask, y, ws, st);
 }

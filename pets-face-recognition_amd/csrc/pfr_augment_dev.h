@@ -7,6 +7,11 @@
 #define AUG_PREC 22     // Resample.c PRECISION_BITS = 32 - 8 - 2
 #define AUG_SLABS 8     // row slabs per image in the pre passes (one workgroup each); lo/hi partials are merged by the consumer
 
+// the colour pre-pass (pfr_augment_color.hip), which the geometry-first pipeline of pfr_augment.hip runs between its own kernels
+extern "C" long pfr_augment_color_ws_bytes(int N);
+extern "C" int pfr_augment_color(const unsigned char* x, int N, int H, int W, const int* color_records, int mask, unsigned char* out,
+                                 void* ws, hipStream_t st);
+
 __device__ __forceinline__ int wave_min_i(int v) {
   for (int o = 32; o; o >>= 1) v = min(v, __shfl_xor(v, o));
   return v;
