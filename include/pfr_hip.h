@@ -336,6 +336,34 @@ int pfr_subcenter_pool(const float* cos_sub, int B, int C, int K, int ld_sub, fl
                        int32_t* count, pfr_stream_t stream);
 int pfr_subcenter_scatter(const void* dcos, int dtype, const uint8_t* arg, int B, int C, int K, int ldc, void* dcos_sub, int ld_sub,
                           pfr_stream_t stream);
+/* Adaptive margins, kind 0 = AdaFace (Kim et al., CVPR 2022), 1 = CurricularFace (Huang et al., CVPR 2020).  Neither is in the
+ * reference; as torch ops each is several B x C temporaries, a boolean mask, an indexed write and a scatter_ around the margin.
+ * pfr_margin_prepare: one launch of one workgroup, fixed-order sums (no atomics: the same bits every launch), nothing read by the host.
+ *   AdaFace replaces `a = norms.clip(1e-3, 100); mean = a.mean(); std = a.std(); batch_mean = t*mean + (1-t)*batch_mean` (likewise
+ *   batch_std, left alone at B = 1); `k = (h * (a - batch_mean) / (batch_std + eps)).clip(-1, 1); g_ang = -m*k; g_add = m + m*k`:
+ *   inv_norm [B] is what pfr_l2norm_fwd wrote (a = 1 / inv_norm), mean and the centred squares are two passes, state0 / state1 are the
+ *   module's batch_mean / batch_std (updated in place when update != 0), `momentum` is t_alpha, row_margin [B][2] = {g_ang, g_add}
+ *   from the buffers after the update, state_used [2] = {batch_mean, batch_std} as this call used them.
+ *   CurricularFace replaces `t = momentum * cos[range(B), label].clamp(-1, 1).mean() + (1 - momentum) * t`: state0 is t (state1,
+ *   inv_norm, row_margin unused, may be NULL), state_used = {t, 0}.  cos is the [B][ldc] fp32 class-cosine matrix (after sub-centre pooling).
+ * pfr_margin_ce_adaptive: pfr_margin_ce_ex's row kernel (same logits / loss_rows / row_stats / grad_scale* / dcos conventions, plain and
+ *   focal cross-entropy, class weights, label smoothing) with the margin kind as a compile-time switch; the learnable focal alpha is
+ *   not available.  It reads row_margin (AdaFace) / state_used (CurricularFace) as pfr_margin_prepare wrote them for this step.
+ *   AdaFace: c^ = clamp(cos, -1+eps, 1-eps) on every entry; target: theta' = clip(acos(c^) + g_ang, eps, pi - eps), l_t = s * (cos theta'
+ *   - g_add), d l_t / d cos = s * sin theta' / sin theta; no gradient where a clamp or the clip is active.  `m` is unused.
+ *   CurricularFace: cos clamped to [-1, 1]; target: ArcFace's hard margin (mode 0 of pfr_margin_ce); a negative with cos > cos(theta_t + m)
+ *   is s * cos * (t + cos) with derivative s * (t + 2 cos).  `eps` is unused.
+ * pfr_margin_bwd_adaptive: pfr_margin_bwd for these margins, dcos = s * dlogits * d l / d cos. */
+int pfr_margin_prepare(int kind, const float* inv_norm, const float* cos, const int64_t* label, int B, int ldc, float m, float h,
+                       float momentum, float eps, int update, float* state0, float* state1, float* row_margin, float* state_used,
+                       pfr_stream_t stream);
+int pfr_margin_ce_adaptive(const float* cos, const int64_t* label, int B, int C, int ldc, int kind, float s, float m, float eps,
+                           float gamma, const float* class_weight, float label_smoothing, const float* row_margin,
+                           const float* state_used, float grad_scale, const float* grad_scale_dev, const float* grad_scale_dev2,
+                           float* logits, float* loss_rows, float* row_stats, void* dcos, int dcos_dtype, pfr_stream_t stream);
+int pfr_margin_bwd_adaptive(const float* cos, const int64_t* label, int B, int C, int ldc, int kind, float s, float m, float eps,
+                            const float* row_margin, const float* state_used, const float* dlogits, void* dcos, int dcos_dtype,
+                            pfr_stream_t stream);
 
 /* ---- optimiser steps over flat fp32 master buffers (configs/dog_fe/fe_dogs_config.py:123-133; body_dog_fe.py:121-131) */
 int pfr_sgd_step(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,

@@ -389,6 +389,108 @@ def subcenter_scatter(dcos, arg, K, ld_sub=None, out=None):
     return out
 
 
+MARGIN_KINDS = {"adaface": 0, "curricular": 1}
+
+
+def _margin_kind(kind, who):
+    if kind not in MARGIN_KINDS:
+        raise PfrError(f"{who}: margin kind must be one of {sorted(MARGIN_KINDS)}, got {kind!r}")
+    return MARGIN_KINDS[kind]
+
+
+def _chk_f32(t, shape, device, name):
+    _chk(t, name)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise PfrError(f"{name}: expected a contiguous fp32 {list(shape)} tensor on {device}")
+
+
+def _chk_cos_label(cosv, label, C, who):
+    _chk(cosv, f"{who}: cos")
+    _chk(label, f"{who}: label")
+    if cosv.dim() != 2 or cosv.dtype != torch.float32 or cosv.shape[1] < C or C < 1:
+        raise PfrError(f"{who}: cos must be fp32 [B, >= C={C}]")
+    if label.dtype != torch.int64 or label.shape != (cosv.shape[0],) or label.device != cosv.device:
+        raise PfrError(f"{who}: label must be int64 [{cosv.shape[0]}] on {cosv.device}")
+
+
+def margin_prepare(kind, state, B, inv_norm=None, cosv=None, label=None, m=0.0, h=0.0, momentum=0.01, eps=1e-3, update=True):
+    """The per-step state of an adaptive margin in one launch -> (row_margin [B, 2] or None, state_used [2]).
+    'adaface': state = (batch_mean, batch_std), one-element fp32 tensors updated in place when `update`; reads inv_norm [B].
+    'curricular': state = (t,); reads the target cosines of cosv [B, ldc] / label [B]."""
+    k = _margin_kind(kind, "margin_prepare")
+    if len(state) != (2 if kind == "adaface" else 1):
+        raise PfrError(f"margin_prepare: '{kind}' takes {2 if kind == 'adaface' else 1} state buffer(s), got {len(state)}")
+    dev = state[0].device
+    for i, t in enumerate(state):
+        _chk_f32(t.view(-1), (1,), dev, f"margin_prepare: state[{i}]")
+    if not 0.0 <= momentum <= 1.0:
+        raise PfrError(f"margin_prepare: momentum {momentum} outside [0, 1]")
+    row_margin = None
+    ldc = 0
+    if kind == "adaface":
+        if inv_norm is None:
+            raise PfrError("margin_prepare: 'adaface' needs inv_norm")
+        _chk_f32(inv_norm, (B,), dev, "margin_prepare: inv_norm")
+        row_margin = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    else:
+        if cosv is None or label is None:
+            raise PfrError("margin_prepare: 'curricular' needs the cosines and the labels")
+        _chk_cos_label(cosv, label, 1, "margin_prepare")
+        if cosv.shape[0] != B or cosv.device != dev:
+            raise PfrError(f"margin_prepare: cos must have {B} rows on {dev}")
+        ldc = cosv.shape[1]
+    state_used = torch.empty(2, dtype=torch.float32, device=dev)
+    lib.pfr_margin_prepare(k, _p(inv_norm), _p(cosv), _p(label), B, ldc, float(m), float(h), float(momentum), float(eps), int(bool(update)),
+                           _p(state[0]), _p(state[1]) if len(state) > 1 else 0, _p(row_margin), _p(state_used), _stream())
+    return row_margin, state_used
+
+
+def _chk_adaptive_state(kind, B, row_margin, state_used, device, who):
+    if kind == "adaface":
+        if row_margin is None:
+            raise PfrError(f"{who}: 'adaface' needs margin_prepare's row_margin")
+        _chk_f32(row_margin, (B, 2), device, f"{who}: row_margin")
+    if state_used is None:
+        raise PfrError(f"{who}: needs margin_prepare's state_used")
+    _chk_f32(state_used, (2,), device, f"{who}: state_used")
+
+
+def margin_ce_adaptive(cosv, label, C, kind, s, m, eps, row_margin, state_used, gamma=0.0, class_weight=None, label_smoothing=0.0,
+                       grad_scale=1.0, grad_scale_dev=None, grad_scale_dev2=None, want_logits=True, want_stats=True, dcos_dtype=None):
+    """margin_ce_ex for the adaptive margins ('adaface' / 'curricular') -> (logits, loss_rows, row_stats [B, 4], dcos)"""
+    k = _margin_kind(kind, "margin_ce_adaptive")
+    _chk_cos_label(cosv, label, C, "margin_ce_adaptive")
+    B, ldc = cosv.shape
+    _chk_adaptive_state(kind, B, row_margin, state_used, cosv.device, "margin_ce_adaptive")
+    _chk_class_vector(class_weight, C, cosv.device, "margin_ce_adaptive: class_weight")
+    if dcos_dtype not in (None, torch.float32, torch.bfloat16):
+        raise PfrError(f"margin_ce_adaptive: dcos dtype must be fp32 or bf16, got {dcos_dtype}")
+    logits = torch.empty((B, C), dtype=torch.float32, device=cosv.device) if want_logits else None
+    loss_rows = torch.empty(B, dtype=torch.float32, device=cosv.device)
+    stats = torch.empty((B, 4), dtype=torch.float32, device=cosv.device) if want_stats else None
+    dcos = None if dcos_dtype is None else torch.zeros((B, ldc), dtype=dcos_dtype, device=cosv.device)
+    lib.pfr_margin_ce_adaptive(_p(cosv), _p(label), B, C, ldc, k, float(s), float(m), float(eps), float(gamma), _p(class_weight),
+                               float(label_smoothing), _p(row_margin), _p(state_used), float(grad_scale), _p(grad_scale_dev),
+                               _p(grad_scale_dev2), _p(logits), _p(loss_rows), _p(stats), _p(dcos),
+                               PFR_F32 if dcos is None else dtype_id(dcos.dtype), _stream())
+    return logits, loss_rows, stats, dcos
+
+
+def margin_bwd_adaptive(cosv, label, C, kind, s, m, eps, row_margin, state_used, dlogits, dcos_dtype):
+    """dlogits [B, C] fp32 -> dcos [B, ldc] (pad columns 0) through the adaptive margin"""
+    k = _margin_kind(kind, "margin_bwd_adaptive")
+    _chk_cos_label(cosv, label, C, "margin_bwd_adaptive")
+    B, ldc = cosv.shape
+    _chk_adaptive_state(kind, B, row_margin, state_used, cosv.device, "margin_bwd_adaptive")
+    _chk_f32(dlogits, (B, C), cosv.device, "margin_bwd_adaptive: dlogits")
+    if dcos_dtype not in (torch.float32, torch.bfloat16):
+        raise PfrError(f"margin_bwd_adaptive: dcos dtype must be fp32 or bf16, got {dcos_dtype}")
+    dcos = torch.zeros((B, ldc), dtype=dcos_dtype, device=cosv.device)
+    lib.pfr_margin_bwd_adaptive(_p(cosv), _p(label), B, C, ldc, k, float(s), float(m), float(eps), _p(row_margin), _p(state_used),
+                                _p(dlogits), _p(dcos), dtype_id(dcos_dtype), _stream())
+    return dcos
+
+
 # ------------------------------------------------------------------------------------------------ optimisers
 def sgd_step(p, g, mom, shadow, lr, momentum, weight_decay, grad_scale=1.0, first_step=False):
     lib.pfr_sgd_step(_p(p), _p(g), _p(mom), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),

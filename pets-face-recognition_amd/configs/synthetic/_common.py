@@ -32,10 +32,12 @@ def _live(key, default):
 def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs, device, n_epochs=1, seed=0,
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
          noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
-         ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd', sub_centers=1, augment_extra=None):
+         ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd', sub_centers=1, augment_extra=None, margin=None,
+         margin_kwargs=None):
     # augment_extra: further DeviceAugmentation keywords of the train pipeline (p_hflip, color_jitter, p_grayscale, erasing); None = the reference's pipeline
     if augment_extra and not device_augment:
         raise ValueError("augment_extra configures the device pipeline (device_augment=True)")
+    # margin / margin_kwargs: 'adaface' / 'curricular' replace the ArcFace head (losses/large_margin.py); None = the reference's head
     # sub_centers: K centres per class in the margin head (losses/large_margin.py); 1 = the reference's head
     # optimizer_kind: 'sgd' (the reference's SGD + MultiStepLR) or 'adamw' (FusedAdamW on the device, torch.optim.AdamW on the CPU)
     if optimizer_kind not in ('sgd', 'adamw'):
@@ -103,8 +105,14 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         _ = config
         # loss_kwargs go to FocalLoss (is_focal) or nn.CrossEntropyLoss as in the reference (losses/__init__.py:28-33).  A learnable
         # FocalLoss alpha is in no optimizer group below, as in the reference's configs: it stays at its initial ones unless a config adds it.
+        # margin / margin_kwargs are passed on only when set, so that the other configs build exactly the head they did
+        margin_args = {}
+        if margin is not None:
+            margin_args['margin'] = margin
+        if margin_kwargs is not None:
+            margin_args['margin_kwargs'] = margin_kwargs
         return SoftmaxBasedMetricLearning(model=model_, num_class=n_train_ids, embedding_size=512, is_focal=is_focal,
-                                          loss_kwargs=loss_kwargs, arc_margin=True, sub_centers=sub_centers)
+                                          loss_kwargs=loss_kwargs, arc_margin=True, sub_centers=sub_centers, **margin_args)
 
     def optimizer(model_):
         # the reference's backbone / embedding-layer split ('fc'); the embedding layer of the torchvision-style backbones is `classifier` / `heads`

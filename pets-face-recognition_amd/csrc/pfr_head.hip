@@ -722,3 +722,340 @@ extern "C" int pfr_subcenter_scatter(const void* dcos, int dtype, const uint8_t*
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }
+
+// ---- adaptive margins: AdaFace (Kim et al., CVPR 2022: the margin is a function of the sample's feature norm) and CurricularFace
+// (Huang et al., CVPR 2020: hard negatives are re-weighted by t + cos, t an EMA of the target cosines).  Neither is in the reference.
+// One small launch (margin_prepare_kernel) turns the batch into the per-row margins / the scalar t and moves the module's EMA buffers on
+// the device; the row kernel below is margin_ce_kernel with the margin kind as a second compile-time switch.  What a step used
+// (state_used, row_margin) is a per-call copy: the backward of a step never reads the buffers a later forward may have moved.
+enum { MK_ADAFACE = 0, MK_CURRICULAR = 1 };
+struct AdaptiveParams {
+  float s, m, eps, gamma;
+  float cos_m, sin_m, th, mm;   // CurricularFace: ArcFace's hard margin on the target
+};
+
+// 256 threads, fixed tree: the same bits every launch
+__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+// one workgroup; sums in fp64 (B values: the cost is the launch), results rounded to fp32 once.
+// AdaFace: a = clip(1 / inv_norm, 1e-3, 100); mean, then the centred squares (two passes); EMA of both into state0 / state1 when
+//   `update` (state1 keeps its value at B = 1: the unbiased deviation is undefined); row_margin[b] = {g_ang, g_add} from the buffers
+//   after the update; state_used = {batch_mean, batch_std}.
+// CurricularFace: t <- momentum * mean_b clamp(cos[b][label_b], -1, 1) + (1 - momentum) * t when `update`; state_used = {t, 0}.
+template <int KIND>
+__global__ __launch_bounds__(256) void margin_prepare_kernel(const float* __restrict__ inv_norm, const float* __restrict__ cosv,
+                                                             const int64_t* __restrict__ label, int B, int ldc, float m, float h,
+                                                             float momentum, float eps, int update, float* __restrict__ state0,
+                                                             float* __restrict__ state1, float* __restrict__ row_margin,
+                                                             float* __restrict__ state_used) {
+  __shared__ double sh[256];
+  const double mom = (double)momentum;
+  if constexpr (KIND == MK_ADAFACE) {
+    double bm = (double)state0[0], bs = (double)state1[0];   // read before the barriers below, written after them
+    if (update) {
+      double a = 0.0;
+      for (int i = threadIdx.x; i < B; i += 256) a += fmin(fmax(1.0 / (double)inv_norm[i], 1e-3), 100.0);
+      const double mu = block_sum_f64(a, sh) / (double)B;
+      bm = (double)(float)(mom * mu + (1.0 - mom) * bm);
+      if (B > 1) {
+        double q = 0.0;
+        for (int i = threadIdx.x; i < B; i += 256) {
+          const double d = fmin(fmax(1.0 / (double)inv_norm[i], 1e-3), 100.0) - mu;
+          q = fma(d, d, q);
+        }
+        const double sigma = sqrt(block_sum_f64(q, sh) / (double)(B - 1));
+        bs = (double)(float)(mom * sigma + (1.0 - mom) * bs);
+      }
+      if (threadIdx.x == 0) {
+        state0[0] = (float)bm;
+        state1[0] = (float)bs;
+      }
+    }
+    if (threadIdx.x == 0) {
+      state_used[0] = (float)bm;
+      state_used[1] = (float)bs;
+    }
+    for (int i = threadIdx.x; i < B; i += 256) {
+      const double a = fmin(fmax(1.0 / (double)inv_norm[i], 1e-3), 100.0);
+      const double k = fmin(fmax((double)h * (a - bm) / (bs + (double)eps), -1.0), 1.0);
+      row_margin[2 * (size_t)i] = (float)(-(double)m * k);
+      row_margin[2 * (size_t)i + 1] = (float)((double)m + (double)m * k);
+    }
+  } else {
+    double t = (double)state0[0];
+    if (update) {
+      double a = 0.0;
+      for (int i = threadIdx.x; i < B; i += 256) a += (double)fminf(fmaxf(cosv[(size_t)i * ldc + (int)label[i]], -1.f), 1.f);
+      const double mu = block_sum_f64(a, sh) / (double)B;
+      t = (double)(float)(mom * mu + (1.0 - mom) * t);
+      if (threadIdx.x == 0) state0[0] = (float)t;
+    }
+    if (threadIdx.x == 0) {
+      state_used[0] = (float)t;
+      state_used[1] = 0.f;
+    }
+  }
+}
+
+extern "C" int pfr_margin_prepare(int kind, const float* inv_norm, const float* cosv, const int64_t* label, int B, int ldc, float m, float h,
+                                  float momentum, float eps, int update, float* state0, float* state1, float* row_margin, float* state_used,
+                                  hipStream_t st) {
+  PFR_CHECK_ARG(kind == MK_ADAFACE || kind == MK_CURRICULAR, "pfr_margin_prepare: bad margin kind %d", kind);
+  PFR_CHECK_ARG(B > 0, "pfr_margin_prepare: bad shape B=%d", B);
+  PFR_CHECK_ARG(state0 && state_used, "pfr_margin_prepare: null pointer");
+  PFR_CHECK_ARG(momentum >= 0.f && momentum <= 1.f, "pfr_margin_prepare: momentum %g outside [0, 1]", (double)momentum);
+  if (kind == MK_ADAFACE) {
+    PFR_CHECK_ARG(inv_norm && state1 && row_margin, "pfr_margin_prepare: null pointer (AdaFace reads inv_norm, writes batch_std and row_margin)");
+    hipLaunchKernelGGL(margin_prepare_kernel<MK_ADAFACE>, dim3(1), dim3(256), 0, st, inv_norm, cosv, label, B, ldc, m, h, momentum, eps, update,
+                       state0, state1, row_margin, state_used);
+  } else {
+    PFR_CHECK_ARG(cosv && label && ldc > 0, "pfr_margin_prepare: null pointer (CurricularFace reads the target cosines)");
+    hipLaunchKernelGGL(margin_prepare_kernel<MK_CURRICULAR>, dim3(1), dim3(256), 0, st, inv_norm, cosv, label, B, ldc, m, h, momentum, eps, update,
+                       state0, state1, row_margin, state_used);
+  }
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// What a row needs once: the target's margin value phi and d phi / d cos, and two numbers (a, b) for the per-entry work.
+//   AdaFace:        a, b = the clamp's edges -1 + eps, 1 - eps;  acosf / cosf / sinf run here, once per row
+//   CurricularFace: a = t, b = cos(theta + m) of the target (the threshold of a hard negative)
+template <int KIND>
+__device__ __forceinline__ void adaptive_row(float craw, int row, const AdaptiveParams& ap, const float* __restrict__ row_margin,
+                                             const float* __restrict__ state_used, float& phi, float& dphi, float& a, float& b) {
+  if constexpr (KIND == MK_ADAFACE) {
+    a = -1.f + ap.eps;
+    b = 1.f - ap.eps;
+    const float ct = fminf(fmaxf(craw, a), b);
+    const float g_ang = row_margin[2 * (size_t)row], g_add = row_margin[2 * (size_t)row + 1];
+    const float theta = acosf(ct);
+    const float lo = ap.eps, hi = 3.14159265358979f - ap.eps;
+    const float tp = theta + g_ang;
+    const float tc = fminf(fmaxf(tp, lo), hi);
+    phi = cosf(tc) - g_add;
+    const bool flat = tp < lo || tp > hi || craw < a || craw > b;   // a clip or the clamp is active: no gradient
+    dphi = flat ? 0.f : sinf(tc) / sqrtf(fmaxf(1.f - ct * ct, 0.f));  // sin(theta) >= sqrt(2 eps) > 0 inside the clamp
+  } else {
+    const float ct = fminf(fmaxf(craw, -1.f), 1.f);
+    const float sine = sqrtf(fmaxf(1.f - ct * ct, 0.f));
+    const float ph = ct * ap.cos_m - sine * ap.sin_m;
+    const float dph = ap.cos_m + (sine > 0.f ? ap.sin_m * ct / sine : 0.f);
+    const bool take = ct > ap.th;
+    phi = take ? ph : ct - ap.mm;
+    dphi = (craw < -1.f || craw > 1.f) ? 0.f : (take ? dph : 1.f);
+    a = state_used[0];
+    b = ph;
+  }
+}
+// a negative's value on the cosine side (the logit is s times it) ...
+template <int KIND>
+__device__ __forceinline__ float adaptive_neg(float c, float a, float b) {
+  if constexpr (KIND == MK_ADAFACE) return fminf(fmaxf(c, a), b);
+  const float cc = fminf(fmaxf(c, -1.f), 1.f);
+  return cc > b ? cc * (a + cc) : cc;
+}
+// ... and its derivative
+template <int KIND>
+__device__ __forceinline__ float adaptive_dneg(float c, float a, float b) {
+  if constexpr (KIND == MK_ADAFACE) return (c < a || c > b) ? 0.f : 1.f;
+  if (c < -1.f || c > 1.f) return 0.f;
+  return c > b ? fmaf(2.f, c, a) : 1.f;
+}
+
+// margin_ce_kernel (same passes, same row_stats / gscale conventions, same dcos dtypes) with the margin kind as a compile-time switch
+template <typename TG, int CRIT, int KIND>
+__global__ __launch_bounds__(1024) void margin_ce_adaptive_kernel(const float* __restrict__ cosv, const int64_t* __restrict__ label,
+                                                                 AdaptiveParams ap, const float* __restrict__ row_margin,
+                                                                 const float* __restrict__ state_used, float* __restrict__ logits,
+                                                                 float* __restrict__ loss_rows, TG* __restrict__ dcos, int C, int ldc,
+                                                                 float gscale, const float* __restrict__ gscale_dev, CritParams cp) {
+  static_assert(CRIT == CRIT_PLAIN || CRIT == CRIT_WCE, "the learnable alpha is not fused with the adaptive margins");
+  __shared__ float sh[16];
+  if (gscale_dev) gscale *= gscale_dev[0];
+  if (CRIT == CRIT_WCE && cp.gscale_dev2) gscale *= cp.gscale_dev2[0];
+  const int row = blockIdx.x;
+  const int nt = blockDim.x;
+  const float* cr = cosv + (size_t)row * ldc;
+  const int t = (int)label[row];
+  float phi, dphi, ma, mb;
+  adaptive_row<KIND>(cr[t], row, ap, row_margin, state_used, phi, dphi, ma, mb);
+  const float lt = ap.s * phi;
+  if constexpr (CRIT == CRIT_PLAIN) {
+    float mx = -INFINITY;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : ap.s * adaptive_neg<KIND>(cr[j], ma, mb);
+      mx = fmaxf(mx, l);
+    }
+    mx = block_reduce_max(mx, sh);
+    float se = 0.f;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : ap.s * adaptive_neg<KIND>(cr[j], ma, mb);
+      se += expf(l - mx);
+    }
+    se = block_reduce_sum(se, sh);
+    const float lse = mx + logf(se);
+    const float logp = lse - lt;
+    const float pt = expf(-logp);
+    float f = 1.f, lossv = logp;
+    if (ap.gamma != 0.f) {
+      const float om = fmaxf(1.f - pt, 0.f);
+      lossv = powf(om, ap.gamma) * logp;
+      f = powf(om, ap.gamma) + ap.gamma * logp * pt * powf(om, ap.gamma - 1.f);
+    }
+    if (threadIdx.x == 0 && loss_rows) loss_rows[row] = lossv;
+    if (threadIdx.x == 0 && cp.row_stats) reinterpret_cast<f32x4*>(cp.row_stats)[row] = f32x4{lse, f, lt, 1.f};
+    const float gs = gscale * f;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float c = cr[j];
+      const float l = (j == t) ? lt : ap.s * adaptive_neg<KIND>(c, ma, mb);
+      if (logits) logits[(size_t)row * C + j] = l;
+      if (dcos) {
+        const float p = expf(l - lse);
+        const float d = (j == t) ? (p - 1.f) * dphi : p * adaptive_dneg<KIND>(c, ma, mb);
+        dcos[(size_t)row * ldc + j] = from_f32<TG>(d * ap.s * gs);
+      }
+    }
+  } else {
+    const float e = cp.smoothing, wt = cp.weight ? cp.weight[t] : 1.f;
+    float mx = -INFINITY;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : ap.s * adaptive_neg<KIND>(cr[j], ma, mb);
+      mx = fmaxf(mx, l);
+    }
+    mx = block_reduce_max(mx, sh);
+    float se = 0.f, swl = 0.f, sw = 0.f;
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float l = (j == t) ? lt : ap.s * adaptive_neg<KIND>(cr[j], ma, mb);
+      se += expf(l - mx);
+      if (e != 0.f) {
+        if (cp.weight) {
+          const float w = cp.weight[j];
+          swl = fmaf(w, l, swl);
+          sw += w;
+        } else {
+          swl += l;
+        }
+      }
+    }
+    se = block_reduce_sum(se, sh);
+    float W = (float)C;
+    if (e != 0.f) {
+      swl = block_reduce_sum(swl, sh);
+      if (cp.weight) W = block_reduce_sum(sw, sh);
+    }
+    const float lse = mx + logf(se);
+    const float hard = (1.f - e) * wt, soft = e / (float)C;
+    float lossv = hard * (lse - lt), S = hard;
+    if (e != 0.f) {
+      lossv += soft * (W * lse - swl);
+      S += soft * W;
+    }
+    if (threadIdx.x == 0 && loss_rows) loss_rows[row] = lossv;
+    if (threadIdx.x == 0 && cp.row_stats) reinterpret_cast<f32x4*>(cp.row_stats)[row] = f32x4{lse, S, lt, wt};
+    for (int j = threadIdx.x; j < C; j += nt) {
+      const float c = cr[j];
+      const float l = (j == t) ? lt : ap.s * adaptive_neg<KIND>(c, ma, mb);
+      if (logits) logits[(size_t)row * C + j] = l;
+      if (dcos) {
+        float d = S * expf(l - lse);
+        if (e != 0.f) d -= soft * (cp.weight ? cp.weight[j] : 1.f);
+        d = (j == t) ? (d - hard) * dphi : d * adaptive_dneg<KIND>(c, ma, mb);
+        dcos[(size_t)row * ldc + j] = from_f32<TG>(d * ap.s * gscale);
+      }
+    }
+  }
+}
+
+static void adaptive_params(AdaptiveParams& ap, float s, float m, float eps, float gamma) {
+  ap.s = s; ap.m = m; ap.eps = eps; ap.gamma = gamma;
+  ap.cos_m = (float)cos((double)m);
+  ap.sin_m = (float)sin((double)m);
+  ap.th = (float)cos(M_PI - (double)m);
+  ap.mm = (float)(sin(M_PI - (double)m) * (double)m);
+}
+
+template <int CRIT, int KIND>
+static void launch_margin_ce_adaptive(const float* cosv, const int64_t* label, int B, int C, int ldc, const AdaptiveParams& ap,
+                                      const float* row_margin, const float* state_used, float grad_scale, const float* grad_scale_dev,
+                                      float* logits, float* loss_rows, void* dcos, int dcos_dtype, const CritParams& cp, hipStream_t st) {
+  const int nt = C >= 4096 ? 1024 : 256;
+  if (dcos_dtype == PFR_BF16)
+    hipLaunchKernelGGL((margin_ce_adaptive_kernel<bf16_t, CRIT, KIND>), dim3(B), dim3(nt), 0, st, cosv, label, ap, row_margin, state_used, logits, loss_rows, (bf16_t*)dcos, C, ldc, grad_scale, grad_scale_dev, cp);
+  else
+    hipLaunchKernelGGL((margin_ce_adaptive_kernel<float, CRIT, KIND>), dim3(B), dim3(nt), 0, st, cosv, label, ap, row_margin, state_used, logits, loss_rows, (float*)dcos, C, ldc, grad_scale, grad_scale_dev, cp);
+}
+
+extern "C" int pfr_margin_ce_adaptive(const float* cosv, const int64_t* label, int B, int C, int ldc, int kind, float s, float m, float eps,
+                                      float gamma, const float* class_weight, float label_smoothing, const float* row_margin,
+                                      const float* state_used, float grad_scale, const float* grad_scale_dev, const float* grad_scale_dev2,
+                                      float* logits, float* loss_rows, float* row_stats, void* dcos, int dcos_dtype, hipStream_t st) {
+  PFR_CHECK_ARG(cosv && label, "pfr_margin_ce_adaptive: null pointer");
+  PFR_CHECK_ARG(B > 0 && C > 0 && (ldc <= 0 || ldc >= C), "pfr_margin_ce_adaptive: bad shape B=%d C=%d ldc=%d", B, C, ldc);
+  PFR_CHECK_ARG(kind == MK_ADAFACE || kind == MK_CURRICULAR, "pfr_margin_ce_adaptive: bad margin kind %d", kind);
+  PFR_CHECK_ARG(kind == MK_ADAFACE ? row_margin != nullptr : state_used != nullptr,
+                "pfr_margin_ce_adaptive: null pointer (AdaFace reads row_margin, CurricularFace state_used: pfr_margin_prepare writes both)");
+  PFR_CHECK_ARG(kind != MK_ADAFACE || (eps > 0.f && eps < 1.f), "pfr_margin_ce_adaptive: eps %g outside (0, 1)", (double)eps);
+  PFR_CHECK_ARG(label_smoothing >= 0.f && label_smoothing <= 1.f, "pfr_margin_ce_adaptive: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  PFR_CHECK_ARG(dcos_dtype == PFR_F32 || dcos_dtype == PFR_BF16, "pfr_margin_ce_adaptive: bad dcos dtype %d", dcos_dtype);
+  const bool wce = class_weight || label_smoothing != 0.f;
+  if (wce && gamma != 0.f) { pfr_set_error("pfr_margin_ce_adaptive: focal gamma excludes class_weight / label_smoothing"); return PFR_ERR_UNSUPPORTED; }
+  PFR_CHECK_ARG(wce || !grad_scale_dev2, "pfr_margin_ce_adaptive: grad_scale_dev2 belongs to the weighted mean only");
+  AdaptiveParams ap;
+  adaptive_params(ap, s, m, eps, gamma);
+  if (ldc <= 0) ldc = C;
+  CritParams cp{nullptr, class_weight, label_smoothing, row_stats, grad_scale_dev2};
+#define MCA(CRIT, KIND) launch_margin_ce_adaptive<CRIT, KIND>(cosv, label, B, C, ldc, ap, row_margin, state_used, grad_scale, grad_scale_dev, logits, loss_rows, dcos, dcos_dtype, cp, st)
+  if (kind == MK_ADAFACE) { if (wce) MCA(CRIT_WCE, MK_ADAFACE); else MCA(CRIT_PLAIN, MK_ADAFACE); }
+  else { if (wce) MCA(CRIT_WCE, MK_CURRICULAR); else MCA(CRIT_PLAIN, MK_CURRICULAR); }
+#undef MCA
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// standalone backward of the adaptive margins (the unfused path: the heads as separate modules, or a criterion the row kernel does not
+// fuse): dcos = s * dlogits * d l / d cos, the derivatives of adaptive_row / adaptive_dneg
+template <typename TG, int KIND>
+__global__ __launch_bounds__(256) void margin_bwd_adaptive_kernel(const float* __restrict__ cosv, const int64_t* __restrict__ label,
+                                                                  AdaptiveParams ap, const float* __restrict__ row_margin,
+                                                                  const float* __restrict__ state_used, const float* __restrict__ dlogits,
+                                                                  TG* __restrict__ dcos, int C, int ldc) {
+  const int row = blockIdx.x;
+  const float* cr = cosv + (size_t)row * ldc;
+  const int t = (int)label[row];
+  float phi, dphi, ma, mb;
+  adaptive_row<KIND>(cr[t], row, ap, row_margin, state_used, phi, dphi, ma, mb);
+  for (int j = threadIdx.x; j < C; j += 256) {
+    const float d = dlogits[(size_t)row * C + j] * ap.s * ((j == t) ? dphi : adaptive_dneg<KIND>(cr[j], ma, mb));
+    dcos[(size_t)row * ldc + j] = from_f32<TG>(d);
+  }
+}
+extern "C" int pfr_margin_bwd_adaptive(const float* cosv, const int64_t* label, int B, int C, int ldc, int kind, float s, float m, float eps,
+                                       const float* row_margin, const float* state_used, const float* dlogits, void* dcos, int dcos_dtype,
+                                       hipStream_t st) {
+  PFR_CHECK_ARG(cosv && label && dlogits && dcos, "pfr_margin_bwd_adaptive: null pointer");
+  PFR_CHECK_ARG(B > 0 && C > 0 && (ldc <= 0 || ldc >= C), "pfr_margin_bwd_adaptive: bad shape B=%d C=%d ldc=%d", B, C, ldc);
+  PFR_CHECK_ARG(kind == MK_ADAFACE || kind == MK_CURRICULAR, "pfr_margin_bwd_adaptive: bad margin kind %d", kind);
+  PFR_CHECK_ARG(kind == MK_ADAFACE ? row_margin != nullptr : state_used != nullptr,
+                "pfr_margin_bwd_adaptive: null pointer (AdaFace reads row_margin, CurricularFace state_used: pfr_margin_prepare writes both)");
+  PFR_CHECK_ARG(kind != MK_ADAFACE || (eps > 0.f && eps < 1.f), "pfr_margin_bwd_adaptive: eps %g outside (0, 1)", (double)eps);
+  PFR_CHECK_ARG(dcos_dtype == PFR_F32 || dcos_dtype == PFR_BF16, "pfr_margin_bwd_adaptive: bad dcos dtype %d", dcos_dtype);
+  AdaptiveParams ap;
+  adaptive_params(ap, s, m, eps, 0.f);
+  if (ldc <= 0) ldc = C;
+#define MBA(TG, KIND) hipLaunchKernelGGL((margin_bwd_adaptive_kernel<TG, KIND>), dim3(B), dim3(256), 0, st, cosv, label, ap, row_margin, state_used, dlogits, (TG*)dcos, C, ldc)
+  if (kind == MK_ADAFACE) { if (dcos_dtype == PFR_BF16) MBA(bf16_t, MK_ADAFACE); else MBA(float, MK_ADAFACE); }
+  else { if (dcos_dtype == PFR_BF16) MBA(bf16_t, MK_CURRICULAR); else MBA(float, MK_CURRICULAR); }
+#undef MBA
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}

@@ -5,16 +5,25 @@ None`, else `{'loss', 'emb', 'logits'}`; a list/tuple of images is embedded one 
 import torch
 import torch.nn as nn
 
-from .large_margin import ArcMarginProduct, AddMarginProduct, _MarginHead
+from .large_margin import ArcMarginProduct, AddMarginProduct, AdaFaceProduct, CurricularFaceProduct, _MarginHead
 from .losses import FocalLoss, describe_criterion
+
+
+_ADAPTIVE_HEADS = {"adaface": AdaFaceProduct, "curricular": CurricularFaceProduct}
 
 
 class SoftmaxBasedMetricLearning(nn.Module):
     def __init__(self, model, num_class, embedding_size=512, s=64.0, m=0.5, is_focal=False, loss_kwargs=None,
-                 arc_margin=False, easy_margin=False, sub_centers=1):
+                 arc_margin=False, easy_margin=False, sub_centers=1, margin=None, margin_kwargs=None):
         super().__init__()
         # sub_centers (not in the reference): K centres per class in the head, see losses/large_margin.py; `logits` stay [B, num_class]
-        if arc_margin:
+        # margin (not in the reference): None = arc_margin / easy_margin choose the head as ever; 'adaface' / 'curricular' build
+        # AdaFaceProduct / CurricularFaceProduct(s=s, **margin_kwargs) (their own default m unless margin_kwargs sets one)
+        if margin in _ADAPTIVE_HEADS:
+            self.add_margin = _ADAPTIVE_HEADS[margin](embedding_size, num_class, s=s, sub_centers=sub_centers, **(margin_kwargs or {}))
+        elif margin is not None:
+            raise ValueError(f"margin must be None or one of {sorted(_ADAPTIVE_HEADS)}, got {margin!r}")
+        elif arc_margin:
             self.add_margin = ArcMarginProduct(embedding_size, num_class, s=s, m=m, easy_margin=easy_margin, sub_centers=sub_centers)
         else:
             self.add_margin = AddMarginProduct(embedding_size, num_class, s=s, m=m, sub_centers=sub_centers)
@@ -30,13 +39,17 @@ class SoftmaxBasedMetricLearning(nn.Module):
         Fused: FocalLoss with a fixed or an adaptive (learnable) alpha; nn.CrossEntropyLoss with `weight`, `label_smoothing` and
         reduction 'mean' / 'sum'.  Left unfused on purpose: reduction='none', a non-default ignore_index, a weight / alpha that is not an
         fp32 [num_class] tensor on the embedding's device, CPU tensors, anything but a [B, in_features] embedding, a head weight that
-        is not [out_features * sub_centers, in_features]."""
+        is not [out_features * sub_centers, in_features], a learnable focal alpha together with an adaptive margin (AdaFace /
+        CurricularFace: the column kernel of d loss / d alpha recomputes the fixed margins' logits)."""
         head = self.add_margin
         if not emb.is_cuda or not isinstance(head, _MarginHead) or emb.dim() != 2 or emb.shape[1] != head.in_features:
             return None
         if head.weight.shape[0] != head.out_features * head.sub_centers:
             return None
-        return describe_criterion(self.focal_loss, head.out_features, emb.device)
+        crit = describe_criterion(self.focal_loss, head.out_features, emb.device)
+        if crit is not None and crit.alpha is not None and head.hip_adaptive() is not None:
+            return None
+        return crit
 
     def _unfused(self, tensor, label):
         logits = self.add_margin(tensor, label)
@@ -56,7 +69,11 @@ class SoftmaxBasedMetricLearning(nn.Module):
         from ._head_hip import MarginCEFunction, resolve_dtype
         head = self.add_margin
         dt = head.compute_dtype or getattr(self.module, "compute_dtype", None)
-        if head.sub_centers == 1:
+        adaptive = head.hip_adaptive()
+        if adaptive is not None:
+            loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
+                                                  resolve_dtype(dt), self.return_logits, None, head.sub_centers, head._count(), adaptive)
+        elif head.sub_centers == 1:
             loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
                                                   resolve_dtype(dt), self.return_logits, crit.alpha)
         else:

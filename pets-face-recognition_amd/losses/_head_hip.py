@@ -2,6 +2,8 @@
 
 Replaces, for CUDA tensors, the torch ops of /root/reference/losses/large_margin.py:30-40,69-84 and
 /root/reference/losses/losses.py:22-28 (see csrc/pfr_head.hip for the kernel-level mapping)."""
+from collections import namedtuple
+
 import torch
 
 from .._hip import ops, PfrError
@@ -68,6 +70,19 @@ def _split_classes(w, K):
     return w.shape[0] // K
 
 
+class AdaptiveMargin(namedtuple("AdaptiveMargin", "kind h momentum eps state update")):
+    """What the head functions need of an adaptive-margin head (losses/large_margin.py: AdaFaceProduct, CurricularFaceProduct): the kind
+    ('adaface' / 'curricular'), AdaFace's h and clamp eps, the EMA momentum (AdaFace's t_alpha), the module's persistent one-element
+    buffers ((batch_mean, batch_std) / (t,)) and whether this forward moves them (training mode)."""
+    __slots__ = ()
+
+
+def _prepare_adaptive(ad, m, inv_x, cos, label):
+    """one launch after the (pooled) cosines: updates the head's buffers on the device, returns this step's (row_margin, state_used)"""
+    return ops.margin_prepare(ad.kind, ad.state, cos.shape[0], inv_norm=inv_x, cosv=cos, label=label, m=m, h=ad.h, momentum=ad.momentum,
+                              eps=ad.eps, update=ad.update)
+
+
 class MarginCEFunction(torch.autograd.Function):
     """(emb, weight, label[, alpha]) → (loss, logits): normalise → cosine GEMM → margin → scale → criterion, fused.  `crit` is the
     losses.losses.Criterion description of the loss (gamma, adaptive alpha, class weight, label smoothing, reduction); `alpha` is the
@@ -75,10 +90,13 @@ class MarginCEFunction(torch.autograd.Function):
     Every criterion is the same launches: only the row kernel's instantiation differs, plus one column kernel for d loss / d alpha.
     K > 1 (sub-centre head, weight [C*K, D]): the cosine GEMM runs over all C*K centres, one pooling pass takes the maximum per class
     before the row kernel, one scatter pass routes dcos to the selected centres after it; `count` ([C, K] int32 or None) collects which
-    centre each sample's own class selected.  K == 1 launches neither."""
+    centre each sample's own class selected.  K == 1 launches neither.
+    `adaptive` (an AdaptiveMargin, `mode` is then its kind): one more small launch after the pooling prepares the step's margins and moves
+    the head's buffers, the row kernel is the adaptive instantiation; row_margin / state_used are saved per call, so this step's backward
+    is independent of forwards that ran after it.  The learnable alpha is not fused with these margins (losses/__init__.py:_fusable)."""
 
     @staticmethod
-    def forward(ctx, emb, weight, label, mode, s, m, crit, T, want_logits, alpha=None, K=1, count=None):
+    def forward(ctx, emb, weight, label, mode, s, m, crit, T, want_logits, alpha=None, K=1, count=None, adaptive=None):
         emb = emb.contiguous().float()
         w = weight.detach().contiguous()
         label = label.contiguous().long()
@@ -88,8 +106,21 @@ class MarginCEFunction(torch.autograd.Function):
         arg = None
         if K > 1:
             cos, arg = _pool_fwd(cos, C, K, T, label, count)
-        stats = inv_denom = None
-        if crit.is_plain:
+        stats = inv_denom = row_margin = state_used = None
+        if adaptive is not None:
+            if alpha is not None:
+                raise PfrError("the fused head does not combine a learnable focal alpha with an adaptive margin")
+            row_margin, state_used = _prepare_adaptive(adaptive, m, saved[2], cos, label)
+            logits, loss_rows, stats, _ = ops.margin_ce_adaptive(cos, label, C, mode, s, m, adaptive.eps, row_margin, state_used,
+                                                                 gamma=crit.gamma, class_weight=crit.weight, label_smoothing=crit.smoothing,
+                                                                 want_logits=want_logits, want_stats=not crit.is_plain)
+            if crit.is_plain:
+                loss = ops.mean(loss_rows)
+            elif crit.reduction == "sum":
+                loss, _ = ops.loss_reduce(loss_rows, None, "sum")
+            else:
+                loss, inv_denom = ops.loss_reduce(loss_rows, stats, "weighted_mean")
+        elif crit.is_plain:
             logits, loss_rows, _ = ops.margin_ce(cos, label, C, mode, s, m, gamma=crit.gamma, want_logits=want_logits)
             loss = ops.mean(loss_rows)
         else:
@@ -102,8 +133,8 @@ class MarginCEFunction(torch.autograd.Function):
                 loss, _ = ops.loss_reduce(loss_rows, None, "sum")
             else:   # F.cross_entropy's 'mean' divides by the sum of the targets' weights (= B without weights)
                 loss, inv_denom = ops.loss_reduce(loss_rows, stats, "weighted_mean")
-        ctx.save_for_backward(emb, w, label, cos, alpha, crit.weight, stats, inv_denom, arg, *saved)
-        ctx.cfg = (mode, s, m, crit, T, C, K)
+        ctx.save_for_backward(emb, w, label, cos, alpha, crit.weight, stats, inv_denom, arg, row_margin, state_used, *saved)
+        ctx.cfg = (mode, s, m, crit, T, C, K, None if adaptive is None else adaptive.eps)
         if logits is None:
             logits = torch.empty(0, device=emb.device)
         ctx.mark_non_differentiable(logits)
@@ -111,12 +142,17 @@ class MarginCEFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dlogits):
-        emb, w, label, cos, alpha, cweight, stats, inv_denom, arg, *saved = ctx.saved_tensors
-        mode, s, m, crit, T, C, K = ctx.cfg
+        emb, w, label, cos, alpha, cweight, stats, inv_denom, arg, row_margin, state_used, *saved = ctx.saved_tensors
+        mode, s, m, crit, T, C, K, ad_eps = ctx.cfg
         B = emb.shape[0]
         dloss = dloss.contiguous().float()
         dalpha = None
-        if crit.is_plain:
+        if ad_eps is not None:
+            _, _, _, dcos = ops.margin_ce_adaptive(cos, label, C, mode, s, m, ad_eps, row_margin, state_used, gamma=crit.gamma,
+                                                   class_weight=cweight, label_smoothing=crit.smoothing,
+                                                   grad_scale=1.0 / B if crit.is_plain else 1.0, grad_scale_dev=dloss,
+                                                   grad_scale_dev2=inv_denom, want_logits=False, want_stats=False, dcos_dtype=T)
+        elif crit.is_plain:
             _, _, dcos = ops.margin_ce(cos, label, C, mode, s, m, gamma=crit.gamma, grad_scale=1.0 / B, grad_scale_dev=dloss,
                                        want_logits=False, dcos_dtype=T)
         else:
@@ -130,14 +166,14 @@ class MarginCEFunction(torch.autograd.Function):
         if K > 1:
             dcos = ops.subcenter_scatter(dcos, arg, K, ld_sub=_cpad(C * K, T))
         demb, dw = _cosine_bwd(dcos, emb, w, saved, T)
-        return demb, dw, None, None, None, None, None, None, None, dalpha, None, None
+        return demb, dw, None, None, None, None, None, None, None, dalpha, None, None, None
 
 
 class MarginFunction(torch.autograd.Function):
-    """(emb, weight, label) → logits; standalone ArcMarginProduct / AddMarginProduct (K, count: as in MarginCEFunction)."""
+    """(emb, weight, label) → logits; standalone ArcMarginProduct / AddMarginProduct (K, count, adaptive: as in MarginCEFunction)."""
 
     @staticmethod
-    def forward(ctx, emb, weight, label, mode, s, m, T, K=1, count=None):
+    def forward(ctx, emb, weight, label, mode, s, m, T, K=1, count=None, adaptive=None):
         emb = emb.contiguous().float()
         w = weight.detach().contiguous()
         label = label.contiguous().long()
@@ -146,25 +182,34 @@ class MarginFunction(torch.autograd.Function):
         arg = None
         if K > 1:
             cos, arg = _pool_fwd(cos, C, K, T, label, count)
-        logits, _, _ = ops.margin_ce(cos, label, C, mode, s, m, want_logits=True)
-        ctx.save_for_backward(emb, w, label, cos, arg, *saved)
-        ctx.cfg = (mode, s, m, T, C, K)
+        row_margin = state_used = None
+        if adaptive is not None:
+            row_margin, state_used = _prepare_adaptive(adaptive, m, saved[2], cos, label)
+            logits, _, _, _ = ops.margin_ce_adaptive(cos, label, C, mode, s, m, adaptive.eps, row_margin, state_used, want_logits=True,
+                                                     want_stats=False)
+        else:
+            logits, _, _ = ops.margin_ce(cos, label, C, mode, s, m, want_logits=True)
+        ctx.save_for_backward(emb, w, label, cos, arg, row_margin, state_used, *saved)
+        ctx.cfg = (mode, s, m, T, C, K, None if adaptive is None else adaptive.eps)
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         from .._hip import lib, dtype_id
-        emb, w, label, cos, arg, *saved = ctx.saved_tensors
-        mode, s, m, T, C, K = ctx.cfg
+        emb, w, label, cos, arg, row_margin, state_used, *saved = ctx.saved_tensors
+        mode, s, m, T, C, K, ad_eps = ctx.cfg
         B, Cp = cos.shape
         dlogits = dlogits.contiguous().float()
-        dcos = torch.zeros((B, Cp), dtype=T, device=emb.device)
-        lib.pfr_margin_bwd(cos.data_ptr(), label.data_ptr(), B, C, Cp, ops.MARGIN_MODES[mode], float(s), float(m),
-                           dlogits.data_ptr(), dcos.data_ptr(), dtype_id(T), torch.cuda.current_stream().cuda_stream)
+        if ad_eps is not None:
+            dcos = ops.margin_bwd_adaptive(cos, label, C, mode, s, m, ad_eps, row_margin, state_used, dlogits, T)
+        else:
+            dcos = torch.zeros((B, Cp), dtype=T, device=emb.device)
+            lib.pfr_margin_bwd(cos.data_ptr(), label.data_ptr(), B, C, Cp, ops.MARGIN_MODES[mode], float(s), float(m),
+                               dlogits.data_ptr(), dcos.data_ptr(), dtype_id(T), torch.cuda.current_stream().cuda_stream)
         if K > 1:
             dcos = ops.subcenter_scatter(dcos, arg, K, ld_sub=_cpad(C * K, T))
         demb, dw = _cosine_bwd(dcos, emb, w, saved, T)
-        return demb, dw, None, None, None, None, None, None, None
+        return demb, dw, None, None, None, None, None, None, None, None
 
 
 class FocalCEFunction(torch.autograd.Function):

@@ -8,6 +8,10 @@ Beyond the reference: `sub_centers=K` (Sub-center ArcFace, Deng et al., ECCV 202
 `(out_features * K, in_features)` with row `c*K + k` the k-th centre of class c, and the class cosine is the maximum of its K
 sub-cosines.  K = 1 (the default) is the reference's head, bit for bit.
 
+Beyond the reference as well: `AdaFaceProduct` (Kim et al., CVPR 2022: the margin follows the sample's feature norm) and
+`CurricularFaceProduct` (Huang et al., CVPR 2020: hard negatives are re-weighted by a factor that grows with training), both with
+persistent one-element statistics buffers.
+
 CUDA inputs run on the gfx950 kernels (losses/_head_hip.py); CPU inputs run the same arithmetic with torch ops."""
 import math
 
@@ -80,6 +84,10 @@ class _MarginHead(nn.Module):
     def hip_mode(self):
         return self._mode
 
+    def hip_adaptive(self):
+        """the losses._head_hip.AdaptiveMargin description of a head whose margin depends on the batch, None for a fixed margin"""
+        return None
+
     def _target_logit(self, cosine):  # torch (CPU) formulation of the margin on every entry
         raise NotImplementedError
 
@@ -91,6 +99,13 @@ class _MarginHead(nn.Module):
                                             resolve_dtype(self.compute_dtype))
             return MarginFunction.apply(input, self.weight, label, self.hip_mode(), self.s, self.m,
                                         resolve_dtype(self.compute_dtype), self.sub_centers, self._count())
+        cosine = self._cpu_cosine(input, label)
+        target = self._target_logit(cosine)
+        hot = F.one_hot(label.view(-1).long(), self.out_features).to(cosine.dtype)
+        return self.s * (hot * target + (1.0 - hot) * cosine)
+
+    def _cpu_cosine(self, input, label):
+        """class cosines [B, out_features] with torch ops: after sub-centre pooling (and counting) when K > 1"""
         cosine = F.normalize(input) @ F.normalize(self.weight).t()
         if self.sub_centers > 1:
             K = self.sub_centers
@@ -100,9 +115,7 @@ class _MarginHead(nn.Module):
                 t = label.view(-1).long()
                 hit = t * K + arg[torch.arange(t.numel()), t]
                 count.view(-1).add_(torch.bincount(hit, minlength=count.numel()).to(count.dtype))
-        target = self._target_logit(cosine)
-        hot = F.one_hot(label.view(-1).long(), self.out_features).to(cosine.dtype)
-        return self.s * (hot * target + (1.0 - hot) * cosine)
+        return cosine
 
 
 class AddMarginProduct(_MarginHead):
@@ -136,3 +149,93 @@ class ArcMarginProduct(_MarginHead):
         if self.easy_margin:
             return torch.where(cosine > 0, shifted, cosine)
         return torch.where(cosine > self.th, shifted, cosine - self.mm)
+
+
+class _AdaptiveMarginHead(_MarginHead):
+    """A head whose margin depends on the batch through persistent statistics buffers.  CUDA inputs: one extra small launch prepares the
+    step's margins and moves the buffers on the device (csrc/pfr_head.hip: margin_prepare_kernel), the row kernel is the adaptive
+    instantiation.  CPU inputs: `_adaptive_logits`, the same arithmetic in torch ops."""
+
+    def forward(self, input, label):
+        if input.is_cuda:
+            from ._head_hip import MarginFunction, resolve_dtype
+            return MarginFunction.apply(input, self.weight, label, self.hip_mode(), self.s, self.m, resolve_dtype(self.compute_dtype),
+                                        self.sub_centers, self._count(), self.hip_adaptive())
+        return self._adaptive_logits(input, self._cpu_cosine(input, label), label.view(-1).long())
+
+    def _adaptive_logits(self, input, cosine, label):
+        raise NotImplementedError
+
+
+class AdaFaceProduct(_AdaptiveMarginHead):
+    """AdaFace (Kim et al., CVPR 2022): the feature norm, a proxy of image quality, moves the margin between an angular one (low norm)
+    and an additive one (high norm): k = clip(h * (|x| - batch_mean) / (batch_std + eps), -1, 1), target logit
+    s * (cos(clip(theta - m k, eps, pi - eps)) - (m + m k)), every cosine clamped to [-1 + eps, 1 - eps].  No gradient flows through the
+    norm, the statistics or the margins.
+    `batch_mean` (initially 20) and `batch_std` (initially 100) are persistent one-element fp32 buffers: exponential moving averages
+    (`t_alpha`) of the batch's mean norm and unbiased deviation, updated by training-mode forwards and used after the update; a batch
+    of one leaves `batch_std` alone.  Under data parallelism the buffers are per rank and not synchronised, as the BatchNorm running
+    statistics of the backbones are here: every rank averages the norms of its own share of the batches."""
+    _mode = "adaface"
+
+    def __init__(self, in_features, out_features, s=64.0, m=0.4, h=0.333, t_alpha=0.01, sub_centers=1, eps=1e-3, **_):
+        super().__init__(in_features, out_features, s, m, sub_centers)
+        self.h, self.t_alpha, self.eps = h, t_alpha, eps
+        self.register_buffer("batch_mean", torch.full((1,), 20.0))
+        self.register_buffer("batch_std", torch.full((1,), 100.0))
+
+    def hip_adaptive(self):
+        from ._head_hip import AdaptiveMargin
+        return AdaptiveMargin("adaface", self.h, self.t_alpha, self.eps, (self.batch_mean, self.batch_std), self.training)
+
+    def _adaptive_logits(self, input, cosine, label):
+        eps, m = self.eps, self.m
+        c = cosine.clamp(-1.0 + eps, 1.0 - eps)
+        with torch.no_grad():
+            a = input.norm(dim=1).clamp_min(1e-12).clip(1e-3, 100.0).to(c.dtype)
+            if self.training:
+                self.batch_mean.copy_(self.t_alpha * a.mean() + (1.0 - self.t_alpha) * self.batch_mean)
+                if a.numel() > 1:
+                    self.batch_std.copy_(self.t_alpha * a.std() + (1.0 - self.t_alpha) * self.batch_std)
+            k = (self.h * (a - self.batch_mean.to(c.dtype)) / (self.batch_std.to(c.dtype) + eps)).clip(-1.0, 1.0)
+            g_ang, g_add = -m * k, m + m * k
+        theta = torch.acos(c.gather(1, label[:, None]).squeeze(1))
+        phi = torch.cos((theta + g_ang).clip(eps, math.pi - eps)) - g_add
+        hot = F.one_hot(label, self.out_features).bool()
+        return self.s * torch.where(hot, phi[:, None], c)
+
+
+class CurricularFaceProduct(_AdaptiveMarginHead):
+    """CurricularFace (Huang et al., CVPR 2020): ArcFace's hard margin on the target, and every negative harder than the shifted target
+    (cos_j > cos(theta_t + m)) becomes cos_j * (t + cos_j): easy negatives first, hard ones as t grows.  No gradient flows through t or
+    the mask.
+    `t` (initially 0) is a persistent one-element fp32 buffer: the exponential moving average (`momentum`) of the batch's mean target
+    cosine, updated by training-mode forwards and used after the update.  Under data parallelism it is per rank and not synchronised,
+    as the BatchNorm running statistics of the backbones are here."""
+    _mode = "curricular"
+
+    def __init__(self, in_features, out_features, s=64.0, m=0.5, momentum=0.01, sub_centers=1, **_):
+        super().__init__(in_features, out_features, s, m, sub_centers)
+        self.momentum = momentum
+        self.cos_m, self.sin_m = math.cos(m), math.sin(m)
+        self.th = math.cos(math.pi - m)
+        self.mm = math.sin(math.pi - m) * m
+        self.register_buffer("t", torch.zeros(1))
+
+    def hip_adaptive(self):
+        from ._head_hip import AdaptiveMargin
+        return AdaptiveMargin("curricular", 0.0, self.momentum, 0.0, (self.t,), self.training)
+
+    def _adaptive_logits(self, input, cosine, label):
+        c = cosine.clamp(-1.0, 1.0)
+        ct = c.gather(1, label[:, None]).squeeze(1)
+        phi = ct * self.cos_m - torch.sqrt((1.0 - ct * ct).clamp_min(0.0)) * self.sin_m
+        with torch.no_grad():
+            if self.training:
+                self.t.copy_(self.momentum * ct.mean() + (1.0 - self.momentum) * self.t)
+            t = self.t.to(c.dtype).clone()      # this step's value: a later forward moves the buffer
+            hard = c > phi[:, None]
+        target = torch.where(ct > self.th, phi, ct - self.mm)
+        neg = torch.where(hard, c * (t + c), c)
+        hot = F.one_hot(label, self.out_features).bool()
+        return self.s * torch.where(hot, target[:, None], neg)

@@ -4,6 +4,9 @@ bf16 and fp32 compute, two variants per criterion interleaved round by round so 
   fallback  the path before the criteria were fused, from its unfused pieces: the margin-logit kernels (add_margin), then for adaptive
             alpha one torch multiply and the device focal-CE kernel, for nn.CrossEntropyLoss torch's own ops over the B x C logits.
             (The default criterion has always been fused: its 'fallback' row is the same unfused chain, for scale.)
+The adaptive margins (AdaFace, CurricularFace; default criterion) are two more rows; their second variant is
+  torch     the head as a chain of torch ops on the same device (the modules' own CPU formulation, losses/large_margin.py, run on the
+            device tensors, then FocalLoss's torch arithmetic): there is no unfused margin kernel of that kind to fall back to.
 Prints one JSON line per (criterion, dtype): median / min ms of forward + backward per variant and the peak of
 torch.cuda.max_memory_allocated over one forward + backward above what was allocated before it.
   python tools/head_bench.py [--rounds 8] [--steps 20] [--warmup 10] [--only default] [--variants fused]"""
@@ -27,7 +30,10 @@ CRITERIA = {
     "alpha_g2": (True, dict(gamma=2, alpha=True)),
     "weight": (False, dict(weight=True)),
     "smooth0.1": (False, dict(label_smoothing=0.1)),
+    "adaface": (True, dict()),
+    "curricular": (True, dict()),
 }
+ADAPTIVE = ("adaface", "curricular")
 
 
 def main():
@@ -47,15 +53,16 @@ def main():
     g = torch.Generator().manual_seed(5)
     emb = torch.randn(B, D, generator=g).to(dev).requires_grad_(True)
     label = torch.randint(0, C, (B,), generator=g).to(dev)
-    variants = args.variants.split(",")
     for name, (is_focal, kw) in CRITERIA.items():
         if args.only and name != args.only:
             continue
+        margin = name if name in ADAPTIVE else None
+        variants = [("torch" if margin and v == "fallback" else v) for v in args.variants.split(",")]
         kw = dict(kw)
         if kw.get("weight"):
             kw["weight"] = 0.25 + 2.0 * torch.rand(C, generator=g)
         for dt in (torch.bfloat16, torch.float32):
-            wrap = SoftmaxBasedMetricLearning(nn.Identity(), C, D, is_focal=is_focal, loss_kwargs=kw, arc_margin=True).to(dev)
+            wrap = SoftmaxBasedMetricLearning(nn.Identity(), C, D, is_focal=is_focal, loss_kwargs=kw, arc_margin=True, margin=margin).to(dev)
             wrap.add_margin.compute_dtype = dt
             params = [emb] + list(wrap.parameters())
 
@@ -64,6 +71,11 @@ def main():
                     p.grad = None
                 if variant == "fused":
                     loss = wrap(emb, label)["loss"]
+                elif variant == "torch":
+                    head = wrap.add_margin
+                    logits = head._adaptive_logits(emb, head._cpu_cosine(emb, label), label)
+                    ce = nn.functional.cross_entropy(logits, label, reduction="none")
+                    loss = ((1 - torch.exp(-ce)) ** wrap.focal_loss.gamma * ce).mean()
                 else:
                     logits = wrap.add_margin(emb, label)
                     if is_focal and kw.get("alpha"):
