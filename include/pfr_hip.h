@@ -407,6 +407,34 @@ int pfr_grad_norm_chunk_elems(void);
 int pfr_grad_norm(const void* segs, const int* chunk_seg, int nseg, long nchunks, float norm_p, float max_norm, double* ws,
                   float* out, pfr_stream_t stream);
 
+/* ---- Partial FC: the margin head on a sampled subset of the class centres (csrc/pfr_pfc.hip; not in the reference) ----
+ * pfr_pfc_sample: label int64 [B], score fp32 [C] (uniform draws in [0, 1)).  key[c] = 2.0 if c occurs in label, else score[c];
+ *   index int32 [S] = the S classes with the largest key, ties towards the lower class id, ascending
+ *   (= torch.sort(key, descending=True, stable=True).indices[:S].sort().values); local_label int64 [B] = position of label[b] in index
+ *   (-1 for a label outside [0, C), which also flags no class).  Needs 1 <= S <= C and 1 <= B <= S.  ws: pfr_pfc_sample_ws_bytes(C)
+ *   bytes of device memory (host arithmetic, no device work).  All work is queued on `stream`, nothing is read back; integer
+ *   histograms and an ordered compaction: bitwise reproducible.
+ * pfr_l2norm_gather_fwd: wn[s] = W[index[s]] / max(|W[index[s]]|, eps) for s < S, W fp32 [C][D], wn [Spad][D] in out_dtype with rows
+ *   S .. Spad-1 zeroed, inv_norm fp32 [S]; wnT (NULL or [D][ldt], ldt >= Spad) the transposed copy with columns S .. Spad-1 zeroed.  The
+ *   arithmetic is pfr_l2norm_fwd's for the same D and wnT: a gathered row has the bits of the same row of the full normalisation.
+ * pfr_l2norm_gather_bwd: rows[s] = pfr_l2norm_bwd's result for row index[s] of W given dwn fp32 [>= S][D] and inv_norm [S].
+ *   dense == 0: out is fp32 [S][D].  dense != 0: out is a fp32 [C][D] buffer the caller zeroed once, row index[s] receives rows[s], and
+ *   the rows prev_index[0 .. prev_S) (the index of the call that last wrote this buffer, ascending; NULL / 0 for the first) that are not
+ *   in index are set to zero in the same launch, so the buffer always holds exactly this call's rows.
+ * pfr_sgd_step_rows: for r = index[s]: g = clamp(rows[s] * grad_scale * *clip_coef, +-clip_value) + weight_decay * p[r];
+ *   mom[r] = momentum * mom[r] + g; p[r] -= lr * mom[r] (momentum == 0: p[r] -= lr * g, mom may be NULL).  p and mom fp32 [C][D], mom
+ *   zero-initialised by the caller; clip_coef / clip_value / grad_scale as in pfr_sgd_step_clip.  Rows not listed are neither read nor
+ *   written; index must not repeat a row. */
+long pfr_pfc_sample_ws_bytes(long C);
+int pfr_pfc_sample(const void* label, int B, const float* score, int C, int S, int* index, void* local_label, void* ws,
+                   pfr_stream_t stream);
+int pfr_l2norm_gather_fwd(const float* W, const int* index, void* wn, void* wnT, int out_dtype, float* inv_norm, int S, int Spad,
+                          int C, int D, int ldt, float eps, pfr_stream_t stream);
+int pfr_l2norm_gather_bwd(const float* W, const int* index, const float* inv_norm, const float* dwn, float* out, int S, int C, int D,
+                          int dense, const int* prev_index, int prev_S, pfr_stream_t stream);
+int pfr_sgd_step_rows(float* p, const int* index, const float* rows, float* mom, int S, int C, int D, float lr, float momentum,
+                      float weight_decay, float grad_scale, const float* clip_coef, float clip_value, pfr_stream_t stream);
+
 /* ---- Swin-T feature extractor (models/swin.py:8-241): LayerNorm (29,215), exact GELU (39-43), fused shifted-window
  * attention (101-135).  Linear layers and the Unfold+Linear patch merging (a stride-f conv) use pfr_conv2d_*. */
 int pfr_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int dtype,

@@ -549,3 +549,81 @@ def weight_avg(avg, p, weight):
         raise PfrError("weight_avg: fp32 tensors of one size expected")
     _chk(avg, "avg"); _chk(p, "p")
     lib.pfr_weight_avg(_p(avg), _p(p), avg.numel(), float(weight), _stream())
+
+
+# ------------------------------------------------------------------------------------------------ Partial FC (csrc/pfr_pfc.hip)
+def _chk_t(t, name, dtype, shape=None):
+    _chk(t, name)
+    if t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise PfrError(f"{name}: expected a contiguous {dtype} tensor" + (f" of shape {tuple(shape)}" if shape is not None else "")
+                       + f", got {t.dtype} {tuple(t.shape)}")
+
+
+def pfc_sample(label, score, S, index=None, local_label=None):
+    """label int64 [B], score fp32 [C] in [0, 1) -> (index int32 [S], local_label int64 [B]): the S classes with the largest key
+    (2.0 for a class of the batch, else its score), ties towards the lower class id, ascending, and every label's position among them.
+    Queued on the current stream, no host read-back."""
+    _chk_t(label, "label", torch.int64)
+    _chk_t(score, "score", torch.float32)
+    B, C, S = label.numel(), score.numel(), int(S)
+    if index is None:
+        index = torch.empty(S, dtype=torch.int32, device=score.device)
+    if local_label is None:
+        local_label = torch.empty(B, dtype=torch.int64, device=score.device)
+    ws = torch.empty(max(lib.pfr_pfc_sample_ws_bytes(C), 4), dtype=torch.uint8, device=score.device)
+    lib.pfr_pfc_sample(_p(label), B, _p(score), C, S, _p(index), _p(local_label), _p(ws), _stream())
+    return index, local_label
+
+
+def l2norm_gather_fwd(w, index, out_dtype, spad=None, want_t=False):
+    """w fp32 [C, D], index int32 [S] -> (wn [Spad, D] out_dtype with rows S.. zero, wnT [D, Spad] or None, inv fp32 [S]):
+    row s is row index[s] of l2norm_fwd(w, out_dtype, want_t) bit for bit"""
+    _chk_t(w, "w", torch.float32)
+    _chk_t(index, "index", torch.int32)
+    C, D = w.shape
+    S = index.numel()
+    spad = S if spad is None else int(spad)
+    wn = torch.empty((spad, D), dtype=out_dtype, device=w.device)
+    wnT = torch.empty((D, spad), dtype=out_dtype, device=w.device) if want_t else None
+    inv = torch.empty(S, dtype=torch.float32, device=w.device)
+    lib.pfr_l2norm_gather_fwd(_p(w), _p(index), _p(wn), _p(wnT), dtype_id(out_dtype), _p(inv), S, spad, C, D, spad, 1e-12, _stream())
+    return wn, wnT, inv
+
+
+def l2norm_gather_bwd(w, index, inv, dwn, dense_out=None, prev_index=None):
+    """l2norm_bwd on the gathered rows: dwn fp32 [>= S, D] -> rows fp32 [S, D]; with `dense_out` (fp32 [C, D], zeroed once by the caller) the
+    rows go to dense_out[index] instead and the rows of `prev_index` (the index of the call that last wrote it) outside index are re-zeroed"""
+    _chk_t(w, "w", torch.float32)
+    _chk_t(index, "index", torch.int32)
+    C, D = w.shape
+    S = index.numel()
+    _chk_t(inv, "inv", torch.float32, (S,))
+    _chk(dwn, "dwn")
+    if dwn.dtype != torch.float32 or dwn.dim() != 2 or dwn.shape[0] < S or dwn.shape[1] != D:
+        raise PfrError(f"l2norm_gather_bwd: dwn must be fp32 [>= {S}, {D}], got {dwn.dtype} {tuple(dwn.shape)}")
+    if dense_out is None:
+        if prev_index is not None:
+            raise PfrError("l2norm_gather_bwd: prev_index belongs to the dense mode")
+        out = torch.empty((S, D), dtype=torch.float32, device=w.device)
+    else:
+        _chk_t(dense_out, "dense_out", torch.float32, (C, D))
+        out = dense_out
+        if prev_index is not None:
+            _chk_t(prev_index, "prev_index", torch.int32)
+    lib.pfr_l2norm_gather_bwd(_p(w), _p(index), _p(inv), _p(dwn), _p(out), S, C, D, int(dense_out is not None), _p(prev_index),
+                              0 if prev_index is None else prev_index.numel(), _stream())
+    return out
+
+
+def sgd_step_rows(p, index, rows, mom, lr, momentum, weight_decay, clip_coef=None, clip_value=0.0, grad_scale=1.0):
+    """SGD on the rows p[index] only (p, mom fp32 [C, D]; rows fp32 [S, D]; mom zero-initialised, None when momentum == 0):
+    g = clamp(rows * grad_scale * clip_coef, ±clip_value) + weight_decay * p[r]; mom[r] = momentum * mom[r] + g; p[r] -= lr * mom[r]"""
+    _chk_t(p, "p", torch.float32)
+    _chk_t(index, "index", torch.int32)
+    C, D = p.shape
+    S = index.numel()
+    _chk_t(rows, "rows", torch.float32, (S, D))
+    if mom is not None:
+        _chk_t(mom, "mom", torch.float32, (C, D))
+    lib.pfr_sgd_step_rows(_p(p), _p(index), _p(rows), _p(mom), S, C, D, float(lr), float(momentum), float(weight_decay), float(grad_scale),
+                          _p(clip_coef), float(clip_value), _stream())

@@ -33,7 +33,8 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
          noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
          ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd', sub_centers=1, augment_extra=None, margin=None,
-         margin_kwargs=None):
+         margin_kwargs=None, sample_rate=None, sparse_grad=None):
+    # sample_rate / sparse_grad: Partial FC in the margin head (losses/large_margin.py); None = every class is scored, as in the reference
     # augment_extra: further DeviceAugmentation keywords of the train pipeline (p_hflip, color_jitter, p_grayscale, erasing); None = the reference's pipeline
     if augment_extra and not device_augment:
         raise ValueError("augment_extra configures the device pipeline (device_augment=True)")
@@ -111,6 +112,10 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
             margin_args['margin'] = margin
         if margin_kwargs is not None:
             margin_args['margin_kwargs'] = margin_kwargs
+        if sample_rate is not None:
+            margin_args['sample_rate'] = sample_rate
+        if sparse_grad is not None:
+            margin_args['sparse_grad'] = sparse_grad
         return SoftmaxBasedMetricLearning(model=model_, num_class=n_train_ids, embedding_size=512, is_focal=is_focal,
                                           loss_kwargs=loss_kwargs, arc_margin=True, sub_centers=sub_centers, **margin_args)
 

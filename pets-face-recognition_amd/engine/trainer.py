@@ -404,7 +404,9 @@ class Trainer:
         plus 'grad_{p}_norm_total', rounded to 4 digits.  CUDA gradients: one pfr_grad_norm call and one device-to-host copy
         (PL syncs once per parameter)."""
         p = self.track_grad_norm
-        named = [(n, q.grad) for n, q in controller.named_parameters() if q.grad is not None]
+        # (a Partial FC head with sparse_grad=True has no dense gradient: its norm is that of the sampled rows, weight.row_grad[1])
+        named = [(n, q.grad if q.grad is not None else q.row_grad[1]) for n, q in controller.named_parameters()
+                 if q.grad is not None or getattr(q, 'row_grad', None) is not None]
         if not named:
             return {}
         if named[0][1].is_cuda:

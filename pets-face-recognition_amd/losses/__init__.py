@@ -1,7 +1,8 @@
 """`SoftmaxBasedMetricLearning` — backbone + cosine-margin head + criterion, with the reference's constructor
 signature, attribute names (`module`, `add_margin`, `focal_loss`) and forward contract
 (/root/reference/losses/__init__.py:8-46): `forward(img, label=None)` returns the embedding tensor when `label is
-None`, else `{'loss', 'emb', 'logits'}`; a list/tuple of images is embedded one by one and concatenated."""
+None`, else `{'loss', 'emb', 'logits'}` (a Partial FC training forward adds `'classes'` and `'local_label'`); a list/tuple of
+images is embedded one by one and concatenated."""
 import torch
 import torch.nn as nn
 
@@ -14,21 +15,31 @@ _ADAPTIVE_HEADS = {"adaface": AdaFaceProduct, "curricular": CurricularFaceProduc
 
 class SoftmaxBasedMetricLearning(nn.Module):
     def __init__(self, model, num_class, embedding_size=512, s=64.0, m=0.5, is_focal=False, loss_kwargs=None,
-                 arc_margin=False, easy_margin=False, sub_centers=1, margin=None, margin_kwargs=None):
+                 arc_margin=False, easy_margin=False, sub_centers=1, margin=None, margin_kwargs=None, sample_rate=1.0, sparse_grad=False):
         super().__init__()
+        # sample_rate / sparse_grad (not in the reference): Partial FC, see losses/large_margin.py; a sampled training forward returns
+        # `logits` [B, S] over the classes `classes` with the targets `local_label`.  Passed on only when set, so that the defaults build
+        # exactly the head they did.
+        pfc = {}
+        if sample_rate != 1.0 or sparse_grad:
+            pfc = dict(sample_rate=sample_rate, sparse_grad=sparse_grad)
         # sub_centers (not in the reference): K centres per class in the head, see losses/large_margin.py; `logits` stay [B, num_class]
         # margin (not in the reference): None = arc_margin / easy_margin choose the head as ever; 'adaface' / 'curricular' build
         # AdaFaceProduct / CurricularFaceProduct(s=s, **margin_kwargs) (their own default m unless margin_kwargs sets one)
         if margin in _ADAPTIVE_HEADS:
-            self.add_margin = _ADAPTIVE_HEADS[margin](embedding_size, num_class, s=s, sub_centers=sub_centers, **(margin_kwargs or {}))
+            self.add_margin = _ADAPTIVE_HEADS[margin](embedding_size, num_class, s=s, sub_centers=sub_centers, **pfc, **(margin_kwargs or {}))
         elif margin is not None:
             raise ValueError(f"margin must be None or one of {sorted(_ADAPTIVE_HEADS)}, got {margin!r}")
         elif arc_margin:
-            self.add_margin = ArcMarginProduct(embedding_size, num_class, s=s, m=m, easy_margin=easy_margin, sub_centers=sub_centers)
+            self.add_margin = ArcMarginProduct(embedding_size, num_class, s=s, m=m, easy_margin=easy_margin, sub_centers=sub_centers, **pfc)
         else:
-            self.add_margin = AddMarginProduct(embedding_size, num_class, s=s, m=m, sub_centers=sub_centers)
+            self.add_margin = AddMarginProduct(embedding_size, num_class, s=s, m=m, sub_centers=sub_centers, **pfc)
         loss_kwargs = loss_kwargs or {}
         self.focal_loss = FocalLoss(num_class=num_class, **loss_kwargs) if is_focal else nn.CrossEntropyLoss(**loss_kwargs)
+        if self.add_margin.sample_rate < 1.0 and (getattr(self.focal_loss, "adaptive_flag", False)
+                                                   or getattr(self.focal_loss, "weight", None) is not None):
+            raise ValueError("sample_rate < 1 (Partial FC) is not combined with a learnable focal alpha or a class weight: both are "
+                             "indexed by the class, the sampled head's logits by the sampled position")
         self.module = model
         self.softmax = nn.Softmax(dim=1)
         self.return_logits = True  # the reference always returns logits; set False to skip writing them (bench)
@@ -51,7 +62,11 @@ class SoftmaxBasedMetricLearning(nn.Module):
             return None
         return crit
 
-    def _unfused(self, tensor, label):
+    def _unfused(self, tensor, label, partial=None):
+        if partial is not None:     # Partial FC: logits [B, S], the criterion sees the labels' positions among the sampled classes
+            logits = self.add_margin(tensor, label, partial)
+            loss = self.focal_loss(logits, partial.local_label)
+            return {'loss': loss, 'emb': tensor, 'logits': logits, 'classes': partial.index, 'local_label': partial.local_label}
         logits = self.add_margin(tensor, label)
         loss = self.focal_loss(logits, label)
         return {'loss': loss, 'emb': tensor, 'logits': logits}
@@ -64,12 +79,18 @@ class SoftmaxBasedMetricLearning(nn.Module):
         if label is None:
             return tensor
         crit = self._fusable(tensor)
-        if crit is None:
-            return self._unfused(tensor, label)
-        from ._head_hip import MarginCEFunction, resolve_dtype
         head = self.add_margin
+        partial = head._partial(label) if isinstance(head, _MarginHead) else None
+        if crit is None:
+            return self._unfused(tensor, label, partial)
+        from ._head_hip import MarginCEFunction, resolve_dtype
         dt = head.compute_dtype or getattr(self.module, "compute_dtype", None)
         adaptive = head.hip_adaptive()
+        if partial is not None:
+            loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
+                                                  resolve_dtype(dt), self.return_logits, None, 1, None, adaptive, partial)
+            return {'loss': loss, 'emb': tensor, 'logits': logits if self.return_logits else None, 'classes': partial.index,
+                    'local_label': partial.local_label}
         if adaptive is not None:
             loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
                                                   resolve_dtype(dt), self.return_logits, None, head.sub_centers, head._count(), adaptive)

@@ -20,12 +20,18 @@ def _dxn_by_rows(B, Cp, T):
     return B % (8 if T == torch.bfloat16 else 4) == 0 and Cp >= 2048
 
 
-def _cosine_fwd(emb, weight, T):
-    """→ cos [B, Cpad] f32 and the saved normalised operands"""
+def _cosine_fwd(emb, weight, T, pfc=None):
+    """→ cos [B, Cpad] f32 and the saved normalised operands.  `pfc` (a PartialFC): the cosines to the S sampled centres, [B, Spad]; the
+    rows pfc.index of the weight are normalised straight into the GEMM operand (pfr_l2norm_gather_fwd), no [S, D] fp32 copy exists"""
     B, D = emb.shape
-    C = weight.shape[0]
+    C = weight.shape[0] if pfc is None else pfc.index.numel()
     Cp = _cpad(C, T)
     xn, _, inv_x = ops.l2norm_fwd(emb, T)
+    if pfc is not None:
+        wn_full, wnT, inv_w = ops.l2norm_gather_fwd(weight, pfc.index, T, spad=Cp, want_t=not _dxn_by_rows(B, Cp, T))
+        cos = torch.empty((B, 1, 1, Cp), dtype=torch.float32, device=emb.device)
+        ops.conv2d_fwd(xn.view(B, 1, 1, D), wn_full[:C].view(C, 1, 1, D), out=cos)
+        return cos.view(B, Cp), (xn, wnT, inv_x, inv_w, wn_full)
     wn_full = torch.zeros((Cp, D), dtype=T, device=emb.device) if Cp != C else torch.empty((C, D), dtype=T, device=emb.device)
     # ŵᵀ is the operand of the plain-GEMM form of dx̂ only: _cosine_bwd's row-split form reads ŵ itself (and the transposed
     # write, 2-byte elements a class apart, is most of this kernel's time at 10 000 classes)
@@ -35,8 +41,9 @@ def _cosine_fwd(emb, weight, T):
     return cos.view(B, Cp), (xn, wnT, inv_x, inv_w, wn_full)
 
 
-def _cosine_bwd(dcos, emb, weight, saved, T):
-    """dcos [B, Cpad] (compute dtype) → (demb f32 [B,D], dweight f32 [C,D])"""
+def _cosine_bwd(dcos, emb, weight, saved, T, pfc=None, param=None):
+    """dcos [B, Cpad] (compute dtype) → (demb f32 [B,D], dweight f32 [C,D]).  `pfc`: dcos is [B, Spad] over the sampled centres and the
+    weight gradient exists for those rows only, see _partial_weight_grad"""
     xn, wnT, inv_x, inv_w, wn_full = saved
     B, D = emb.shape
     C = weight.shape[0]
@@ -54,8 +61,37 @@ def _cosine_bwd(dcos, emb, weight, saved, T):
         ops.conv2d_fwd(dcos.view(B, 1, 1, Cp), wnT.view(D, 1, 1, Cp), out=dxn)
     dwn = ops.conv2d_wgrad(xn.view(B, 1, 1, D), dcos.view(B, 1, 1, Cp), 1, 1, 1, 0)  # [Cp,1,1,D] f32
     demb = ops.l2norm_bwd(emb, inv_x, dxn.view(B, D), torch.float32)
+    if pfc is not None:
+        return demb, _partial_weight_grad(weight, inv_w, dwn.view(Cp, D), pfc, param)
     dw = ops.l2norm_bwd(weight, inv_w, dwn.view(Cp, D), torch.float32, out=torch.empty_like(weight))
     return demb, dw
+
+
+def _partial_weight_grad(w, inv_w, dwn, pfc, param):
+    """Weight gradient of a Partial FC step, as what the function returns for the weight.
+    Dense mode: a [C, D] gradient whose unsampled rows are zero.  The buffer lives in the head (pfc.cache) across steps: it is zeroed
+    once, each backward writes its rows and re-zeroes only those of the backward before it.  Autograd copies it into `weight.grad` (the
+    head keeps a reference, so it is never adopted as the gradient itself).
+    Sparse mode: None; the rows are left on the parameter as `row_grad = (index, rows fp32 [S, D])` for optim.FusedSGD.  A second
+    backward before the optimizer consumed them accumulates when it reuses the same index tensor and is refused otherwise."""
+    if pfc.sparse:
+        rows = ops.l2norm_gather_bwd(w, pfc.index, inv_w, dwn)
+        have = getattr(param, "row_grad", None)
+        if have is None:
+            param.row_grad = (pfc.index, rows)
+        elif have[0] is pfc.index:
+            have[1].add_(rows)
+        else:
+            raise PfrError("Partial FC with sparse_grad=True: weight.row_grad still holds the rows of another draw; call the fused "
+                           "optimizer's zero_grad() before the next backward (gradients of different draws accumulate with sparse_grad=False)")
+        return None
+    cache = pfc.cache
+    buf, prev = cache.get("dense"), cache.get("prev")
+    grad = getattr(param, "grad", None)
+    if buf is None or buf.shape != w.shape or buf.device != w.device or (grad is not None and grad.data_ptr() == buf.data_ptr()):
+        buf, prev = torch.zeros_like(w), None
+    cache["dense"], cache["prev"] = buf, pfc.index
+    return ops.l2norm_gather_bwd(w, pfc.index, inv_w, dwn, dense_out=buf, prev_index=prev)
 
 
 def _pool_fwd(cos_sub, C, K, T, label, count):
@@ -68,6 +104,14 @@ def _split_classes(w, K):
     if not 1 <= K <= 16 or w.shape[0] % K:
         raise PfrError(f"sub-centre head: a [{w.shape[0]}, {w.shape[1]}] weight does not hold K={K} centres per class (1 <= K <= 16)")
     return w.shape[0] // K
+
+
+def _check_partial(pfc, K, alpha, class_weight):
+    if K != 1 or alpha is not None or class_weight is not None:
+        raise ValueError("Partial FC (sample_rate < 1) is not combined with sub_centers > 1, a learnable focal alpha or a class weight: "
+                         "they are indexed by the class, not by the sampled position")
+    if pfc.index.dtype != torch.int32 or pfc.local_label.dtype != torch.int64 or not pfc.index.is_cuda or not pfc.local_label.is_cuda:
+        raise PfrError("Partial FC: index must be an int32 and local_label an int64 CUDA tensor (_MarginHead.sample)")
 
 
 class AdaptiveMargin(namedtuple("AdaptiveMargin", "kind h momentum eps state update")):
@@ -93,16 +137,23 @@ class MarginCEFunction(torch.autograd.Function):
     centre each sample's own class selected.  K == 1 launches neither.
     `adaptive` (an AdaptiveMargin, `mode` is then its kind): one more small launch after the pooling prepares the step's margins and moves
     the head's buffers, the row kernel is the adaptive instantiation; row_margin / state_used are saved per call, so this step's backward
-    is independent of forwards that ran after it.  The learnable alpha is not fused with these margins (losses/__init__.py:_fusable)."""
+    is independent of forwards that ran after it.  The learnable alpha is not fused with these margins (losses/__init__.py:_fusable).
+    `pfc` (a losses.large_margin.PartialFC = (index, local_label, sparse, cache)): Partial FC, the same launches on the S sampled centres
+    [B, Spad] with the gathered normalisation kernels in place of the full ones; `logits` are [B, S].  The weight's gradient is dense with
+    zero unsampled rows, or with pfc.sparse None, the rows being left on `weight.row_grad` (_partial_weight_grad)."""
 
     @staticmethod
-    def forward(ctx, emb, weight, label, mode, s, m, crit, T, want_logits, alpha=None, K=1, count=None, adaptive=None):
+    def forward(ctx, emb, weight, label, mode, s, m, crit, T, want_logits, alpha=None, K=1, count=None, adaptive=None, pfc=None):
         emb = emb.contiguous().float()
         w = weight.detach().contiguous()
         label = label.contiguous().long()
         C = w.shape[0] if K == 1 else _split_classes(w, K)
         B = emb.shape[0]
-        cos, saved = _cosine_fwd(emb, w, T)
+        if pfc is not None:    # Partial FC: the head below runs on the S sampled centres with the labels' positions among them
+            _check_partial(pfc, K, alpha, crit.weight)
+            C, label = pfc.index.numel(), pfc.local_label.contiguous()
+        ctx.pfc, ctx.param = pfc, weight
+        cos, saved = _cosine_fwd(emb, w, T, pfc)
         arg = None
         if K > 1:
             cos, arg = _pool_fwd(cos, C, K, T, label, count)
@@ -165,20 +216,24 @@ class MarginCEFunction(torch.autograd.Function):
                 dalpha = ops.alpha_grad(cos, label, alpha, stats, C, s, grad_scale=gs, grad_scale_dev=dloss)
         if K > 1:
             dcos = ops.subcenter_scatter(dcos, arg, K, ld_sub=_cpad(C * K, T))
-        demb, dw = _cosine_bwd(dcos, emb, w, saved, T)
-        return demb, dw, None, None, None, None, None, None, None, dalpha, None, None, None
+        demb, dw = _cosine_bwd(dcos, emb, w, saved, T, ctx.pfc, ctx.param)
+        return demb, dw, None, None, None, None, None, None, None, dalpha, None, None, None, None
 
 
 class MarginFunction(torch.autograd.Function):
     """(emb, weight, label) → logits; standalone ArcMarginProduct / AddMarginProduct (K, count, adaptive: as in MarginCEFunction)."""
 
     @staticmethod
-    def forward(ctx, emb, weight, label, mode, s, m, T, K=1, count=None, adaptive=None):
+    def forward(ctx, emb, weight, label, mode, s, m, T, K=1, count=None, adaptive=None, pfc=None):
         emb = emb.contiguous().float()
         w = weight.detach().contiguous()
         label = label.contiguous().long()
         C = w.shape[0] if K == 1 else _split_classes(w, K)
-        cos, saved = _cosine_fwd(emb, w, T)
+        if pfc is not None:
+            _check_partial(pfc, K, None, None)
+            C, label = pfc.index.numel(), pfc.local_label.contiguous()
+        ctx.pfc, ctx.param = pfc, weight
+        cos, saved = _cosine_fwd(emb, w, T, pfc)
         arg = None
         if K > 1:
             cos, arg = _pool_fwd(cos, C, K, T, label, count)
@@ -208,8 +263,8 @@ class MarginFunction(torch.autograd.Function):
                                dlogits.data_ptr(), dcos.data_ptr(), dtype_id(T), torch.cuda.current_stream().cuda_stream)
         if K > 1:
             dcos = ops.subcenter_scatter(dcos, arg, K, ld_sub=_cpad(C * K, T))
-        demb, dw = _cosine_bwd(dcos, emb, w, saved, T)
-        return demb, dw, None, None, None, None, None, None, None, None
+        demb, dw = _cosine_bwd(dcos, emb, w, saved, T, ctx.pfc, ctx.param)
+        return demb, dw, None, None, None, None, None, None, None, None, None
 
 
 class FocalCEFunction(torch.autograd.Function):

@@ -12,22 +12,46 @@ Beyond the reference as well: `AdaFaceProduct` (Kim et al., CVPR 2022: the margi
 `CurricularFaceProduct` (Huang et al., CVPR 2020: hard negatives are re-weighted by a factor that grows with training), both with
 persistent one-element statistics buffers.
 
+Beyond the reference too: `sample_rate < 1` (Partial FC, An et al., CVPR 2022): a training-mode forward scores the batch's own classes plus
+random negatives, `int(sample_rate * out_features)` centres in all (`_MarginHead.sample`); `sparse_grad=True` leaves the gradient of those
+rows on `weight.row_grad` for `optim.FusedSGD` instead of a dense `weight.grad`.  The defaults (1.0, False) are the head as it was.
+
 CUDA inputs run on the gfx950 kernels (losses/_head_hip.py); CPU inputs run the same arithmetic with torch ops."""
 import math
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 
+class PartialFC(namedtuple("PartialFC", "index local_label sparse cache")):
+    """One forward's Partial FC draw as the head functions take it: the sampled classes (int32 [S], ascending), the labels' positions
+    among them (int64 [B]), whether the weight gradient stays row-sparse (`weight.row_grad`, CUDA only) and the head's dictionary
+    holding the dense gradient buffer of the CUDA path between steps."""
+    __slots__ = ()
+
+
 class _MarginHead(nn.Module):
     _mode = None
 
-    def __init__(self, in_features, out_features, s, m, sub_centers=1):
+    def __init__(self, in_features, out_features, s, m, sub_centers=1, sample_rate=1.0, sparse_grad=False):
         super().__init__()
         sub_centers = int(sub_centers)
         if not 1 <= sub_centers <= 16:
             raise ValueError(f"sub_centers must be in 1..16, got {sub_centers}")
+        sample_rate = float(sample_rate)
+        if not 0.0 < sample_rate <= 1.0:
+            raise ValueError(f"sample_rate must be in (0, 1], got {sample_rate}")
+        if sample_rate < 1.0 and int(sample_rate * out_features) < 1:
+            raise ValueError(f"sample_rate={sample_rate} of {out_features} classes samples no class at all")
+        if sample_rate < 1.0 and sub_centers > 1:
+            raise ValueError("sample_rate < 1 (Partial FC) is not combined with sub_centers > 1")
+        self.sample_rate, self.sparse_grad = sample_rate, bool(sparse_grad)
+        self.num_sample = int(sample_rate * out_features) if sample_rate < 1.0 else out_features
+        self.sample_generator = None   # torch.Generator of the negatives' draw (None: the device's default generator)
+        self.last_index = None         # the classes of the last sampled forward (int32, ascending)
+        self._pfc_cache = {}           # dense-gradient buffer of the CUDA path and the index that last wrote it
         self.in_features, self.out_features = in_features, out_features
         self.sub_centers = sub_centers
         self.s, self.m = s, m
@@ -84,6 +108,50 @@ class _MarginHead(nn.Module):
     def hip_mode(self):
         return self._mode
 
+    def sampling(self, label):
+        """whether a forward with `label` scores a sampled subset of the classes: training mode, labels given, fewer samples than classes"""
+        return self.training and label is not None and self.num_sample < self.out_features
+
+    def sample(self, label, score=None):
+        """Partial FC's draw -> (index int32 [S] ascending, local_label int64 [B]) with S = int(sample_rate * out_features):
+        key[c] = 2.0 if class c occurs in `label`, else score[c] (`score`: fp32 [out_features] in [0, 1); None draws it with
+        torch.rand and `sample_generator`); index = the S classes with the largest key, ties towards the lower class id;
+        local_label[b] = position of label[b] in index.  A batch larger than S is refused, so every positive is in index and S is a
+        host constant (nothing is read back from the device).  Also kept in `last_index`."""
+        C, S = self.out_features, self.num_sample
+        label = label.reshape(-1).long()
+        if label.numel() > S:
+            raise ValueError(f"Partial FC: a batch of {label.numel()} does not fit into the {S} sampled classes "
+                             f"(sample_rate={self.sample_rate}, {C} classes)")
+        if score is None:
+            score = torch.rand(C, device=label.device, generator=self.sample_generator)
+        if score.shape != (C,) or score.device != label.device:
+            raise ValueError(f"Partial FC: score must be [{C}] on {label.device}, got {tuple(score.shape)} on {score.device}")
+        score = score.float().contiguous()
+        if label.is_cuda:
+            from .._hip import ops
+            index, local = ops.pfc_sample(label.contiguous(), score, S)
+        else:
+            key = score.clone()
+            key[label] = 2.0
+            index = torch.sort(key, descending=True, stable=True).indices[:S].sort().values
+            local = torch.searchsorted(index, label)
+            index = index.to(torch.int32)
+        self.last_index = index
+        return index, local
+
+    def _partial(self, label):
+        """the losses._head_hip.PartialFC description of this forward (a fresh draw), or None when every class is scored"""
+        if not self.sampling(label):
+            return None
+        index, local = self.sample(label)
+        if self.sparse_grad and label.is_cuda and torch.distributed.is_available() and torch.distributed.is_initialized() \
+                and torch.distributed.get_world_size() > 1:
+            from .._hip import PfrError
+            raise PfrError("Partial FC with sparse_grad=True keeps the sampled rows' gradient out of weight.grad, which the "
+                           "data-parallel reducers never see: use sparse_grad=False in a distributed run")
+        return PartialFC(index, local, self.sparse_grad and label.is_cuda, self._pfc_cache)
+
     def hip_adaptive(self):
         """the losses._head_hip.AdaptiveMargin description of a head whose margin depends on the batch, None for a fixed margin"""
         return None
@@ -91,21 +159,33 @@ class _MarginHead(nn.Module):
     def _target_logit(self, cosine):  # torch (CPU) formulation of the margin on every entry
         raise NotImplementedError
 
-    def forward(self, input, label):
+    def forward(self, input, label, partial=None):
+        """logits [B, out_features]; a sampled forward (`sampling(label)`) returns [B, num_sample] over the classes `last_index`, whose
+        targets are `partial.local_label` (`partial`: this forward's draw when the caller made it, else it is drawn here)"""
+        if partial is None:
+            partial = self._partial(label)
         if input.is_cuda:
             from ._head_hip import MarginFunction, resolve_dtype
+            if partial is not None:
+                return MarginFunction.apply(input, self.weight, label, self.hip_mode(), self.s, self.m,
+                                            resolve_dtype(self.compute_dtype), 1, None, None, partial)
             if self.sub_centers == 1:
                 return MarginFunction.apply(input, self.weight, label, self.hip_mode(), self.s, self.m,
                                             resolve_dtype(self.compute_dtype))
             return MarginFunction.apply(input, self.weight, label, self.hip_mode(), self.s, self.m,
                                         resolve_dtype(self.compute_dtype), self.sub_centers, self._count())
-        cosine = self._cpu_cosine(input, label)
+        if partial is not None:
+            label = partial.local_label
+        cosine = self._cpu_cosine(input, label, partial)
         target = self._target_logit(cosine)
-        hot = F.one_hot(label.view(-1).long(), self.out_features).to(cosine.dtype)
+        hot = F.one_hot(label.view(-1).long(), cosine.shape[1]).to(cosine.dtype)
         return self.s * (hot * target + (1.0 - hot) * cosine)
 
-    def _cpu_cosine(self, input, label):
-        """class cosines [B, out_features] with torch ops: after sub-centre pooling (and counting) when K > 1"""
+    def _cpu_cosine(self, input, label, partial=None):
+        """class cosines [B, out_features] with torch ops: after sub-centre pooling (and counting) when K > 1; the cosines to the
+        sampled centres [B, num_sample] under Partial FC (index_select's autograd leaves the unsampled rows' gradient exactly 0)"""
+        if partial is not None:
+            return F.normalize(input) @ F.normalize(self.weight.index_select(0, partial.index.long())).t()
         cosine = F.normalize(input) @ F.normalize(self.weight).t()
         if self.sub_centers > 1:
             K = self.sub_centers
@@ -122,8 +202,9 @@ class AddMarginProduct(_MarginHead):
     """CosFace: s·(cos θ − m) on the target class."""
     _mode = "cos"
 
-    def __init__(self, in_features, out_features, s=30.0, m=0.40, device=None, sub_centers=1, **_):
-        super().__init__(in_features, out_features, s, m, sub_centers)
+    def __init__(self, in_features, out_features, s=30.0, m=0.40, device=None, sub_centers=1, sample_rate=1.0, sparse_grad=False,
+                 **_):
+        super().__init__(in_features, out_features, s, m, sub_centers, sample_rate, sparse_grad)
         self.device = device
 
     def _target_logit(self, cosine):
@@ -133,8 +214,9 @@ class AddMarginProduct(_MarginHead):
 class ArcMarginProduct(_MarginHead):
     """ArcFace: s·cos(θ + m) on the target class, with the hard (default) or easy fallback outside [0, π−m]."""
 
-    def __init__(self, in_features, out_features, s=30.0, m=0.50, easy_margin=False, sub_centers=1, **_):
-        super().__init__(in_features, out_features, s, m, sub_centers)
+    def __init__(self, in_features, out_features, s=30.0, m=0.50, easy_margin=False, sub_centers=1, sample_rate=1.0,
+                 sparse_grad=False, **_):
+        super().__init__(in_features, out_features, s, m, sub_centers, sample_rate, sparse_grad)
         self.easy_margin = easy_margin
         self.cos_m, self.sin_m = math.cos(m), math.sin(m)
         self.th = math.cos(math.pi - m)
@@ -156,12 +238,19 @@ class _AdaptiveMarginHead(_MarginHead):
     step's margins and moves the buffers on the device (csrc/pfr_head.hip: margin_prepare_kernel), the row kernel is the adaptive
     instantiation.  CPU inputs: `_adaptive_logits`, the same arithmetic in torch ops."""
 
-    def forward(self, input, label):
+    def forward(self, input, label, partial=None):
+        if partial is None:
+            partial = self._partial(label)
         if input.is_cuda:
             from ._head_hip import MarginFunction, resolve_dtype
+            if partial is not None:
+                return MarginFunction.apply(input, self.weight, label, self.hip_mode(), self.s, self.m, resolve_dtype(self.compute_dtype),
+                                            1, None, self.hip_adaptive(), partial)
             return MarginFunction.apply(input, self.weight, label, self.hip_mode(), self.s, self.m, resolve_dtype(self.compute_dtype),
                                         self.sub_centers, self._count(), self.hip_adaptive())
-        return self._adaptive_logits(input, self._cpu_cosine(input, label), label.view(-1).long())
+        if partial is not None:
+            label = partial.local_label
+        return self._adaptive_logits(input, self._cpu_cosine(input, label, partial), label.view(-1).long())
 
     def _adaptive_logits(self, input, cosine, label):
         raise NotImplementedError
@@ -178,8 +267,9 @@ class AdaFaceProduct(_AdaptiveMarginHead):
     statistics of the backbones are here: every rank averages the norms of its own share of the batches."""
     _mode = "adaface"
 
-    def __init__(self, in_features, out_features, s=64.0, m=0.4, h=0.333, t_alpha=0.01, sub_centers=1, eps=1e-3, **_):
-        super().__init__(in_features, out_features, s, m, sub_centers)
+    def __init__(self, in_features, out_features, s=64.0, m=0.4, h=0.333, t_alpha=0.01, sub_centers=1, eps=1e-3, sample_rate=1.0,
+                 sparse_grad=False, **_):
+        super().__init__(in_features, out_features, s, m, sub_centers, sample_rate, sparse_grad)
         self.h, self.t_alpha, self.eps = h, t_alpha, eps
         self.register_buffer("batch_mean", torch.full((1,), 20.0))
         self.register_buffer("batch_std", torch.full((1,), 100.0))
@@ -201,7 +291,7 @@ class AdaFaceProduct(_AdaptiveMarginHead):
             g_ang, g_add = -m * k, m + m * k
         theta = torch.acos(c.gather(1, label[:, None]).squeeze(1))
         phi = torch.cos((theta + g_ang).clip(eps, math.pi - eps)) - g_add
-        hot = F.one_hot(label, self.out_features).bool()
+        hot = F.one_hot(label, c.shape[1]).bool()
         return self.s * torch.where(hot, phi[:, None], c)
 
 
@@ -214,8 +304,9 @@ class CurricularFaceProduct(_AdaptiveMarginHead):
     as the BatchNorm running statistics of the backbones are here."""
     _mode = "curricular"
 
-    def __init__(self, in_features, out_features, s=64.0, m=0.5, momentum=0.01, sub_centers=1, **_):
-        super().__init__(in_features, out_features, s, m, sub_centers)
+    def __init__(self, in_features, out_features, s=64.0, m=0.5, momentum=0.01, sub_centers=1, sample_rate=1.0, sparse_grad=False,
+                 **_):
+        super().__init__(in_features, out_features, s, m, sub_centers, sample_rate, sparse_grad)
         self.momentum = momentum
         self.cos_m, self.sin_m = math.cos(m), math.sin(m)
         self.th = math.cos(math.pi - m)
@@ -237,5 +328,5 @@ class CurricularFaceProduct(_AdaptiveMarginHead):
             hard = c > phi[:, None]
         target = torch.where(ct > self.th, phi, ct - self.mm)
         neg = torch.where(hard, c * (t + c), c)
-        hot = F.one_hot(label, self.out_features).bool()
+        hot = F.one_hot(label, c.shape[1]).bool()
         return self.s * torch.where(hot, target[:, None], neg)

@@ -13,7 +13,13 @@ Weight averaging (`attach_average('ema', decay)` / `attach_average('swa')`, torc
 average is one more flat state buffer per run (`state[p]['avg']`).  An EMA is updated by the step kernel itself, which has the new
 parameter in registers (pfr_*_step_avg: one more read and write of the average, no launch); SWA's running mean is updated by
 `update_average()` (pfr_weight_avg per run).  `swap_averaged()` exchanges master and average; the engines re-derive everything
-they compute with (compute-dtype shadow, weight layouts, folded inference weights) from the master at the next forward pass."""
+they compute with (compute-dtype shadow, weight layouts, folded inference weights) from the master at the next forward pass.
+
+Row gradients (Partial FC with `sparse_grad=True`, losses/_head_hip.py): the head weight's `grad` stays None and backward leaves
+`weight.row_grad = (index int32 [S], rows fp32 [S, D])`.  `FusedSGD.step()` updates exactly those rows with one launch
+(pfr_sgd_step_rows) against a zero-initialised dense momentum state, `state[p]['momentum_buffer']`: unsampled rows and their momentum
+are untouched (lazy momentum).  The clipping calls see `rows` as that parameter's gradient, `zero_grad()` clears `row_grad`.
+FusedAdamW and an attached average refuse such a parameter."""
 import contextlib
 
 import torch
@@ -118,7 +124,33 @@ class _FusedBase(torch.optim.Optimizer):
         return sd
 
     def _grads(self):
-        return [p.grad for group in self.param_groups for p in group["params"] if p.grad is not None]
+        """every gradient of every group in parameter order; a parameter with a row gradient contributes its rows"""
+        grads = []
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is not None:
+                    grads.append(p.grad)
+                elif _row_grad(p) is not None:
+                    grads.append(_row_grad(p)[1])
+        return grads
+
+    def zero_grad(self, set_to_none=True):
+        super().zero_grad(set_to_none=set_to_none)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if _row_grad(p) is not None:
+                    p.row_grad = None
+
+    def _row_params(self, group):
+        """the group's parameters that carry a row gradient (and no dense one), refused where the rows cannot be honoured"""
+        rows = [p for p in group["params"] if p.grad is None and _row_grad(p) is not None]
+        if rows and not isinstance(self, FusedSGD):
+            raise PfrError(f"{type(self).__name__} has no row-wise update for a Partial FC head with sparse_grad=True: "
+                           "use FusedSGD, or build the head with sparse_grad=False")
+        if rows and self._avg is not None:
+            raise PfrError("an attached EMA / SWA average does not follow a Partial FC head with sparse_grad=True (its rows are "
+                           "updated outside the flat buffers): build the head with sparse_grad=False")
+        return rows
 
     @torch.no_grad()
     def clip_grad_norm_(self, max_norm, norm_type=2.0):
@@ -265,6 +297,11 @@ class _FusedBase(torch.optim.Optimizer):
                 return None
             expect *= sizes[i]
         return (t.data_ptr(), n)
+
+
+def _row_grad(p):
+    """(index, rows) left on a parameter by a Partial FC backward with sparse_grad=True, else None"""
+    return getattr(p, "row_grad", None)
 
 
 def _check_average(kind, decay):
@@ -429,6 +466,20 @@ class FusedSGD(_FusedBase):
                                       clip_value, first_step=False)
                 else:
                     ops.sgd_step(r["pf"], r["gf"], buf, None, group["lr"], group["momentum"], group["weight_decay"], first_step=False)
+            for p in self._row_params(group):
+                index, rows = _row_grad(p)
+                if not p.is_cuda or p.dtype != torch.float32 or p.dim() != 2 or not p.is_contiguous():
+                    raise PfrError("a row gradient needs a contiguous fp32 [C, D] CUDA parameter")
+                st = self.state[p]
+                buf = st.get("momentum_buffer")
+                if group["momentum"] != 0 and (buf is None or buf.shape != p.shape or buf.device != p.device or not buf.is_contiguous()):
+                    # lazy momentum: a dense zero-initialised state of its own (a loaded or earlier buffer is carried over)
+                    new = torch.zeros_like(p.data)
+                    if buf is not None and buf.shape == p.shape:
+                        new.copy_(buf)
+                    buf = st["momentum_buffer"] = new
+                ops.sgd_step_rows(p.data, index, rows, buf if group["momentum"] != 0 else None, group["lr"], group["momentum"],
+                                  group["weight_decay"], coef, clip_value)
         if ema:
             self.n_averaged += 1
         return loss
@@ -462,6 +513,7 @@ class FusedAdamW(_FusedBase):
         ema = self._ema()
         avg_w = self._avg_weight() if ema else 0.0
         for gi, group in enumerate(self.param_groups):
+            self._row_params(group)
             for r in self._group_runs(gi, group):
                 if ema:
                     ops.adamw_step_avg(r["pf"], r["gf"], r["state"]["exp_avg"], r["state"]["exp_avg_sq"], None, group["lr"],
