@@ -2,8 +2,8 @@
 
 Same design as models/_mobilenet_engine.MobileNetV2Engine: flat fp32 master / gradient buffers (the module's nn.Parameters become
 views, torchvision's state-dict names unchanged), compute-dtype shadow, activations NHWC end to end, one pre-built plan of C-ABI calls
-per (N, H, W, train, with_backward); the plan runtime is models/_plan_engine.PlanEngine.  The BatchNorm buffers live in one flat
-`stats` tensor.
+per (N, H, W, train, with_backward); the plan runtime and the PlanBuilder that build_plan emits through are models/_plan_engine.py,
+the BatchNorm emitters models/_plan_layers.BatchNormLayers.  The BatchNorm buffers live in one flat `stats` tensor.
 
 Mapping (models/efficientnet.py):
   stem 3x3 stride 2, expand / project / last 1x1 → pfr_conv2d_fwd with the BatchNorm partials in its epilogue (stats_part), pfr_conv2d_wgrad
@@ -21,14 +21,13 @@ Mapping (models/efficientnet.py):
                                                     recomputed from the convolution output (linear BN: the _clamp forms, mask_mode 0)
   avgpool → Linear                                → pfr_avgpool_fwd, pfr_conv2d_fwd
 """
-import struct
-
 import torch
 import torch.nn as nn
 
 from .._hip import lib, dtype_id, PfrError
-from .._hip.cplan import SIDE, FORK, SREC, WAIT, MWAIT
-from ._plan_engine import PlanEngine, Plan, engine_forward, flat_offsets
+from .._hip.cplan import SIDE
+from ._plan_engine import PlanEngine, PlanBuilder, Plan, engine_forward
+from ._plan_layers import BatchNormLayers
 
 
 class _Rec:
@@ -40,7 +39,6 @@ class EfficientNetEngine(PlanEngine):
 
     def __init__(self, model, device, compute_dtype=None):
         super().__init__(model, device, compute_dtype)
-        self.pool_depth = 48   # see SwinEngine: backward buffers per class before one a side-stream op still reads is re-used
         # True: the expand BatchNorm + SiLU as the prologue of pfr_dwconvk_fwd / pfr_dwconvk_wgrad (the activated expand tensor is never
         # stored).  False: a materialising pfr_bn_act_silu before each depthwise conv.  The A/B of tools/efficientnet_bench.py went to
         # the materialised form (profiles/efficientnet_b2.txt, bs 256: 43.70 against 51.10 ms/step; the prologue pays one exponential per TAP, 9 or 25 per element, and
@@ -52,7 +50,7 @@ class EfficientNetEngine(PlanEngine):
     # ------------------------------------------------------------------------------------------ parameters
     def _adopt(self, model):
         from .efficientnet import MBConv, SqueezeExcitation
-        dev = self.device
+        dev, what = self.device, "EfficientNet"
         # the reference's head, a bare Linear (keys classifier.weight / classifier.bias), or torchvision's Sequential(Dropout, Linear)
         if isinstance(model.classifier, nn.Linear):
             lins, self._dropouts = [("classifier", model.classifier)], []
@@ -65,93 +63,19 @@ class EfficientNetEngine(PlanEngine):
         named = list(model.named_parameters())
         if not all(p.requires_grad for _, p in named):
             raise PfrError("HIP EfficientNet path trains every parameter (no frozen layers)")
-        offs, total = flat_offsets(named)
-        self.n_flat = total
-        self.master = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.shadow = self.master if self.dtype == torch.float32 else torch.zeros(total, dtype=self.dtype, device=dev)
-        self.offs = offs
-        self._views = {}
-        self.param_list = []
-        for name, p in named:
-            o, n = offs[name], p.numel()
-            mv = self.master[o:o + n].view(p.shape)
-            mv.copy_(p.data.detach().to(dev))
-            p.data = mv
-            p.grad = None
-            self._views[name] = (p, self.grad[o:o + n].view(p.shape))
-            self.param_list.append(p)
-        self.first_param = named[0][1]
-
-        # BatchNorm buffers → flat (running means, then running variances), as FEEngine
-        bns = [(n, m) for n, m in model.named_modules() if isinstance(m, nn.BatchNorm2d)]
-        nstat = sum(m.num_features for _, m in bns)
-        self.stats = torch.zeros(2 * nstat, dtype=torch.float32, device=dev)
-        self.nbt = torch.zeros(len(bns), dtype=torch.int64, device=dev)
-        bn_of = {}
-        so = 0
-        for i, (n, m) in enumerate(bns):
-            if m.momentum is None or not m.affine or not m.track_running_stats:
-                raise PfrError(f"{n}: the HIP EfficientNet path needs an affine BatchNorm2d with running statistics and a momentum")
-            C = m.num_features
-            b = _Rec()
-            b.C, b.eps, b.momentum = C, float(m.eps), float(m.momentum)
-            b.rm, b.rv = self.stats[so:so + C], self.stats[nstat + so:nstat + so + C]
-            b.rm.copy_(m.running_mean.detach().to(dev))
-            b.rv.copy_(m.running_var.detach().to(dev))
-            self.nbt[i] = int(m.num_batches_tracked.item())
-            m.running_mean, m.running_var, m.num_batches_tracked = b.rm, b.rv, self.nbt[i]
-            so += C
-            ow, ob = offs[n + ".weight"], offs[n + ".bias"]
-            b.gamma, b.dgamma = self.master[ow:ow + C], self.grad[ow:ow + C]
-            b.beta, b.dbeta = self.master[ob:ob + C], self.grad[ob:ob + C]
-            bn_of[id(m)] = b
-        maxc = max(m.num_features for _, m in bns)
-        self.bn_ws = torch.empty(max(1, lib.pfr_bn_finalize_ws_floats(1 << 20, maxc)), dtype=torch.float32, device=dev)
-
-        def chunked(name, c):
-            if c % self.kp:
-                raise PfrError(f"HIP EfficientNet path: {name} has {c} channels, not a multiple of {self.kp} in {self.dtype}")
+        offs = self._adopt_flat(named)
+        bn_of = self._adopt_batchnorms(model, what)     # BatchNorm buffers → flat
+        plain, chunked = self._plain, self._chunked
 
         def pw(prefix, m, bias=False):
-            """1x1 convolution / Linear: the [O][I](x1x1) parameter is the kernel's [O][1][1][I] layout as it stands"""
-            r = _Rec()
-            r.out, r.inp = m.weight.shape[0], m.weight.shape[1]
-            chunked(prefix, r.inp)
-            chunked(prefix, r.out)
-            r.off = offs[prefix + ".weight"]
-            n = r.out * r.inp
-            r.w, r.g = self.shadow[r.off:r.off + n], self.grad[r.off:r.off + n]
-            r.wt = torch.zeros(n, dtype=self.dtype, device=dev)     # [I][1][1][O]
-            if bias:
-                bo = offs[prefix + ".bias"]
-                r.bias, r.dbias = self.master[bo:bo + r.out], self.grad[bo:bo + r.out]
-            return r
-
-        def plain(m, k, stride, groups):
-            return (m.kernel_size == (k, k) and m.stride == (stride, stride) and m.padding == ((k - 1) // 2,) * 2 and m.groups == groups
-                    and m.dilation == (1, 1) and m.bias is None)
+            return self._pw(what, prefix, m, bias)
 
         def vec(name, n):
             o = offs[name]
             return self.master[o:o + n], self.grad[o:o + n]
 
         feats = model.features
-        # stem: [O][3][3][3] parameter ↔ [O][9][I padded] conv layout
-        sc = feats[0][0]
-        if not plain(sc, 3, 2, 1):
-            raise PfrError("HIP EfficientNet path: the stem is a bias-free 3x3 stride-2 convolution")
-        st = _Rec()
-        st.out, st.cin = sc.out_channels, sc.in_channels
-        chunked("features.0.0", st.out)
-        st.cinp = (st.cin + self.kp - 1) // self.kp * self.kp
-        st.off = offs["features.0.0.weight"]
-        st.g = self.grad[st.off:st.off + st.out * st.cin * 9]
-        st.w = torch.zeros(st.out * 9 * st.cinp, dtype=self.dtype, device=dev)
-        st.g_conv = torch.zeros(st.out * 9 * st.cinp, dtype=torch.float32, device=dev)
-        st.bn = bn_of[id(feats[0][1])]
-        self.stem = st
-        self.in_channels, self.cp = st.cin, st.cinp
+        self._adopt_stem(what, feats[0][0], bn_of[id(feats[0][1])])
         self.blocks = []
         for fi in range(1, len(feats) - 1):
             if not isinstance(feats[fi], nn.Sequential) or not all(isinstance(m, MBConv) for m in feats[fi]):
@@ -176,7 +100,7 @@ class EfficientNetEngine(PlanEngine):
                 b.C = dwc.out_channels
                 if b.K not in (3, 5) or not plain(dwc, b.K, b.stride, b.C) or dwc.in_channels != b.C:
                     raise PfrError(f"{pre}: the depthwise convolution is 3x3 or 5x5, padding k // 2, stride 1 or 2, bias-free")
-                chunked(f"{pre}.{j}.0", b.C)
+                chunked(what, f"{pre}.{j}.0", b.C)
                 KK = b.K * b.K
                 b.dw_off = offs[f"{pre}.{j}.0.weight"]
                 b.dw_g = self.grad[b.dw_off:b.dw_off + KK * b.C]
@@ -246,49 +170,10 @@ class EfficientNetEngine(PlanEngine):
     def build_plan(self, N, H, W, train, with_backward):
         T, dev, did = self.dtype, self.device, self.did
         plan = Plan()
-        fwd, bwd = [], []
-
-        def A(shape, dtype=None):
-            return plan.keep(torch.empty(shape, dtype=dtype or T, device=dev))
-
-        def coef(bn):
-            """this plan's (mean, invstd, scale, shift) and backward coefficients of a BatchNorm"""
-            c = _Rec()
-            c.bn = bn
-            c.f = plan.keep(torch.zeros((4, bn.C), dtype=torch.float32, device=dev))
-            c.b = plan.keep(torch.zeros((3, bn.C), dtype=torch.float32, device=dev))
-            c.scale, c.shift = c.f[2], c.f[3]
-            return c
-
-        def bn_fwd(c, part, nparts, rpp, count):
-            bn = c.bn
-            if train:
-                nws = lib.pfr_bn_finalize_ws_floats(nparts, bn.C)
-                assert nws <= self.bn_ws.numel()
-                fwd.append((lib.pfr_bn_finalize, (part.data_ptr(), nparts, rpp, bn.C, float(count), bn.gamma.data_ptr(), bn.beta.data_ptr(),
-                                                  bn.eps, bn.momentum, bn.rm.data_ptr(), bn.rv.data_ptr(), c.f[0].data_ptr(),
-                                                  c.f[1].data_ptr(), c.f[2].data_ptr(), c.f[3].data_ptr(),
-                                                  self.bn_ws.data_ptr() if nws else 0)))
-            else:
-                fwd.append((lib.pfr_bn_eval_coeff, (bn.C, bn.gamma.data_ptr(), bn.beta.data_ptr(), bn.rm.data_ptr(), bn.rv.data_ptr(),
-                                                    bn.eps, c.f[2].data_ptr(), c.f[3].data_ptr())))
-
-        def conv_bn(x, xshape, w, cout, R, stride, pad, bn):
-            """dense convolution + the BatchNorm coefficients of its output → (raw output, its shape, coefficients)"""
-            Nq, Hq, Wq, Cq = xshape
-            OH, OW = (Hq + 2 * pad - R) // stride + 1, (Wq + 2 * pad - R) // stride + 1
-            M = Nq * OH * OW
-            z = A((Nq, OH, OW, cout))
-            part, nt, mt = None, 0, 0
-            if train:
-                mt = lib.pfr_conv2d_mtile(Nq, Hq, Wq, Cq, cout, R, R, stride, pad, OH, OW, did, did, 0)
-                nt = (M + mt - 1) // mt
-                part = A((nt, 2, cout), torch.float32)
-            fwd.append((lib.pfr_conv2d_fwd, (x.data_ptr(), w.data_ptr(), z.data_ptr(), did, did, Nq, Hq, Wq, Cq, cout, R, R, stride, pad, 0,
-                                             OH, OW, cout, 0, 0, 0, 0, 0, 0, 0, part.data_ptr() if train else 0)))
-            c = coef(bn)
-            bn_fwd(c, part, nt, mt, M)
-            return z, (Nq, OH, OW, cout), c
+        pb = PlanBuilder(plan, T, dev, did, self.pool_depth)
+        A, fwd, bwd = pb.A, pb.fwd, pb.bwd
+        bn = BatchNormLayers(pb, train, self.bn_ws)
+        coef, bn_fwd, conv_bn = bn.coef, bn.bn_fwd, bn.conv_bn
 
         def act(z, shape, c):
             """materialised silu(bn(z))"""
@@ -373,87 +258,10 @@ class EfficientNetEngine(PlanEngine):
         if not with_backward:
             return plan
 
-        # ================================================================= backward
-        # Weight gradients (dense and depthwise) and the bias column sum feed nothing before the optimizer: they run on the SIDE stream
-        # with the FORK / SREC / WAIT roles of _hip/cplan.py, exactly as in ConvNeXtEngine.build_plan (see the comments there).
-        pool = {}
-        nalloc = {}
-        pending = {}      # data_ptr of a pooled buffer -> last side op that reads it
-        side_reads = []   # (k, data_ptr) of every side-op input
-        nside = [0]
-        ws_need = [0]
-
-        def G(shape, dtype=None):
-            key = (tuple(shape), dtype or T)
-            lst = pool.setdefault(key, [])
-            for i, t in enumerate(lst):
-                if t.data_ptr() not in pending:
-                    return lst.pop(i)
-            if not lst or nalloc.get(key, 0) < self.pool_depth:
-                nalloc[key] = nalloc.get(key, 0) + 1
-                return A(shape, dtype)
-            t = lst.pop(0)
-            bwd.append((WAIT, pending.pop(t.data_ptr())))
-            return t
-
-        def release(t):
-            lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
-            ks = [k for k, ptr in side_reads if lo <= ptr < hi]
-            if ks:
-                pending[t.data_ptr()] = max(ks)
-            side_reads[:] = [(k, ptr) for k, ptr in side_reads if not (lo <= ptr < hi)]
-            pool.setdefault((tuple(t.shape), t.dtype), []).append(t)
-
-        def side(op, *reads):
-            if bwd and bwd[-1][0] == SREC:
-                k = bwd.pop()[1]
-            else:
-                k = nside[0]
-                nside[0] += 1
-                bwd.append((FORK, k))
-            bwd.append(op)
-            bwd.append((SREC, k))
-            for r in reads:
-                side_reads.append((k, r.data_ptr()))
-
-        def wgrad(x, xshape, dy, dyshape, R, stride, pad, out):
-            Nq, Hq, Wq, Cq = xshape
-            _, OH, OW, Co = dyshape
-            KK = R * R * Cq
-            splits = lib.pfr_conv2d_wgrad_splits(Nq * OH * OW, Co, KK)
-            ws_need[0] = max(ws_need[0], splits * Co * KK)
-            side(("wgrad", (x.data_ptr(), dy.data_ptr(), out.data_ptr(), None, did, Nq, Hq, Wq, Cq, Co, R, R, stride, pad, OH, OW, Co,
-                            0, 0, 0, 1.0, 0)), dy)
-
-        def dgrad_pw(dy, rows, r, dx, residual=None):
-            bwd.append((lib.pfr_conv2d_fwd, (dy.data_ptr(), r.wt.data_ptr(), dx.data_ptr(), did, did, rows, 1, 1, r.out, r.inp, 1, 1, 1, 0, 0,
-                                             1, 1, r.inp, 0, 0 if residual is None else residual.data_ptr(), 0, 0, 0, 0, 0, 0)))
-
-        def bn_bwd(dout, z, c, rows, silu):
-            """dz of z from the gradient of silu?(bn(z)), in place of a fresh buffer; dgamma / dbeta into the flat gradient"""
-            bn = c.bn
-            nb = lib.pfr_colreduce_blocks(bn.C, did, rows)
-            part = A((nb, 2, bn.C), torch.float32)
-            if silu:
-                bwd.append((lib.pfr_bn_bwd_reduce_silu, (dout.data_ptr(), z.data_ptr(), c.f[0].data_ptr(), c.f[1].data_ptr(),
-                                                         c.scale.data_ptr(), c.shift.data_ptr(), did, rows, bn.C, part.data_ptr())))
-            else:
-                bwd.append((lib.pfr_bn_bwd_reduce_clamp, (dout.data_ptr(), z.data_ptr(), c.f[0].data_ptr(), c.f[1].data_ptr(),
-                                                          c.scale.data_ptr(), c.shift.data_ptr(), 0.0, 0, did, rows, bn.C, part.data_ptr())))
-            bwd.append((lib.pfr_bn_bwd_finalize, (part.data_ptr(), nb, bn.C, float(rows), bn.gamma.data_ptr(), c.f[0].data_ptr(),
-                                                  c.f[1].data_ptr(), bn.dgamma.data_ptr(), bn.dbeta.data_ptr(), c.b.data_ptr(), 0)))
-            dz = G(tuple(z.shape))
-            if silu:
-                bwd.append((lib.pfr_bn_bwd_apply_silu, (dout.data_ptr(), z.data_ptr(), c.b.data_ptr(), c.scale.data_ptr(), c.shift.data_ptr(),
-                                                        dz.data_ptr(), did, rows, bn.C)))
-            else:
-                bwd.append((lib.pfr_bn_bwd_apply_clamp, (dout.data_ptr(), z.data_ptr(), c.b.data_ptr(), c.scale.data_ptr(), c.shift.data_ptr(),
-                                                         0.0, 0, dz.data_ptr(), did, rows, bn.C)))
-            return dz
-
-        def stop(final, off):
-            bwd.append((WAIT if final else MWAIT, nside[0] - 1))
-            bwd.append((None, (off,)))
+        # ================================================================= backward (stream roles, buffer pool: PlanBuilder; the
+        # depthwise weight gradients and the bias column sum run on the side stream like the dense weight gradients)
+        G, release, side, wgrad, mark = pb.G, pb.release, pb.side, pb.wgrad, pb.mark
+        dgrad_pw, bn_bwd = bn.dgrad_pw, bn.bn_bwd
 
         demb = A((N, self.emb_dim))
         plan.meta["demb"] = demb
@@ -464,15 +272,15 @@ class EfficientNetEngine(PlanEngine):
         dal = G(lshape)
         bwd.append((lib.pfr_avgpool_bwd, (dpooled.data_ptr(), dal.data_ptr(), did, N, Hh * Ww, Cf)))
         release(dpooled)
-        stop(False, self.head_off)
+        mark(self.head_off)
         rows_l = N * Hh * Ww
-        dzl = bn_bwd(dal, zl, cl, rows_l, True)
+        dzl = bn_bwd(dal, zl, cl, rows_l, "silu")
         release(dal)
         wgrad(last_in, last_inshape, dzl, lshape, 1, 1, 0, self.last.g)
         dout = G(last_inshape)
         dgrad_pw(dzl, rows_l, self.last, dout)
         release(dzl)
-        stop(False, self.last_off)
+        mark(self.last_off)
         for b, sv in zip(reversed(self.blocks), reversed(saved)):
             Nq, OH, OW, Ch = sv.dshape
             rows_o = Nq * OH * OW
@@ -481,7 +289,7 @@ class EfficientNetEngine(PlanEngine):
             if sv.rows_sd:     # the branch gradient of a block under stochastic depth: row_scale[n] * dout
                 dbr = G(sv.pshape)
                 bwd.append((lib.pfr_row_scale, (dout.data_ptr(), sd[b.bid].data_ptr(), dbr.data_ptr(), did, Nq, OH * OW, sv.pshape[3])))
-            dzp = bn_bwd(dbr, sv.zp, sv.cp, rows_o, False)
+            dzp = bn_bwd(dbr, sv.zp, sv.cp, rows_o)
             if sv.rows_sd:
                 release(dbr)
             wgrad(sv.ys, sv.dshape, dzp, sv.pshape, 1, 1, 0, b.project.g)
@@ -499,7 +307,7 @@ class EfficientNetEngine(PlanEngine):
             bwd.append((lib.pfr_se_bwd_apply, (dys.data_ptr(), sv.gate.data_ptr(), dpool.data_ptr(), dad.data_ptr(), did, Nq, OH * OW, Ch)))
             release(dys)
             # ---- depthwise BN + SiLU, depthwise conv: weight gradient from the recomputed operand (side), gather data gradient
-            dzd = bn_bwd(dad, sv.zd, sv.cd, rows_o, True)
+            dzd = bn_bwd(dad, sv.zd, sv.cd, rows_o, "silu")
             release(dad)
             Ne, He, We, _ = sv.eshape
             npart = lib.pfr_dwconvk_wgrad_parts(did, Ne, He, We, Ch, b.K, b.stride)
@@ -513,7 +321,7 @@ class EfficientNetEngine(PlanEngine):
             release(dzd)
             rows_e = Ne * He * We
             if b.expand is not None:     # (materialised or fused into the depthwise prologue: the backward is the same BN + SiLU step)
-                dze = bn_bwd(dae, sv.ze, sv.ce, rows_e, True)
+                dze = bn_bwd(dae, sv.ze, sv.ce, rows_e, "silu")
                 release(dae)
                 wgrad(sv.xin, sv.in_shape, dze, sv.eshape, 1, 1, 0, b.expand.g)
                 dxin = G(sv.in_shape)
@@ -528,24 +336,20 @@ class EfficientNetEngine(PlanEngine):
             release(dout)
             dout = dxin
             if sv.in_c is not None:     # the block input was silu(bn(raw)) of the layer before (the stem): its BatchNorm step
-                dz = bn_bwd(dout, sv.in_raw, sv.in_c, rows_e, True)
+                dz = bn_bwd(dout, sv.in_raw, sv.in_c, rows_e, "silu")
                 release(dout)
                 dout = dz
             if b.stride == 2 and b is not self.blocks[0]:
-                stop(False, b.off)
+                mark(b.off)
         if not self.blocks:
-            dz = bn_bwd(dout, z0, c0, shape[0] * shape[1] * shape[2], True)
+            dz = bn_bwd(dout, z0, c0, shape[0] * shape[1] * shape[2], "silu")
             release(dout)
             dout = dz
         # ---- stem (no data gradient)
         wgrad(x_nhwc, (N, H, W, self.cp), dout, (N,) + tuple(z0.shape[1:]), 3, 2, 1, st.g_conv)
         side((SIDE, (lib.pfr_nhwc_to_nchw_f32, (st.g_conv.data_ptr(), st.g.data_ptr(), st.out, st.cin, 9, st.cinp, 0))))
-        stop(True, 0)
-        plan.meta["n_side"] = nside[0]
-        if self.ws is None or self.ws.numel() < ws_need[0]:
-            self.ws = torch.empty(ws_need[0], dtype=torch.float32, device=dev)
-        plan.ops = fwd + bwd
-        return plan
+        mark(0, last=True)
+        return pb.finish(self)
 
     def forward(self, x, sd, train, with_backward, ticket=None):
         if x.dim() != 4 or x.shape[1] != self.in_channels:
@@ -560,33 +364,11 @@ class EfficientNetEngine(PlanEngine):
         N, _, H, W = x.shape
         if tuple(sd.shape) != (self.n_blocks, N):
             raise PfrError(f"stochastic-depth draw of shape {tuple(sd.shape)}, expected {(self.n_blocks, N)}")
-        plan = self.acquire_plan(N, H, W, train, with_backward, ticket=ticket if with_backward else None)
-        if with_backward:
-            self._fresh(plan)
-        stream = torch.cuda.current_stream().cuda_stream
-        self.refresh_weights(stream, for_backward=with_backward)
-        if self.n_blocks:
-            plan.meta["sd"].copy_(sd, non_blocking=True)
-        lib.pfr_nchw_to_nhwc(x.data_ptr(), plan.meta["x_nhwc"].data_ptr(), self.did, N, x.shape[1], H, W, self.cp, stream)
-        self._run_fwd(plan, stream)
+        fill = (lambda plan: plan.meta["sd"].copy_(sd, non_blocking=True)) if self.n_blocks else None
+        emb = self._forward_plan(x, N, H, W, train, with_backward, with_backward=with_backward, ticket=ticket, fill=fill)
         if train:
             self.nbt.add_(1)
-        self._last_plan = plan
-        return plan.meta["emb"]
-
-    def backward(self, demb, plan=None):
-        plan = plan if plan is not None else self._last_plan
-        self._begin_backward(plan, demb)
-        # As in ConvNeXtEngine: the plan's gradient launches overwrite their slices; a second backward before zero_grad sets the
-        # previous sum aside and adds it back (the accumulate forms of pfr_dwconvk_wgrad / pfr_se_gate_bwd / pfr_bn_bwd_finalize serve hosts without it)
-        prev = self.grad.clone() if self.first_param.grad is not None else None
-        hook = self.grad_ready_hook
-        if prev is not None or any(self._plan_busy(q) for q in self.plans.values()):
-            hook = None
-        self._run_bwd(plan, "bwd", hook, hook)
-        if prev is not None:
-            self.grad.add_(prev)
-        self.attach_grads()
+        return emb
 
 
 def efficientnet_forward(model, x, sd):

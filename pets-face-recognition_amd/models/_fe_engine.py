@@ -15,7 +15,7 @@ resnet (/root/reference/losses/__init__.py:38-41 called from engine/controller.p
     tail (BN + projection-BN + residual add + ReLU) is one pass that also writes the ReLU sign as a bit mask, which the two
     backward kernels of the block's last BN and the residual join in conv1's data-gradient epilogue read; inner BNs recompute
     their ReLU mask from scale*x+shift;
-  * the plan runtime is models/_plan_engine.PlanEngine (shared with the Swin engine): a step's launch lists are replayed from
+  * the plan runtime is models/_plan_engine.PlanEngine (shared with the other five engines, which also share its PlanBuilder): a step's launch lists are replayed from
     C (csrc/pfr_plan.hip) unless PFR_C_PLAN=0 or a launch tracer is installed; one plan slot per forward pass in flight allows
     list inputs (two forwards before one backward), each with its own BN coefficients.  This module keeps what is ResNet's:
     parameter adoption, the plan builders, the folded / graphed inference path and the overwrite / accumulate backward pair.

@@ -1,4 +1,5 @@
-"""PlanEngine — the plan runtime shared by models/_fe_engine.FEEngine (ResNet) and models/_swin_engine.SwinEngine.
+"""PlanEngine — the plan runtime and the plan builder shared by the six engines: models/_fe_engine.FEEngine (ResNet), _swin_engine,
+_convnext_engine, _vit_engine, _mobilenet_engine and _efficientnet_engine.
 
 An engine turns a model into pre-built launch lists ("plans": C-ABI calls with fixed device pointers, one plan per input
 shape).  Everything that makes such a list a training step on two streams is model-independent and lives here, once:
@@ -11,9 +12,19 @@ shape).  Everything that makes such a list a training step on two streams is mod
   * replay: through the C executor (_run_list; its events belong to the CPlan) or, under PFR_C_PLAN=0 and always under a
     launch tracer, through run_ops, the one Python interpreter of the roles (its events belong to the engine);
   * the side-stream policy (_side_ok), the side-stream half of refresh_weights and the matching wait in backward;
-  * the autograd wrapper (engine_forward).
+  * the autograd wrapper (engine_forward);
+  * PlanBuilder, the build-time half: the forward and backward lists of one plan, the backward buffer pool, the side-stream
+    fork / join bookkeeping, the split-K workspace sizing, the deferred column sums and the grad-ready marks;
+  * parameter adoption (_adopt_flat; _adopt_batchnorms and the 1x1 / stem records of the BatchNorm networks), the tail of
+    forward() (_forward_plan) and backward().
 
-The engines keep what is theirs: parameter adoption, build_plan and its layer closures, how a second backward accumulates."""
+Who uses what: all six engines use the runtime.  Swin, ConvNeXt, ViT, MobileNetV2 and EfficientNet build their plans with
+PlanBuilder and the layer emitters of models/_plan_layers.py (Linear / LayerNorm family: Swin, ConvNeXt, ViT; BatchNorm family:
+MobileNetV2, EfficientNet), adopt their parameters with _adopt_flat and run _forward_plan and backward() as they stand.  FEEngine
+keeps a builder of its own (a FIFO pool with a measured lag, weight gradients that carry a BatchNorm prologue, a second workspace),
+its own _adopt, forward and backward.
+
+The engines keep what is theirs: the layer records, build_plan's model-specific middle, the argument checks of forward()."""
 import os
 import struct
 import weakref
@@ -106,9 +117,122 @@ def run_ops(ops, main, side, events, hook, hook_syncs_side):
             fn(*args, stream)
 
 
+class _Rec:
+    pass
+
+
+class PlanBuilder:
+    """The build-time state of one plan: the forward and backward lists, and for the backward list the buffer pool, the side
+    stream's fork / join bookkeeping, the split-K workspace need of the weight gradients and the deferred column sums.
+
+    Weight gradients and bias / normalisation-parameter column sums feed nothing before the optimizer: they run on a SIDE stream
+    (≈ 150 short launches per step that would otherwise sit in the dependency chain).  Stream roles (_hip/cplan.py): (FORK, k)
+    side waits for main's current point; (SREC, k) side records "op k done"; (WAIT, k) main waits for op k — emitted before a pooled
+    buffer that op k read is handed out again, before grad-ready marks and at the end.  Only the weight gradients stay symbolic
+    ("wgrad": PlanEngine.resolve fills the split-K workspace pointer in)."""
+
+    def __init__(self, plan, dtype, device, did, pool_depth):
+        self.plan, self.dtype, self.device, self.did, self.pool_depth = plan, dtype, device, did, pool_depth
+        self.fwd, self.bwd = [], []
+        self.pool = {}         # (shape, dtype) class -> released buffers, oldest first
+        self.nalloc = {}       # buffers allocated per class
+        self.pending = {}      # data_ptr of a pooled buffer -> last side op that reads it
+        self.side_reads = []   # (k, data_ptr) of every side-op input
+        self.nside = 0
+        self.ws_need = 0       # floats of split-K workspace the largest weight gradient needs
+        self.pend_cs = []      # column sums whose final merge is deferred to the next flush: (partials, out, partial rows, C, tile height | 0, rows)
+
+    def A(self, shape, dtype=None):
+        return self.plan.keep(torch.empty(shape, dtype=dtype or self.dtype, device=self.device))
+
+    def G(self, shape, dtype=None):
+        key = (tuple(shape), dtype or self.dtype)
+        lst = self.pool.setdefault(key, [])
+        for i, t in enumerate(lst):              # a buffer no side op is reading
+            if t.data_ptr() not in self.pending:
+                return lst.pop(i)
+        if not lst or self.nalloc.get(key, 0) < self.pool_depth:    # rotation so that the side stream may lag behind without stalling main
+            self.nalloc[key] = self.nalloc.get(key, 0) + 1
+            return self.A(shape, dtype)
+        t = lst.pop(0)
+        self.bwd.append((WAIT, self.pending.pop(t.data_ptr())))
+        return t
+
+    def release(self, t):
+        lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+        ks = [k for k, ptr in self.side_reads if lo <= ptr < hi]
+        if ks:
+            self.pending[t.data_ptr()] = max(ks)
+        self.side_reads[:] = [(k, ptr) for k, ptr in self.side_reads if not (lo <= ptr < hi)]
+        self.pool.setdefault((tuple(t.shape), t.dtype), []).append(t)
+
+    def side(self, op, *reads):
+        ops = self.bwd
+        if ops and ops[-1][0] == SREC:
+            # no main-stream launch since the previous side op: it joins that op's fork (every fork is an event recorded on the
+            # main stream, i.e. a marker packet in front of the next kernel of the dependency chain)
+            k = ops.pop()[1]
+        else:
+            k = self.nside
+            self.nside += 1
+            ops.append((FORK, k))
+        ops.append(op)
+        ops.append((SREC, k))
+        for r in reads:
+            self.side_reads.append((k, r.data_ptr()))
+
+    def wgrad(self, x, xshape, dy, dyshape, R, stride, pad, out):
+        Nq, Hq, Wq, Cq = xshape
+        _, OH, OW, Co = dyshape
+        KK = R * R * Cq
+        splits = lib.pfr_conv2d_wgrad_splits(Nq * OH * OW, Co, KK)
+        self.ws_need = max(self.ws_need, splits * Co * KK)
+        self.side(("wgrad", (x.data_ptr(), dy.data_ptr(), out.data_ptr(), None, self.did, Nq, Hq, Wq, Cq, Co, R, R, stride, pad,
+                             OH, OW, Co, 0, 0, 0, 1.0, 0)), dy)
+
+    def colsum(self, x, rows, C, out, dt=None):
+        """bias / LayerNorm-parameter / position-table gradient = column sum of x; the partial sums run now (side stream), the
+        ~100 tiny final merges of a step are batched into one launch per DDP bucket boundary (flush_colsums)"""
+        d = dt if dt is not None else self.did
+        n = lib.pfr_colsum_parts(d, rows, C)
+        if n <= 0:   # a few hundred rows: one small kernel does it all
+            self.side((SIDE, (lib.pfr_colsum, (x.data_ptr(), d, rows, C, out.data_ptr(), 0, 0))), x)
+            return
+        ws = self.A((lib.pfr_colsum_ws_floats(rows, C),), torch.float32)   # its own workspace: alive until the batched final
+        self.side((SIDE, (lib.pfr_colsum_partial, (x.data_ptr(), d, rows, C, ws.data_ptr()))), x)
+        self.pend_cs.append((ws, out, n, C, 0, 0))
+
+    def flush_colsums(self):
+        pend = self.pend_cs
+        if not pend:
+            return
+        raw = b"".join(struct.pack("<QQiiiiii", ws.data_ptr(), out.data_ptr(), n, C, 0, mt, rws, 0) for ws, out, n, C, mt, rws in pend)
+        tab = self.plan.keep(torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device))
+        self.side((SIDE, (lib.pfr_colsum_final_batch, (tab.data_ptr(), len(pend), max(e[3] for e in pend)))))
+        del pend[:]
+
+    def mark(self, off, last=False):
+        """grad-ready mark (DDP bucket boundary; `last`: the end of the backward pass): flat gradients [off, end) are final"""
+        self.flush_colsums()
+        if self.nside:   # everything the side stream was given so far is final
+            self.bwd.append((WAIT if last else MWAIT, self.nside - 1))
+        self.bwd.append((None, (off,)))
+
+    def finish(self, engine):
+        plan = self.plan
+        plan.meta["n_side"] = self.nside
+        if engine.ws is None or engine.ws.numel() < self.ws_need:
+            engine.ws = torch.empty(self.ws_need, dtype=torch.float32, device=self.device)
+        plan.ops = self.fwd + self.bwd
+        return plan
+
+
 class PlanEngine:
     max_plans = 8            # plans kept (all shapes and slots) before the oldest idle one is evicted
     bwd_lists = ("bwd",)     # resolved backward lists, one per value of the accumulate flag (0, 1, ...)
+    # buffers per (shape, dtype) class of the backward pool before one that a side-stream op still reads is re-used (HBM is
+    # plentiful; a shallow pool makes the main stream wait for the side stream at almost every layer)
+    pool_depth = 48
 
     def __init__(self, model, device, compute_dtype=None):
         if not str(device).startswith("cuda"):
@@ -139,6 +263,99 @@ class PlanEngine:
         self.hook_syncs_side = False    # True: the hook makes ITS stream wait for self.side (the main stream then never waits at a mark)
 
     # ------------------------------------------------------------------------------------------ parameters
+    def _adopt_flat(self, named):
+        """the (name, parameter) list `named` into flat fp32 master / gradient buffers (the parameters become views) and their
+        compute-dtype shadow"""
+        dev = self.device
+        offs, total = flat_offsets(named)
+        self.n_flat = total
+        self.master = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.shadow = self.master if self.dtype == torch.float32 else torch.zeros(total, dtype=self.dtype, device=dev)
+        self.offs = offs
+        self._views = {}
+        self.param_list = []
+        for name, p in named:
+            o, n = offs[name], p.numel()
+            mv = self.master[o:o + n].view(p.shape)
+            mv.copy_(p.data.detach().to(dev))
+            p.data = mv
+            p.grad = None
+            self._views[name] = (p, self.grad[o:o + n].view(p.shape))
+            self.param_list.append(p)
+        self.first_param = named[0][1]
+        return offs
+
+    def _adopt_batchnorms(self, model, what):
+        """BatchNorm buffers → flat `stats` (running means, then running variances) and `nbt`, as FEEngine; running_mean /
+        running_var / num_batches_tracked of the modules become views.  → id(module) -> record"""
+        dev, offs = self.device, self.offs
+        bns = [(n, m) for n, m in model.named_modules() if isinstance(m, torch.nn.BatchNorm2d)]
+        nstat = sum(m.num_features for _, m in bns)
+        self.stats = torch.zeros(2 * nstat, dtype=torch.float32, device=dev)
+        self.nbt = torch.zeros(len(bns), dtype=torch.int64, device=dev)
+        bn_of = {}
+        so = 0
+        for i, (n, m) in enumerate(bns):
+            if m.momentum is None or not m.affine or not m.track_running_stats:
+                raise PfrError(f"{n}: the HIP {what} path needs an affine BatchNorm2d with running statistics and a momentum")
+            C = m.num_features
+            b = _Rec()
+            b.C, b.eps, b.momentum = C, float(m.eps), float(m.momentum)
+            b.rm, b.rv = self.stats[so:so + C], self.stats[nstat + so:nstat + so + C]
+            b.rm.copy_(m.running_mean.detach().to(dev))
+            b.rv.copy_(m.running_var.detach().to(dev))
+            self.nbt[i] = int(m.num_batches_tracked.item())
+            m.running_mean, m.running_var, m.num_batches_tracked = b.rm, b.rv, self.nbt[i]
+            so += C
+            ow, ob = offs[n + ".weight"], offs[n + ".bias"]
+            b.gamma, b.dgamma = self.master[ow:ow + C], self.grad[ow:ow + C]
+            b.beta, b.dbeta = self.master[ob:ob + C], self.grad[ob:ob + C]
+            bn_of[id(m)] = b
+        maxc = max(m.num_features for _, m in bns)
+        self.bn_ws = torch.empty(max(1, lib.pfr_bn_finalize_ws_floats(1 << 20, maxc)), dtype=torch.float32, device=dev)
+        return bn_of
+
+    def _chunked(self, what, name, c):
+        if c % self.kp:
+            raise PfrError(f"HIP {what} path: {name} has {c} channels, not a multiple of {self.kp} in {self.dtype}")
+
+    def _pw(self, what, prefix, m, bias=False):
+        """1x1 convolution / Linear: the [O][I](x1x1) parameter is the kernel's [O][1][1][I] layout as it stands"""
+        r = _Rec()
+        r.out, r.inp = m.weight.shape[0], m.weight.shape[1]
+        self._chunked(what, prefix, r.inp)
+        self._chunked(what, prefix, r.out)
+        r.off = self.offs[prefix + ".weight"]
+        n = r.out * r.inp
+        r.w, r.g = self.shadow[r.off:r.off + n], self.grad[r.off:r.off + n]
+        r.wt = torch.zeros(n, dtype=self.dtype, device=self.device)     # [I][1][1][O]
+        if bias:
+            bo = self.offs[prefix + ".bias"]
+            r.bias, r.dbias = self.master[bo:bo + r.out], self.grad[bo:bo + r.out]
+        return r
+
+    @staticmethod
+    def _plain(m, k, stride, groups):
+        return (m.kernel_size == (k, k) and m.stride == (stride, stride) and m.padding == ((k - 1) // 2,) * 2 and m.groups == groups
+                and m.dilation == (1, 1) and m.bias is None)
+
+    def _adopt_stem(self, what, sc, bn):
+        """the 3x3 stride-2 stem `features.0.0` and its BatchNorm record: [O][3][3][3] parameter ↔ [O][9][I padded] conv layout"""
+        if not self._plain(sc, 3, 2, 1):
+            raise PfrError(f"HIP {what} path: the stem is a bias-free 3x3 stride-2 convolution")
+        st = _Rec()
+        st.out, st.cin = sc.out_channels, sc.in_channels
+        self._chunked(what, "features.0.0", st.out)
+        st.cinp = (st.cin + self.kp - 1) // self.kp * self.kp
+        st.off = self.offs["features.0.0.weight"]
+        st.g = self.grad[st.off:st.off + st.out * st.cin * 9]
+        st.w = torch.zeros(st.out * 9 * st.cinp, dtype=self.dtype, device=self.device)
+        st.g_conv = torch.zeros(st.out * 9 * st.cinp, dtype=torch.float32, device=self.device)
+        st.bn = bn
+        self.stem = st
+        self.in_channels, self.cp = st.cin, st.cinp
+
     def matches(self, model):
         return id(model) == self.model_id and self.first_param.data.data_ptr() == self.master.data_ptr()
 
@@ -327,6 +544,39 @@ class PlanEngine:
             while len(ev) < n_events:
                 ev.append(torch.cuda.Event())
         run_ops(plan.meta[key], main, side, ev, hook, self.hook_syncs_side)
+
+    # ------------------------------------------------------------------------------------------ forward / backward
+    def _forward_plan(self, x, *key, with_backward, ticket, fill=None):
+        """the tail of forward(): the plan of `key` (build_plan's arguments), fresh weights, the NCHW fp32 input `x` into the plan's
+        NHWC buffer, the forward list; `fill(plan)` sets further plan inputs first (a stochastic-depth draw)"""
+        plan = self.acquire_plan(*key, ticket=ticket if with_backward else None)
+        if with_backward:
+            self._fresh(plan)
+        stream = torch.cuda.current_stream().cuda_stream
+        self.refresh_weights(stream, for_backward=with_backward)
+        if fill is not None:
+            fill(plan)
+        N, C, H, W = x.shape
+        lib.pfr_nchw_to_nhwc(x.data_ptr(), plan.meta["x_nhwc"].data_ptr(), self.did, N, C, H, W, self.cp, stream)
+        self._run_fwd(plan, stream)
+        self._last_plan = plan
+        return plan.meta["emb"]
+
+    def backward(self, demb, plan=None):
+        plan = plan if plan is not None else self._last_plan
+        self._begin_backward(plan, demb)
+        # Every gradient kernel of these engines OVERWRITES its slice of the flat buffer.  When gradients are already present
+        # (a second backward before zero_grad: gradient accumulation, list inputs) the previous sum is set aside and added
+        # back afterwards — two extra passes over the flat buffer, only on that path.
+        prev = self.grad.clone() if self.first_param.grad is not None else None
+        hook = self.grad_ready_hook
+        if prev is not None or any(self._plan_busy(q) for q in self.plans.values()):
+            hook = None   # not final yet (accumulating, or another forward pass still waits for its backward)
+        # (the side-stream decision follows the hook IN EFFECT: no bucket is reduced during this pass when it is None)
+        self._run_bwd(plan, "bwd", hook, hook)
+        if prev is not None:
+            self.grad.add_(prev)
+        self.attach_grads()
 
 
 class _EngineFunction(torch.autograd.Function):
