@@ -846,7 +846,9 @@ __global__ __launch_bounds__(256) void window_attn_fwd_kernel(const T* __restric
 }
 
 // backward: recomputes the probabilities; writes dqkv and this workgroup's partial of the position-table gradient
-// (dpos_part [nblocks][(2w−1)²], summed afterwards by pfr_colsum → deterministic).
+// (dpos_part [nblocks][(2w−1)²], summed afterwards by pfr_colsum in a fixed order).  The partial itself is accumulated with
+// atomicAdd on LDS floats, whose order is not fixed: its last bits differ from run to run (measured; dqkv is bit-reproducible, and so
+// is the dpos_part of the MFMA kernel below with its integer bins — tests/test_window_attention_gpu.py).
 template <typename T>
 __global__ __launch_bounds__(256) void window_attn_bwd_kernel(const T* __restrict__ qkv, const float* __restrict__ tab,
                                                               const T* __restrict__ dout, T* __restrict__ dqkv,
