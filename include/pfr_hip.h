@@ -726,6 +726,25 @@ int pfr_bn_bwd_reduce_silu(const void* dout, const void* x, const float* mean, c
                            const float* shift, int dtype, long rows, int C, float* part, pfr_stream_t stream);
 int pfr_bn_bwd_apply_silu(const void* dout, const void* x, const float* coef, const float* scale, const float* shift, void* dx, int dtype,
                           long rows, int C, pfr_stream_t stream);
+/* PReLU forms of the BatchNorm apply / backward (csrc/pfr_prelu.hip; insightface arcface_torch iresnet.py: `self.prelu = nn.PReLU(planes)`
+ * after `self.bn2`, i.e. F.prelu(F.batch_norm(x, ...), weight) and its autograd), beside the _clamp / _silu forms and with their
+ * layouts and checks.  u = scale[c]*x + shift[c], slope [C] fp32 (the nn.PReLU weight as it stands):
+ *   pfr_bn_act_prelu:         y = u > 0 ? u : slope[c]*u   (eval mode: the same kernel on the coefficients of pfr_bn_eval_coeff)
+ *   pfr_bn_bwd_reduce_prelu:  g = dout * (u > 0 ? 1 : slope[c]), u recomputed from the BatchNorm input x (no mask, no stored activation).
+ *                             part: fp32 [nb][2][C] rows (Σg, Σg·x̂) per row block — pfr_bn_bwd_finalize reads them as they stand — followed
+ *                             by [nb][C] rows Σ dout*min(u, 0), the slope gradient (u == 0 contributes 0, as torch's prelu_backward):
+ *                             3*nb*C floats, nb = pfr_colreduce_blocks(C, dtype, rows).  Deterministic, no atomics.
+ *   pfr_prelu_slope_finalize: the SEPARATE finalize of the third rows (pfr_bn_bwd_finalize stays as it is for dgamma, dbeta and coef):
+ *                             dslope[c] = Σ_b part[2*nparts*C + b*C + c] (+ dslope[c] if accumulate); `part`, `nparts` as given to
+ *                             pfr_bn_bwd_reduce_prelu / pfr_bn_bwd_finalize
+ *   pfr_bn_bwd_apply_prelu:   dx = coef0*g + coef1*x + coef2 with the same g (dx may alias dout) */
+int pfr_bn_act_prelu(const void* x, const float* scale, const float* shift, const float* slope, void* y, int dtype, long rows, int C,
+                     pfr_stream_t stream);
+int pfr_bn_bwd_reduce_prelu(const void* dout, const void* x, const float* mean, const float* invstd, const float* scale,
+                            const float* shift, const float* slope, int dtype, long rows, int C, float* part, pfr_stream_t stream);
+int pfr_prelu_slope_finalize(const float* part, int nparts, int C, float* dslope, int accumulate, pfr_stream_t stream);
+int pfr_bn_bwd_apply_prelu(const void* dout, const void* x, const float* coef, const float* scale, const float* shift,
+                           const float* slope, void* dx, int dtype, long rows, int C, pfr_stream_t stream);
 
 /* ---- squeeze-and-excitation of the MBConv block (csrc/pfr_se.hip; torchvision ops/misc.py SqueezeExcitation.forward:
  * `scale = scale_activation(fc2(activation(fc1(avgpool(input))))); return scale * input` with activation = SiLU, scale_activation =

@@ -98,6 +98,8 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
             model_ = getattr(models, arch)(**kw, **(model_kwargs or {}))
             model_.heads = torch.nn.Linear(model_.hidden_dim, 512)
             return model_
+        if arch.startswith('iresnet'):   # the face backbone: flatten → fc → features IS its 512-d embedding neck (models/iresnet.py)
+            return getattr(models, arch)(num_features=512, **kw, **(model_kwargs or {}))
         model_ = getattr(models, arch)(**kw)
         model_.fc = torch.nn.Linear(model_.fc.in_features, 512)
         return model_
@@ -122,8 +124,9 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
     def optimizer(model_):
         # the reference's backbone / embedding-layer split ('fc'); the embedding layer of the torchvision-style backbones is `classifier` / `heads`
         head = 'classifier' if arch.startswith(('convnext', 'mobilenet', 'efficientnet')) else ('heads' if arch.startswith('vit') else 'fc')
-        params1 = [p for i, p in model_.module.named_parameters() if head not in i]
-        params2 = [p for i, p in model_.module.named_parameters() if head in i]
+        heads = ('fc.', 'features.') if arch.startswith('iresnet') else (head,)   # IResNet: the Linear and the BatchNorm1d behind it
+        params1 = [p for i, p in model_.module.named_parameters() if not any(h in i for h in heads)]
+        params2 = [p for i, p in model_.module.named_parameters() if any(h in i for h in heads)]
         base = _live('init_lr', 10 ** -2 if optimizer_kind == 'sgd' else 10 ** -3)
         d = [{'lr': base / 2, 'params': params1},
              {'lr': base, 'params': params2},

@@ -1,5 +1,5 @@
-"""PlanEngine — the plan runtime and the plan builder shared by the six engines: models/_fe_engine.FEEngine (ResNet), _swin_engine,
-_convnext_engine, _vit_engine, _mobilenet_engine and _efficientnet_engine.
+"""PlanEngine — the plan runtime and the plan builder shared by the seven engines: models/_fe_engine.FEEngine (ResNet), _swin_engine,
+_convnext_engine, _vit_engine, _mobilenet_engine, _efficientnet_engine and _iresnet_engine.
 
 An engine turns a model into pre-built launch lists ("plans": C-ABI calls with fixed device pointers, one plan per input
 shape).  Everything that makes such a list a training step on two streams is model-independent and lives here, once:
@@ -18,9 +18,9 @@ shape).  Everything that makes such a list a training step on two streams is mod
   * parameter adoption (_adopt_flat; _adopt_batchnorms and the 1x1 / stem records of the BatchNorm networks), the tail of
     forward() (_forward_plan) and backward().
 
-Who uses what: all six engines use the runtime.  Swin, ConvNeXt, ViT, MobileNetV2 and EfficientNet build their plans with
+Who uses what: all seven engines use the runtime.  Swin, ConvNeXt, ViT, MobileNetV2, EfficientNet and IResNet build their plans with
 PlanBuilder and the layer emitters of models/_plan_layers.py (Linear / LayerNorm family: Swin, ConvNeXt, ViT; BatchNorm family:
-MobileNetV2, EfficientNet), adopt their parameters with _adopt_flat and run _forward_plan and backward() as they stand.  FEEngine
+MobileNetV2, EfficientNet, IResNet), adopt their parameters with _adopt_flat and run _forward_plan and backward() as they stand.  FEEngine
 keeps a builder of its own (a FIFO pool with a measured lag, weight gradients that carry a BatchNorm prologue, a second workspace),
 its own _adopt, forward and backward.
 
@@ -286,11 +286,12 @@ class PlanEngine:
         self.first_param = named[0][1]
         return offs
 
-    def _adopt_batchnorms(self, model, what):
+    def _adopt_batchnorms(self, model, what, kinds=(torch.nn.BatchNorm2d,)):
         """BatchNorm buffers → flat `stats` (running means, then running variances) and `nbt`, as FEEngine; running_mean /
-        running_var / num_batches_tracked of the modules become views.  → id(module) -> record"""
+        running_var / num_batches_tracked of the modules become views.  → id(module) -> record.  A weight that is not in the flat
+        buffers (frozen; the engine has moved it to the device) is read where it stands, its gradient goes to scratch."""
         dev, offs = self.device, self.offs
-        bns = [(n, m) for n, m in model.named_modules() if isinstance(m, torch.nn.BatchNorm2d)]
+        bns = [(n, m) for n, m in model.named_modules() if isinstance(m, kinds)]
         nstat = sum(m.num_features for _, m in bns)
         self.stats = torch.zeros(2 * nstat, dtype=torch.float32, device=dev)
         self.nbt = torch.zeros(len(bns), dtype=torch.int64, device=dev)
@@ -308,8 +309,11 @@ class PlanEngine:
             self.nbt[i] = int(m.num_batches_tracked.item())
             m.running_mean, m.running_var, m.num_batches_tracked = b.rm, b.rv, self.nbt[i]
             so += C
-            ow, ob = offs[n + ".weight"], offs[n + ".bias"]
-            b.gamma, b.dgamma = self.master[ow:ow + C], self.grad[ow:ow + C]
+            ow, ob = offs.get(n + ".weight"), offs[n + ".bias"]
+            if ow is None:
+                b.gamma, b.dgamma = m.weight.data, torch.zeros(C, dtype=torch.float32, device=dev)
+            else:
+                b.gamma, b.dgamma = self.master[ow:ow + C], self.grad[ow:ow + C]
             b.beta, b.dbeta = self.master[ob:ob + C], self.grad[ob:ob + C]
             bn_of[id(m)] = b
         maxc = max(m.num_features for _, m in bns)
@@ -340,15 +344,15 @@ class PlanEngine:
         return (m.kernel_size == (k, k) and m.stride == (stride, stride) and m.padding == ((k - 1) // 2,) * 2 and m.groups == groups
                 and m.dilation == (1, 1) and m.bias is None)
 
-    def _adopt_stem(self, what, sc, bn):
-        """the 3x3 stride-2 stem `features.0.0` and its BatchNorm record: [O][3][3][3] parameter ↔ [O][9][I padded] conv layout"""
-        if not self._plain(sc, 3, 2, 1):
-            raise PfrError(f"HIP {what} path: the stem is a bias-free 3x3 stride-2 convolution")
+    def _adopt_stem(self, what, sc, bn, stride=2, name="features.0.0"):
+        """the 3x3 stem `name` (stride 2 unless given) and its BatchNorm record: [O][3][3][3] parameter ↔ [O][9][I padded] conv layout"""
+        if not self._plain(sc, 3, stride, 1):
+            raise PfrError(f"HIP {what} path: the stem is a bias-free 3x3 stride-{stride} convolution")
         st = _Rec()
         st.out, st.cin = sc.out_channels, sc.in_channels
-        self._chunked(what, "features.0.0", st.out)
+        self._chunked(what, name, st.out)
         st.cinp = (st.cin + self.kp - 1) // self.kp * self.kp
-        st.off = self.offs["features.0.0.weight"]
+        st.off = self.offs[name + ".weight"]
         st.g = self.grad[st.off:st.off + st.out * st.cin * 9]
         st.w = torch.zeros(st.out * 9 * st.cinp, dtype=self.dtype, device=self.device)
         st.g_conv = torch.zeros(st.out * 9 * st.cinp, dtype=torch.float32, device=self.device)

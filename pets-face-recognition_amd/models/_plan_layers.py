@@ -1,13 +1,14 @@
 """Layer emitters on a models/_plan_engine.PlanBuilder `pb`: the launches of one layer appended to pb.fwd or pb.bwd.
 
   Linear / LayerNorm family (Swin, ConvNeXt, ViT): gemm, dgrad_lin, ln_fwd, ln_bwd, bias_grad
-  BatchNorm family (MobileNetV2, EfficientNet):    BatchNormLayers — coef, bn_fwd, conv_bn, dgrad_pw, bn_bwd
+  BatchNorm family (MobileNetV2, EfficientNet, IResNet):    BatchNormLayers — coef, bn_fwd, conv_bn, dgrad_pw, bn_bwd
 
 A Linear record `r` has out, inp, w ([out][in]), wt ([in][out]) and bias (or None); a LayerNorm record gamma, beta, dgamma, dbeta,
 eps; a BatchNorm record is what PlanEngine._adopt_batchnorms returns."""
 import torch
 
 from .._hip import lib, dtype_id
+from .._hip.cplan import SIDE
 from ._plan_engine import _Rec
 
 
@@ -113,15 +114,19 @@ class BatchNormLayers:
         self.pb.bwd.append((lib.pfr_conv2d_fwd, (dy.data_ptr(), r.wt.data_ptr(), dx.data_ptr(), did, did, rows, 1, 1, r.out, r.inp, 1, 1, 1,
                                                  0, 0, 1, 1, r.inp, 0, 0 if residual is None else residual.data_ptr(), 0, 0, 0, 0, 0, 0)))
 
-    def bn_bwd(self, dout, z, c, rows, act=None, hi=0.0):
-        """dz of z from the gradient of act(bn(z)) — `act` None (linear), "clamp" (to [0, hi]: ReLU6 with hi = 6) or "silu", the
+    def bn_bwd(self, dout, z, c, rows, act=None, hi=0.0, slope=None):
+        """dz of z from the gradient of act(bn(z)) — `act` None (linear), "clamp" (to [0, hi]: ReLU6 with hi = 6), "silu" or "prelu"
+        (`slope`: the record of the nn.PReLU weight, w and g [C] fp32; its gradient is finalised on the side stream), the
         derivative recomputed from z — into a pooled buffer; dgamma / dbeta into the flat gradient"""
         pb, did, bn = self.pb, self.pb.did, c.bn
         bwd = pb.bwd
         nb = lib.pfr_colreduce_blocks(bn.C, did, rows)
-        part = pb.A((nb, 2, bn.C), torch.float32)
+        part = pb.A((nb, 3 if act == "prelu" else 2, bn.C), torch.float32)
         mode, hi = (2, hi) if act == "clamp" else (0, 0.0)
-        if act == "silu":
+        if act == "prelu":
+            bwd.append((lib.pfr_bn_bwd_reduce_prelu, (dout.data_ptr(), z.data_ptr(), c.f[0].data_ptr(), c.f[1].data_ptr(), c.scale.data_ptr(),
+                                                      c.shift.data_ptr(), slope.w.data_ptr(), did, rows, bn.C, part.data_ptr())))
+        elif act == "silu":
             bwd.append((lib.pfr_bn_bwd_reduce_silu, (dout.data_ptr(), z.data_ptr(), c.f[0].data_ptr(), c.f[1].data_ptr(),
                                                      c.scale.data_ptr(), c.shift.data_ptr(), did, rows, bn.C, part.data_ptr())))
         else:
@@ -130,7 +135,11 @@ class BatchNormLayers:
         bwd.append((lib.pfr_bn_bwd_finalize, (part.data_ptr(), nb, bn.C, float(rows), bn.gamma.data_ptr(), c.f[0].data_ptr(),
                                               c.f[1].data_ptr(), bn.dgamma.data_ptr(), bn.dbeta.data_ptr(), c.b.data_ptr(), 0)))
         dz = pb.G(tuple(z.shape))
-        if act == "silu":
+        if act == "prelu":
+            pb.side((SIDE, (lib.pfr_prelu_slope_finalize, (part.data_ptr(), nb, bn.C, slope.g.data_ptr(), 0))))
+            bwd.append((lib.pfr_bn_bwd_apply_prelu, (dout.data_ptr(), z.data_ptr(), c.b.data_ptr(), c.scale.data_ptr(), c.shift.data_ptr(),
+                                                     slope.w.data_ptr(), dz.data_ptr(), did, rows, bn.C)))
+        elif act == "silu":
             bwd.append((lib.pfr_bn_bwd_apply_silu, (dout.data_ptr(), z.data_ptr(), c.b.data_ptr(), c.scale.data_ptr(), c.shift.data_ptr(),
                                                     dz.data_ptr(), did, rows, bn.C)))
         else:
