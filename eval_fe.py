@@ -25,8 +25,13 @@ def main(argv=None):
     ap.add_argument('--checkpoint', type=Path, default=None, help='state_dict with keys model_loss.module.* (optional)')
     ap.add_argument('--averaged', action='store_true',
                     help="evaluate the checkpoint's averaged weights: `averaged_state_dict` of its .trainer sidecar (Trainer(ema_decay=))")
+    ap.add_argument('--all-pairs-far', type=float, nargs='+', default=None, metavar='F',
+                    help='also report verification metrics over EVERY pair of the set (score histograms from one GEMM): '
+                         'AllPairs ROC AUC / EER and TAR, threshold at each of these false-accept rates, e.g. 1e-4 1e-5 1e-6')
     args = ap.parse_args(argv)
     config = get_config(args.config)
+    if args.all_pairs_far is not None:
+        config['all_pairs_far'] = list(args.all_pairs_far)
     controller = Controller(config)
     if args.averaged and args.checkpoint is None:
         ap.error('--averaged needs --checkpoint')

@@ -534,6 +534,23 @@ long pfr_pair_curve_ws_bytes(int P);
 int pfr_pair_curve(const float* scores, const int* labels, int P, void* workspace, float* sorted_scores, int* cum_tp,
                    unsigned char* run_end, pfr_stream_t stream);
 
+/* ---- all-pairs verification: genuine / impostor score histograms of EVERY pair, from the match GEMM with a histogram epilogue (the
+ * score matrix is never written).  a [Na][D], b [Nb][D]: rows of `dtype` in the layouts of the match — PFR_F32 / PFR_BF16 rows with the
+ * D multiples of pfr_match_scores_filter (128-byte k-steps: D % 32 == 0 / D % 64 == 0); PFR_I8 rows of pfr_quantize_rows_i8 with their
+ * scales a_scale [Na], b_scale [Nb] (D = Dp, Dp % 128 == 0, Dp <= 1040 so that the int32 -> float conversion is exact); the scales are
+ * NULL for the other dtypes.  a_cls [Na], b_cls [Nb]: int32 class of every row.  b == NULL: symmetric mode, every unordered pair i < j
+ * of a is counted exactly once (b_scale, b_cls, Nb are ignored).
+ *   Score s of (a row i, b row j): the fp32 accumulator (PFR_F32, PFR_BF16), or ((float) acc * a_scale[i]) * b_scale[j] (PFR_I8; the
+ *     operations and the order of pfr_match_scores_i8).
+ *   Bin rule (fp32, each operation rounded on its own, no fma):  x = (s - lo) * inv_w;  t = floorf(x);
+ *     bin = (int) fminf(fmaxf(t, 0), bins - 1);  a NaN score goes to slot `bins`.  Scores outside the range therefore saturate into
+ *     the first or the last bin.  1 <= bins <= 8192; inv_w > 0.
+ *   kind = (a_cls[i] == b_cls[j]) ? 1 : 0;   hist[kind][bin] += 1   with hist u64 [2][bins + 1].
+ * The call ADDS to hist (the caller zeroes it; chunked or sharded callers accumulate into one table).  Na == 0, Nb == 0 and a symmetric
+ * Na == 1 add nothing and return 0.  Workgroup-private counters are 32-bit and are flushed after at most 2^16 tiles of 2^14 pairs. */
+int pfr_pair_hist(const void* a, const float* a_scale, const int* a_cls, int Na, const void* b, const float* b_scale, const int* b_cls,
+                  int Nb, int dtype, int D, float lo, float inv_w, int bins, unsigned long long* hist, pfr_stream_t stream);
+
 /* mean-strategy card matching (generate_tsv.py:71-78,91-125): centroid of the L2-normalised photo embeddings of each card;
  * seg [ncards+1] int64 row offsets; cent32 fp32 [ncards][D] (always written), cent (cent_dtype) optional copy */
 int pfr_card_centroids(const float* emb, const long* seg, int ncards, int D, float eps, float* cent32, void* cent,

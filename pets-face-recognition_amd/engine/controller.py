@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import metrics as M
-from ..match import recall_at_k, pair_similarity
+from ..match import recall_at_k, pair_similarity, pair_histogram
 
 
 class Controller(nn.Module):
@@ -103,6 +103,22 @@ class Controller(nn.Module):
         dt = torch.float32 if not emb.is_cuda else getattr(self.config, 'match_dtype', torch.bfloat16)
         return recall_at_k(emb, classes, tuple(ks), compute_dtype=dt)
 
+    def _all_pairs(self, emb, classes):
+        """Opt-in (config.all_pairs_far, a list of FARs): verification metrics over EVERY pair of the validation set from the genuine /
+        impostor score histograms (match.pair_histogram: one GEMM with a histogram epilogue on the device) instead of the sampled pair
+        list — TAR at FAR 1e-4 .. 1e-6 needs the ~N^2 / 2 impostor pairs.  Thresholds are similarities (cos + 1) / 2 like TH@FAR."""
+        fars = self.config.get('all_pairs_far')
+        if fars is None:
+            return {}
+        dt = torch.float32 if not emb.is_cuda else getattr(self.config, 'match_dtype', torch.bfloat16)
+        hist, lo, inv_w = pair_histogram(emb, classes, bins=int(self.config.get('all_pairs_bins', 4096)), compute_dtype=dt)
+        hs = M.HistStats(hist, lo, inv_w)
+        out = {'AllPairs ROC AUC': hs.auroc(), 'AllPairs EER': hs.eer()}
+        pts = hs.far_points(list(fars))
+        out.update((f'AllPairs TAR@FAR={far}', pts[far][0]) for far in fars)
+        out.update((f'AllPairs TH@FAR={far}', pts[far][1]) for far in fars)
+        return out
+
     def test_epoch_end(self, outputs):
         all_metrics = {}
         for i in range(len(outputs)):
@@ -113,6 +129,7 @@ class Controller(nn.Module):
             metrics = {'ROC AUC': ps.auroc(), 'Accuracy': ps.best_threshold_accuracy()[0]}
             rk = self._recall(emb, classes, [10, 100])
             metrics.update({f'Recall@K={k}': (x / y if y else float('nan')) for k, (x, y) in rk.items()})
+            metrics.update(self._all_pairs(emb, classes))
             print('', *[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')
             all_metrics[name] = metrics
         self.last_metrics = all_metrics
@@ -160,6 +177,7 @@ class Controller(nn.Module):
             for frr, (trr, th) in ps.frr_points(cfg.get('frr_thr', ())).items():
                 metrics[f'TRR@FRR={frr}'] = trr
                 metrics[f'TH@FRR={frr}'] = th
+            metrics.update(self._all_pairs(emb, classes))
             all_metrics[name] = metrics
             self.last_confmat[name] = confmat
             print(*[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')

@@ -127,6 +127,68 @@ class PairStats:
         return out
 
 
+class HistStats:
+    """Verification metrics from the genuine / impostor score HISTOGRAMS of every pair (match.pair_histogram): `hist` int64
+    [2, bins + 1] (row 1 = genuine, last slot = NaN scores), with the bin of a score s = clamp(floor((s - lo) * inv_w), 0, bins - 1).
+    Operating point b (0 .. bins): a pair is predicted positive when its bin is >= b, so TP(b) / FP(b) are suffix sums of the two
+    rows (b = bins predicts nothing).  The NaN slot is reported as `n_nan` and takes part in no rate.  Thresholds are the lower
+    edge lo + b / inv_w of bin b, mapped to the reference's similarity (cos + 1) / 2 when `to_similarity`."""
+
+    def __init__(self, hist, lo, inv_w, to_similarity=True):
+        h = torch.as_tensor(hist).detach().cpu().long()
+        if h.dim() != 2 or h.shape[0] != 2 or h.shape[1] < 2:
+            raise ValueError("HistStats: hist must be [2, bins + 1]")
+        self.bins = h.shape[1] - 1
+        self.lo, self.inv_w, self.to_similarity = float(lo), float(inv_w), bool(to_similarity)
+        self.neg, self.pos = h[0, :self.bins], h[1, :self.bins]
+        self.n_nan = int(h[:, self.bins].sum())
+        self.n_pos, self.n_neg = int(self.pos.sum()), int(self.neg.sum())
+        z = torch.zeros(1, dtype=torch.long)
+        # suffix sums, index b = 0 .. bins
+        self.tp = torch.cat([self.pos.flip(0).cumsum(0).flip(0), z])
+        self.fp = torch.cat([self.neg.flip(0).cumsum(0).flip(0), z])
+
+    def threshold(self, b):
+        t = self.lo + b / self.inv_w
+        return (t + 1) / 2 if self.to_similarity else t
+
+    def auroc(self):
+        """trapezoid over the operating points in float64: the pairs inside one bin count as ties (half a win each)"""
+        tpr = self.tp.double().flip(0) / max(self.n_pos, 1)
+        fpr = self.fp.double().flip(0) / max(self.n_neg, 1)
+        return float(torch.trapz(tpr, fpr))
+
+    def eer(self):
+        """equal error rate: (FAR + FRR) / 2 at the operating point where |FAR - FRR| is smallest (ties: the lowest bin)"""
+        far = self.fp.double() / max(self.n_neg, 1)
+        frr = 1 - self.tp.double() / max(self.n_pos, 1)
+        b = int(torch.argmin((far - frr).abs()))
+        return float((far[b] + frr[b]) / 2)
+
+    def stats_at_bin(self, b):
+        b = int(b)
+        if not 0 <= b <= self.bins:
+            raise ValueError(f"HistStats: operating point {b} outside 0..{self.bins}")
+        tp, fp = int(self.tp[b]), int(self.fp[b])
+        fn, tn = self.n_pos - tp, self.n_neg - fp
+        return dict(tp=tp, fp=fp, tn=tn, fn=fn, threshold=self.threshold(b),
+                    tar=tp / self.n_pos if self.n_pos else 0.0, far=fp / self.n_neg if self.n_neg else 0.0,
+                    accuracy=(tp + tn) / max(1, self.n_pos + self.n_neg))
+
+    def far_points(self, fars):
+        """for every far: the smallest b with FP(b) / n_neg <= far — the most permissive threshold that does not exceed it (b = bins,
+        which accepts nothing, always qualifies; the comparison is on integers: FP(b) <= far * n_neg evaluated as FP(b) / n_neg <= far
+        in float64) → {far: (TAR, threshold, achieved FAR)}"""
+        out = {}
+        rate = self.fp.double() / max(self.n_neg, 1)          # non-increasing in b
+        for far in fars:
+            ok = torch.nonzero(rate <= float(far)).flatten()
+            b = int(ok[0])
+            st = self.stats_at_bin(b)
+            out[far] = (st['tar'], st['threshold'], st['far'])
+        return out
+
+
 # ---- function forms (one sort per call)
 def roc_curve(scores, labels):
     return PairStats(scores, labels).roc()

@@ -567,3 +567,93 @@ def cosine_topk_sharded(q, g_local, k, g_offset, group=None, **kw):
     S, I = torch.gather(S, 1, order), torch.gather(I, 1, order)
     order = torch.argsort(S, dim=1, descending=True, stable=True)[:, :k]
     return torch.gather(S, 1, order), torch.gather(I, 1, order)
+
+
+# ---- all-pairs verification ------------------------------------------------------------------------------------------------------
+_PAIR_HIST_DTYPES = (torch.float32, torch.bfloat16, torch.int8)
+
+
+def _hist_range(bins, range):
+    """(lo, inv_w) as the fp32 numbers both paths use: inv_w = float32(bins) / (float32(hi) - float32(lo))"""
+    lo, hi = torch.tensor(float(range[0]), dtype=torch.float32), torch.tensor(float(range[1]), dtype=torch.float32)
+    inv_w = torch.tensor(float(bins), dtype=torch.float32) / (hi - lo)
+    if not (bool(torch.isfinite(inv_w)) and float(inv_w) > 0 and bool(torch.isfinite(lo))):
+        raise PfrError(f"pair_histogram: bad range {tuple(range)}")
+    return float(lo), float(inv_w)
+
+
+def _pad_cols(x, mult):
+    pad = -x.shape[1] % mult
+    return x if pad == 0 else torch.nn.functional.pad(x, (0, pad)).contiguous()
+
+
+def _hist_operand(x, T, normalize):
+    """rows -> (GEMM operand of pfr_pair_hist, per-row scales or None): the match's own preparation, columns zero padded to a 128-byte k-step"""
+    x32 = x.float().contiguous()
+    if T == torch.int8:
+        (q8, sc), _ = _prep_rows_i8(x32, False, normalize)
+        return q8, sc
+    xn, _ = _prep_rows(x32, T, False, normalize)
+    return _pad_cols(xn.contiguous(), 32 if T == torch.float32 else 64), None
+
+
+def pair_histogram(emb, classes, emb_b=None, classes_b=None, bins=4096, range=(-1.0, 1.0), compute_dtype=torch.bfloat16, normalize=True):
+    """Genuine / impostor score histograms over EVERY pair: all unordered pairs i < j of `emb` [N, D], or — with `emb_b`, `classes_b` — all
+    Na x Nb pairs of the two sets.  The score of a pair is the dot product of the (L2-normalised unless normalize=False) rows in
+    `compute_dtype` (torch.float32, torch.bfloat16, or torch.int8: the selection score of `quantize_rows`); it is binned by the rule of
+    pfr_pair_hist (include/pfr_hip.h): x = (s - lo) * inv_w in fp32, bin = clamp(floor(x), 0, bins - 1), NaN -> slot `bins`.
+    → (hist int64 [2, bins + 1] with hist[1] the same-class pairs, lo, inv_w).
+    CUDA tensors: ONE pfr_pair_hist launch, the score matrix is never written.  CPU tensors: chunked fp32 matmul, same bin rule."""
+    if compute_dtype not in _PAIR_HIST_DTYPES:
+        raise PfrError(f"pair_histogram: compute_dtype must be one of {_PAIR_HIST_DTYPES}")
+    bins = int(bins)
+    if not 1 <= bins <= 8192:
+        raise PfrError(f"pair_histogram: bins={bins} must be in 1..8192")
+    if (emb_b is None) != (classes_b is None):
+        raise PfrError("pair_histogram: emb_b and classes_b come together")
+    if emb.dim() != 2 or classes.numel() != emb.shape[0] or (emb_b is not None and (emb_b.dim() != 2 or emb_b.shape[1] != emb.shape[1]
+                                                                                    or classes_b.numel() != emb_b.shape[0])):
+        raise PfrError("pair_histogram: emb [N, D] with classes [N] (and emb_b [Nb, D] with classes_b [Nb])")
+    lo, inv_w = _hist_range(bins, range)
+    if not emb.is_cuda:
+        return _pair_histogram_torch(emb, classes, emb_b, classes_b, bins, lo, inv_w, normalize), lo, inv_w
+    dev = emb.device
+    hist = torch.zeros((2, bins + 1), dtype=torch.int64, device=dev)
+    Na, Nb = emb.shape[0], 0 if emb_b is None else emb_b.shape[0]
+    if Na == 0 or (emb_b is None and Na == 1) or (emb_b is not None and Nb == 0):
+        return hist, lo, inv_w
+    a, sa = _hist_operand(emb, compute_dtype, normalize)
+    ca = classes.to(device=dev, dtype=torch.int32).contiguous()
+    b = sb = cb = None
+    if emb_b is not None:
+        b, sb = _hist_operand(emb_b.to(dev), compute_dtype, normalize)
+        cb = classes_b.to(device=dev, dtype=torch.int32).contiguous()
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    lib.pfr_pair_hist(ptr(a), ptr(sa), ptr(ca), Na, ptr(b), ptr(sb), ptr(cb), Nb, dtype_id(compute_dtype), a.shape[1], lo, inv_w, bins,
+                      hist.data_ptr(), _stream())
+    return hist, lo, inv_w
+
+
+def _bin_rule_torch(s, lo, inv_w, bins):
+    """the bin rule on an fp32 tensor of scores -> int64 slots (NaN -> bins)"""
+    x = (s - torch.tensor(lo, dtype=torch.float32)) * torch.tensor(inv_w, dtype=torch.float32)
+    slot = torch.floor(x).clamp(0, bins - 1)
+    return torch.where(torch.isnan(s), torch.full_like(slot, bins), slot).long()
+
+
+def _pair_histogram_torch(emb, classes, emb_b, classes_b, bins, lo, inv_w, normalize, chunk=2048):
+    def rows(x):
+        x = x.float()
+        return x / x.norm(dim=1, keepdim=True).clamp_min(1e-12) if normalize else x
+    a, ca = rows(emb), classes.long().reshape(-1)
+    sym = emb_b is None
+    b, cb = (a, ca) if sym else (rows(emb_b), classes_b.long().reshape(-1))
+    hist = torch.zeros(2 * (bins + 1), dtype=torch.int64)
+    jb = torch.arange(b.shape[0])
+    for r0 in range(0, a.shape[0], chunk):
+        s = a[r0:r0 + chunk] @ b.t()
+        slot = _bin_rule_torch(s, lo, inv_w, bins) + (ca[r0:r0 + chunk, None] == cb[None, :]).long() * (bins + 1)
+        if sym:
+            slot = slot[torch.arange(r0, r0 + s.shape[0])[:, None] < jb[None, :]]
+        hist += torch.bincount(slot.reshape(-1), minlength=2 * (bins + 1))
+    return hist.view(2, bins + 1)
