@@ -28,8 +28,13 @@ def main(argv=None):
     ap.add_argument('--all-pairs-far', type=float, nargs='+', default=None, metavar='F',
                     help='also report verification metrics over EVERY pair of the set (score histograms from one GEMM): '
                          'AllPairs ROC AUC / EER and TAR, threshold at each of these false-accept rates, e.g. 1e-4 1e-5 1e-6')
+    ap.add_argument('--rerank', nargs=3, default=None, metavar=('K1', 'K2', 'LAMBDA'),
+                    help="also report 'Rerank Recall@K=…': Recall@K of the k-reciprocal re-ranked match lists (match.rerank), "
+                         'e.g. 20 6 0.3')
     args = ap.parse_args(argv)
     config = get_config(args.config)
+    if args.rerank is not None:
+        config['rerank'] = dict(k1=int(args.rerank[0]), k2=int(args.rerank[1]), lambda_value=float(args.rerank[2]))
     if args.all_pairs_far is not None:
         config['all_pairs_far'] = list(args.all_pairs_far)
     controller = Controller(config)

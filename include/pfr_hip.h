@@ -551,6 +551,48 @@ int pfr_pair_curve(const float* scores, const int* labels, int P, void* workspac
 int pfr_pair_hist(const void* a, const float* a_scale, const int* a_cls, int Na, const void* b, const float* b_scale, const int* b_cls,
                   int Nb, int dtype, int D, float lo, float inv_w, int bins, unsigned long long* hist, pfr_stream_t stream);
 
+/* ---- k-reciprocal re-ranking of match lists (Zhong et al., "Re-ranking Person Re-identification with k-reciprocal Encoding", CVPR 2017)
+ * on SPARSE rows: nothing N x N is built.  The set is N items with unit-norm fp32 rows emb32 [N][D].
+ * Inputs
+ *   nbr [N][K1] int32, K1 = k1 + 1: nbr[i][0] = i, then the k1 nearest OTHER items by descending cosine, padded with -1 when N - 1 < k1.
+ *     Any entry outside [0, N) is padding and is skipped, wherever it stands; the kernels never use it as an address.
+ *   cand [R][kc] int32 with cand_cos [R][kc] fp32: the candidates to be re-ranked for the R output rows rows [R], sorted by descending
+ *     cosine, padded with -1 / -inf; kc <= 512 (the limit of the running top-K lists that produce them).
+ * Definitions
+ *   kh = round(k1 / 2) with halves to even, as Python's round() in the published code (k1 = 5 -> 2, k1 = 3 -> 2, k1 = 1 -> 0).
+ *   L_k(i) = the first k + 1 valid entries of nbr[i].        R(i, k) = { j in L_k(i) : i in L_k(j) }.
+ * Steps
+ *   1. Expansion.  R*(i) = R(i, k1)  ∪  ⋃ { R(j, kh) : j in R(i, k1) and 3 |R(j, kh) ∩ R(i, k1)| > 2 |R(j, kh)| }; the intersection is
+ *      taken with the UNEXPANDED R(i, k1); duplicates are removed.  Integer logic: exact.  Row capacity E = (k1 + 1) + (k1 + 1)(kh + 1).
+ *   2. Weights.  For j in R*(i): d(i, j) = 2 - 2 <emb32[i], emb32[j]> (the squared Euclidean distance of unit rows, computed in fp32 from
+ *      the rows, because j need not be in nbr[i]);  V[i][j] = exp(-d(i, j)) / Σ_j' exp(-d(i, j')).  Rows are stored padded (-1 / 0),
+ *      sorted by ascending index, with a count.
+ *      DEVIATION from the published code: that code first divides the distance matrix by its per-column maximum, which needs the N x N
+ *      matrix; this normalisation is dropped.
+ *   3. Local query expansion.  V'[i] = (1 / k2') Σ_{n in the first k2' valid entries of nbr[i]} V[n], k2' = min(k2, valid entries); self is
+ *      included, as in the published code.  Capacity E2 = k2 E.  k2 = 1 is the identity (bit for bit).
+ *   4. Scores.  For an output row i = rows[r] and each valid c = cand[r][t]:  m = Σ_j min(V'[i][j], V'[c][j]) over the common j;
+ *      dJ = 1 - m / (2 - m) (exact Jaccard: both rows sum to 1);  final = (1 - lambda) dJ + lambda (2 - 2 cand_cos[r][t]).
+ *      Output: the k smallest as dist [R][k] fp32 ascending with idx [R][k] int32 (= cand[r][t]); ties -> lower position t; padding +inf / -1.
+ *      A row index rows[r] outside [0, N) gives an all-padding output row.
+ * RESTRICTED CANDIDATE LISTS: re-ranking kc candidates equals re-ranking everything only when the list covers every other item — an item
+ *   outside the list with a non-zero overlap m could otherwise enter the top k.
+ * Determinism: every reduction runs in a fixed order, there are no floating-point atomics: two calls on the same inputs give the same bits.
+ * One workgroup per row, lists and sets in LDS sized from E, E2 and kc; (k1, k2) whose rows do not fit the 160 KiB return
+ * PFR_ERR_UNSUPPORTED.  Argument errors (null pointers, k1 < 1, k1 + 1 > 512, k2 < 1, kc > 512, k > kc, rows shorter than the capacity) return
+ * PFR_ERR_ARG and launch nothing. */
+/* host only, no device needed: E and E2 of (k1, k2) — the row lengths the caller's buffers need */
+int pfr_rerank_row_capacity(int k1, int k2, int* E, int* E2);
+/* steps 1 and 2: v_idx [N][cap] int32 (ascending, -1 padded), v_val [N][cap] fp32 (0 padded), v_cnt [N] int32; cap >= E */
+int pfr_rerank_expand(const float* emb32, int N, int D, const int* nbr, int k1, int* v_idx, float* v_val, int* v_cnt, int cap,
+                      pfr_stream_t stream);
+/* step 3: the rows of pfr_rerank_expand (cap >= E) -> q_idx / q_val [N][cap2], q_cnt [N] in the same layout; cap2 >= E2 */
+int pfr_rerank_average(const int* nbr, int N, int k1, int k2, const int* v_idx, const float* v_val, const int* v_cnt, int cap, int* q_idx,
+                       float* q_val, int* q_cnt, int cap2, pfr_stream_t stream);
+/* step 4 on the rows of pfr_rerank_average (row length cap2), including the per-row sort of the kc <= 512 values; 0 <= lambda <= 1 */
+int pfr_rerank_score(const int* q_idx, const float* q_val, const int* q_cnt, int N, int cap2, const int* rows, int R, const int* cand,
+                     const float* cand_cos, int kc, float lambda, int k, float* dist, int* idx, pfr_stream_t stream);
+
 /* mean-strategy card matching (generate_tsv.py:71-78,91-125): centroid of the L2-normalised photo embeddings of each card;
  * seg [ncards+1] int64 row offsets; cent32 fp32 [ncards][D] (always written), cent (cent_dtype) optional copy */
 int pfr_card_centroids(const float* emb, const long* seg, int ncards, int D, float eps, float* cent32, void* cent,

@@ -103,6 +103,16 @@ class Controller(nn.Module):
         dt = torch.float32 if not emb.is_cuda else getattr(self.config, 'match_dtype', torch.bfloat16)
         return recall_at_k(emb, classes, tuple(ks), compute_dtype=dt)
 
+    def _rerank_recall(self, emb, classes, ks):
+        """Opt-in (config.rerank = dict(k1=…, k2=…, lambda_value=…[, candidates=…])): Recall@K of the k-reciprocal re-ranked order
+        (match.rerank) next to the cosine-order Recall@K, as 'Rerank Recall@K={k}'."""
+        rr = self.config.get('rerank')
+        if rr is None or not len(ks):
+            return {}
+        dt = torch.float32 if not emb.is_cuda else getattr(self.config, 'match_dtype', torch.bfloat16)
+        rk = recall_at_k(emb, classes, tuple(ks), compute_dtype=dt, rerank=dict(rr))
+        return {f'Rerank Recall@K={k}': (x / y if y else float('nan')) for k, (x, y) in rk.items()}
+
     def _all_pairs(self, emb, classes):
         """Opt-in (config.all_pairs_far, a list of FARs): verification metrics over EVERY pair of the validation set from the genuine /
         impostor score histograms (match.pair_histogram: one GEMM with a histogram epilogue on the device) instead of the sampled pair
@@ -130,6 +140,7 @@ class Controller(nn.Module):
             rk = self._recall(emb, classes, [10, 100])
             metrics.update({f'Recall@K={k}': (x / y if y else float('nan')) for k, (x, y) in rk.items()})
             metrics.update(self._all_pairs(emb, classes))
+            metrics.update(self._rerank_recall(emb, classes, [10, 100]))
             print('', *[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')
             all_metrics[name] = metrics
         self.last_metrics = all_metrics
@@ -178,6 +189,7 @@ class Controller(nn.Module):
                 metrics[f'TRR@FRR={frr}'] = trr
                 metrics[f'TH@FRR={frr}'] = th
             metrics.update(self._all_pairs(emb, classes))
+            metrics.update(self._rerank_recall(emb, classes, ks))
             all_metrics[name] = metrics
             self.last_confmat[name] = confmat
             print(*[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')

@@ -345,12 +345,17 @@ def _cosine_topk_torch(q, g, k, exclude_self, normalize=True):
     return torch.gather(sc, 1, order), order.int()
 
 
-def recall_at_k(emb, classes, ks=(10, 100), compute_dtype=torch.float32):
+def recall_at_k(emb, classes, ks=(10, 100), compute_dtype=torch.float32, rerank=None):
     """candR@K of the reference's validation protocol (controller.py:77-90): every embedding queries all the OTHERS;
     a hit at K = some same-class item among the K best; denominator = queries that have a same-class other.
+    rerank: None, or a dict of keyword arguments of `match.rerank` (k1, k2, lambda_value, candidates): the K best are then taken from the
+    k-reciprocal re-ranked order instead of the cosine order.
     → {k: [hits, denom]}"""
     kmax = min(max(ks), emb.shape[0] - 1)
-    _, idx = cosine_topk(emb, emb, kmax, compute_dtype=compute_dtype, exclude_self=True)
+    if rerank is None:
+        _, idx = cosine_topk(emb, emb, kmax, compute_dtype=compute_dtype, exclude_self=True)
+    else:
+        _, idx = _rerank(emb, kmax, compute_dtype=compute_dtype, **dict(rerank))
     idx = idx.long()
     cls = classes.to(idx.device)
     valid = idx >= 0
@@ -657,3 +662,212 @@ def _pair_histogram_torch(emb, classes, emb_b, classes_b, bins, lo, inv_w, norma
             slot = slot[torch.arange(r0, r0 + s.shape[0])[:, None] < jb[None, :]]
         hist += torch.bincount(slot.reshape(-1), minlength=2 * (bins + 1))
     return hist.view(2, bins + 1)
+
+
+# ---- k-reciprocal re-ranking -----------------------------------------------------------------------------------------------------
+#: workspace limit of `rerank` on the device: the sparse V and V' rows take N * (E + E2) * 8 bytes
+RERANK_WORKSPACE_BUDGET = 16 << 30
+#: the CPU path is dense (an N x N fp32 matrix for V and V'): it refuses larger sets
+RERANK_CPU_MAX_ITEMS = 4096
+
+
+def rerank_row_capacity(k1, k2):
+    """(E, E2): the row lengths of the sparse V and V' rows for (k1, k2) — pfr_rerank_row_capacity of include/pfr_hip.h (host arithmetic)"""
+    e, e2 = ctypes.c_int(0), ctypes.c_int(0)
+    lib.pfr_rerank_row_capacity(int(k1), int(k2), ctypes.addressof(e), ctypes.addressof(e2))
+    return e.value, e2.value
+
+
+def _pad_lists(sc, idx, width):
+    """(scores, idx) lists cut or padded (−inf / −1) to `width` columns"""
+    sc, idx = sc[:, :width], idx[:, :width].int()
+    pad = width - sc.shape[1]
+    if pad > 0:
+        sc = torch.cat([sc, torch.full((sc.shape[0], pad), -float("inf"), dtype=sc.dtype, device=sc.device)], 1)
+        idx = torch.cat([idx, torch.full((idx.shape[0], pad), -1, dtype=torch.int32, device=idx.device)], 1)
+    return sc.float().contiguous(), idx.contiguous()
+
+
+def _unit_rows(x):
+    x32 = x.float().contiguous()
+    if x32.is_cuda and x32.shape[0]:
+        return ops.l2norm_fwd(x32, torch.float32)[0]
+    return x32 / x32.norm(dim=1, keepdim=True).clamp_min(1e-12)
+
+
+def _check_rerank_sizes(k, k1, k2, lambda_value):
+    if k > 512:
+        raise PfrError(f"rerank: k={k} exceeds the 512-entry running list of the gfx950 top-K kernels")
+    if k1 < 1 or k1 + 1 > 512:
+        raise PfrError(f"rerank: k1={k1} must be >= 1 and k1 + 1 <= 512 (the neighbour lists are running top-K lists)")
+    if k2 < 1:
+        raise PfrError(f"rerank: k2={k2} must be >= 1")
+    if not 0.0 <= float(lambda_value) <= 1.0:
+        raise PfrError(f"rerank: lambda_value={lambda_value} must be in [0, 1]")
+
+
+def rerank_inputs(emb, k, k1=20, candidates=None, emb_b=None, compute_dtype=torch.bfloat16, neighbors=None):
+    """The inputs of the re-ranking contract (include/pfr_hip.h, pfr_rerank_*) from embeddings, through `cosine_topk`:
+    → (emb32 [N, D] unit fp32 rows of the set — with emb_b the union, queries first, nbr [N, k1 + 1] int32, rows [R] int32,
+       cand [R, kc] int32 in the set's numbering, cand_cos [R, kc] fp32, offset to subtract from returned indices (0, or len(emb))).
+    The lists are those of `cosine_topk(emb32, emb32, ·, exclude_self=True, normalize=False)` — with a reduced compute_dtype re-scored exactly
+    in fp32 — so the cosines are the fp32 dot products of the rows the weights are computed from."""
+    _check_rerank_sizes(k, k1, 1, 0.0)
+    Nq = emb.shape[0]
+    X = emb if emb_b is None else torch.cat([emb.float(), emb_b.float().to(emb.device)], 0)
+    N = X.shape[0]
+    dev = X.device
+    emb32 = _unit_rows(X)
+    others = N - 1 if emb_b is None else N - Nq
+    if candidates is not None and candidates > 512:
+        raise PfrError(f"rerank: candidates={candidates} exceeds the 512-entry running list of the gfx950 top-K kernels")
+    kc = max(0, min(max(k, 100) if candidates is None else int(candidates), 512, others))
+    want = min(max(k1, kc) if emb_b is None else k1, N - 1)
+    if neighbors is not None:
+        sc, idx = neighbors
+        if sc.shape[0] != N or idx.shape != sc.shape or sc.shape[1] < want:
+            raise PfrError(f"rerank: neighbors must be the (cos, idx) lists [{N}, >= {want}] of cosine_topk(x, x, m, exclude_self=True) "
+                           f"on the whole set (queries first, then emb_b)")
+        sc, idx = sc.to(dev), idx.to(dev)
+    elif want > 0:
+        sc, idx = cosine_topk(emb32, emb32, want, compute_dtype=compute_dtype if emb32.is_cuda else torch.float32, exclude_self=True,
+                              normalize=False)
+    else:
+        sc, idx = torch.empty((N, 0), device=dev), torch.empty((N, 0), dtype=torch.int32, device=dev)
+    _, nb = _pad_lists(sc, idx, k1)
+    nbr = torch.cat([torch.arange(N, dtype=torch.int32, device=dev)[:, None], nb], 1).contiguous()
+    if emb_b is None:
+        cand_cos, cand = _pad_lists(sc, idx, kc)
+        return emb32, nbr, torch.arange(N, dtype=torch.int32, device=dev), cand, cand_cos, 0
+    if kc > 0 and Nq > 0:
+        gs, gi = cosine_topk(emb32[:Nq], emb32[Nq:], kc, compute_dtype=compute_dtype if emb32.is_cuda else torch.float32, normalize=False)
+    else:
+        gs, gi = torch.empty((Nq, 0), device=dev), torch.empty((Nq, 0), dtype=torch.int32, device=dev)
+    cand_cos, cand = _pad_lists(gs, gi, kc)
+    cand = torch.where(cand >= 0, cand + Nq, cand).contiguous()
+    return emb32, nbr, torch.arange(Nq, dtype=torch.int32, device=dev), cand, cand_cos, Nq
+
+
+def rerank_lists(emb32, nbr, rows, cand, cand_cos, k, k1=20, k2=6, lambda_value=0.3):
+    """Steps 1-4 of the re-ranking contract (include/pfr_hip.h, pfr_rerank_*) on given lists → (dist [R, k] fp32 ascending, idx [R, k] int32,
+    +inf / −1 padded).  CUDA tensors: pfr_rerank_expand → pfr_rerank_average → pfr_rerank_score with sparse rows of E and E2 = k2 · E entries
+    (`rerank_row_capacity`).  CPU tensors: a dense torch restatement for at most RERANK_CPU_MAX_ITEMS items."""
+    _check_rerank_sizes(k, k1, k2, lambda_value)
+    N, D = emb32.shape
+    R, kc = cand.shape
+    if nbr.shape != (N, k1 + 1) or cand_cos.shape != cand.shape or rows.numel() != R:
+        raise PfrError(f"rerank_lists: nbr must be [{N}, {k1 + 1}], cand and cand_cos [R, kc], rows [R]")
+    if kc > 512:
+        raise PfrError(f"rerank_lists: kc={kc} exceeds the 512-entry running list of the gfx950 top-K kernels")
+    dev = emb32.device
+    dist = torch.full((R, k), float("inf"), dtype=torch.float32, device=dev)
+    out = torch.full((R, k), -1, dtype=torch.int32, device=dev)
+    kk = min(k, kc)
+    if R == 0 or kk == 0 or N == 0:
+        return dist, out
+    if not emb32.is_cuda:
+        if N > RERANK_CPU_MAX_ITEMS:
+            raise PfrError(f"rerank: the CPU path is dense (N x N) and takes at most {RERANK_CPU_MAX_ITEMS} items, got {N}; "
+                           f"the sparse path runs on the gfx950 device")
+        d, i = _rerank_lists_torch(emb32.float(), nbr, rows, cand, cand_cos.float(), kk, k1, k2, float(lambda_value))
+        dist[:, :kk], out[:, :kk] = d, i
+        return dist, out
+    E, E2 = rerank_row_capacity(k1, k2)
+    need = N * (E + E2) * 8
+    if need > RERANK_WORKSPACE_BUDGET:
+        raise PfrError(f"rerank: the workspace N * (E + E2) * 8 = {N} * ({E} + {E2}) * 8 = {need} bytes exceeds the budget of "
+                       f"{RERANK_WORKSPACE_BUDGET} bytes (match.RERANK_WORKSPACE_BUDGET); lower k1 / k2 or split the set")
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+    e32, nbr, rows, cand = emb32.float().contiguous(), i32(nbr), i32(rows), i32(cand)
+    cand_cos = cand_cos.to(device=dev, dtype=torch.float32).contiguous()
+    v_idx = torch.empty((N, E), dtype=torch.int32, device=dev)
+    v_val = torch.empty((N, E), dtype=torch.float32, device=dev)
+    q_idx = torch.empty((N, E2), dtype=torch.int32, device=dev)
+    q_val = torch.empty((N, E2), dtype=torch.float32, device=dev)
+    v_cnt = torch.empty(N, dtype=torch.int32, device=dev)
+    q_cnt = torch.empty(N, dtype=torch.int32, device=dev)
+    lib.pfr_rerank_expand(e32.data_ptr(), N, D, nbr.data_ptr(), k1, v_idx.data_ptr(), v_val.data_ptr(), v_cnt.data_ptr(), E, _stream())
+    lib.pfr_rerank_average(nbr.data_ptr(), N, k1, k2, v_idx.data_ptr(), v_val.data_ptr(), v_cnt.data_ptr(), E, q_idx.data_ptr(),
+                           q_val.data_ptr(), q_cnt.data_ptr(), E2, _stream())
+    d = torch.empty((R, kk), dtype=torch.float32, device=dev)
+    i = torch.empty((R, kk), dtype=torch.int32, device=dev)
+    lib.pfr_rerank_score(q_idx.data_ptr(), q_val.data_ptr(), q_cnt.data_ptr(), N, E2, rows.data_ptr(), R, cand.data_ptr(), cand_cos.data_ptr(),
+                         kc, float(lambda_value), kk, d.data_ptr(), i.data_ptr(), _stream())
+    if kk == k:
+        return d, i
+    dist[:, :kk], out[:, :kk] = d, i
+    return dist, out
+
+
+def _rerank_lists_torch(emb32, nbr, rows, cand, cand_cos, k, k1, k2, lam):
+    """dense CPU form of the contract in matrix algebra: membership, R, R*, V and V' as N x N matrices (no per-item set logic)"""
+    N, K1 = emb32.shape[0], nbr.shape[1]
+    kh = round(k1 / 2)
+    nb = nbr.long()
+    valid = (nb >= 0) & (nb < N)
+    rank = valid.cumsum(1) - 1                                     # position among the valid entries of the row
+    row_of = torch.arange(N)[:, None].expand_as(nb)
+
+    def member(width):                                             # A[i, j] = j is among the first `width` valid entries of nbr[i]
+        A = torch.zeros((N, N), dtype=torch.bool)
+        sel = valid & (rank < width)
+        A[row_of[sel], nb[sel]] = True
+        return A
+    A1, Ah = member(k1 + 1), member(kh + 1)
+    B1, Bh = A1 & A1.t(), Ah & Ah.t()                              # R(i, k1) and R(i, kh) as rows; both symmetric
+    B1f, Bhf = B1.float(), Bh.float()
+    inter = B1f @ Bhf                                              # [i, j] = |R(i, k1) ∩ R(j, kh)|  (small integers: exact)
+    accept = B1 & (3 * inter > 2 * Bhf.sum(0)[None, :])
+    Rs = B1 | ((accept.float() @ Bhf) > 0)
+    W = torch.where(Rs, torch.exp(-(2 - 2 * (emb32 @ emb32.t()))), torch.zeros(()))
+    V = W / W.sum(1, keepdim=True).clamp_min(1e-30)
+    sel = valid & (rank < k2)
+    Vq = torch.zeros_like(V)
+    for t in range(K1):                                            # (in list order, as the kernel sums)
+        s = sel[:, t]
+        if bool(s.any()):
+            Vq[s] += V[nb[s, t]]
+    Vq /= sel.sum(1).clamp_min(1)[:, None]
+    R, kc = cand.shape
+    rw, c = rows.long(), cand.long()
+    ok = (c >= 0) & (c < N) & ((rw >= 0) & (rw < N))[:, None]
+    rw, cc = rw.clamp(0, N - 1), c.clamp(0, N - 1)
+    dist = torch.empty((R, k), dtype=torch.float32)
+    idx = torch.empty((R, k), dtype=torch.int32)
+    step = max(1, (1 << 24) // max(1, kc * N))
+    for r0 in range(0, R, step):
+        r1 = min(R, r0 + step)
+        m = torch.minimum(Vq[rw[r0:r1], None, :], Vq[cc[r0:r1]]).sum(2)
+        fin = (1 - lam) * (1 - m / (2 - m)) + lam * (2 - 2 * cand_cos[r0:r1])
+        fin = torch.where(ok[r0:r1], fin, torch.full_like(fin, float("inf")))
+        order = torch.argsort(fin, dim=1, stable=True)[:, :k]
+        dist[r0:r1] = torch.gather(fin, 1, order)
+        idx[r0:r1] = torch.where(torch.gather(ok[r0:r1], 1, order), torch.gather(c[r0:r1], 1, order), torch.full_like(order, -1)).int()
+    return dist, idx
+
+
+def rerank(emb, k, k1=20, k2=6, lambda_value=0.3, candidates=None, emb_b=None, compute_dtype=torch.bfloat16, neighbors=None):
+    """k-reciprocal re-ranking (Zhong et al., CVPR 2017) of the cosine match lists → (dist [R, k] fp32 ascending, idx [R, k] int32; +inf / −1
+    padded when fewer than k candidates exist).  dist = (1 − lambda_value) · Jaccard distance of the expanded k-reciprocal neighbour
+    encodings + lambda_value · (2 − 2 cos); the exact contract is the comment at pfr_rerank_* in include/pfr_hip.h.
+    One set (`emb` [N, D]): all-vs-all, self excluded from the candidates, as in `recall_at_k`.
+    With `emb_b` (the gallery): the set is the union, queries first; the output rows are the queries, the candidates each query's
+    top-`candidates` gallery rows, and idx is in gallery numbering.
+    candidates (default max(k, 100), capped at 512 and at the number of other items): ONLY these are re-ranked.  This equals re-ranking every
+    item only when the list covers every other item: an item outside the list that shares neighbours with the query (non-zero overlap)
+    could otherwise enter the top k.
+    neighbors = (cos, idx): the `cosine_topk(x, x, m, exclude_self=True)` lists of the whole set already computed (m >= k1, and in the
+    one-set form m >= candidates: they provide the candidates too).  compute_dtype is passed to `cosine_topk`, whose lists are re-scored
+    exactly in fp32.
+    Deviation from the published code: its division of the distance matrix by the per-column maximum needs the N x N matrix and is dropped.
+    CUDA tensors run the sparse gfx950 kernels (workspace N · (E + E2) · 8 bytes, limited by RERANK_WORKSPACE_BUDGET); CPU tensors a dense
+    torch form for at most RERANK_CPU_MAX_ITEMS items."""
+    _check_rerank_sizes(k, k1, k2, lambda_value)
+    emb32, nbr, rows, cand, cand_cos, off = rerank_inputs(emb, k, k1, candidates, emb_b, compute_dtype, neighbors)
+    dist, idx = rerank_lists(emb32, nbr, rows, cand, cand_cos, k, k1, k2, lambda_value)
+    if off:
+        idx = torch.where(idx >= 0, idx - off, idx)
+    return dist, idx
+
+
+_rerank = rerank      # (recall_at_k has a parameter of this name)
