@@ -598,6 +598,44 @@ int pfr_rerank_score(const int* q_idx, const float* q_val, const int* q_cnt, int
 int pfr_card_centroids(const float* emb, const long* seg, int ncards, int D, float eps, float* cent32, void* cent,
                        int cent_dtype, pfr_stream_t stream);
 
+/* ---- max-strategy card matching (generate_tsv.py:81-88): the score of a card pair is the BEST photo pair.  The photo x photo score
+ * GEMM of the match with a segmented-max epilogue over ragged card boundaries on both tile axes; nothing photo-matrix-sized is written.
+ * Cards are photo rows q [Pq][D], g [Pg][D] (unit-normalised by the caller) with int64 row offsets seg [ncards+1]; an empty range is a
+ * card without photos, allowed anywhere (consecutively and at both ends included).
+ *
+ * pfr_card_tiles (host only, no device needed): packs WHOLE cards greedily, in order, into tiles of at most 128 photo rows.
+ *   tiles [cap][4] int32 records: first card, card count, first row (= seg[first card]), row count.  Returns the number of tiles; with
+ *   tiles == NULL nothing is written (size query), a second call with cap >= that number fills the records (cap too small: PFR_ERR_ARG).
+ *   A non-empty card opens a new tile when it does not fit the open one.  Empty cards belong to the tile of the NEXT non-empty card,
+ *   trailing empty cards to the last tile; a table of only empty cards is one tile of 0 rows; ncards == 0 gives 0 tiles.  Every card
+ *   belongs to exactly one tile, the rows of a tile are contiguous, and so every output element below is written by exactly one workgroup
+ *   with a plain store.  A card above 128 photos returns PFR_ERR_UNSUPPORTED (the message names the card), decreasing offsets, a negative
+ *   seg[0] or more than 2^31 - 1 rows PFR_ERR_ARG.
+ *
+ * pfr_card_max_scores: q, g rows of `dtype` PFR_F32 / PFR_BF16 with the D multiples of pfr_pair_hist (128-byte k-steps: D % 32 == 0 /
+ *   D % 64 == 0).  q_seg / g_seg and the records q_tiles [n_qtiles][4] / g_tiles [n_gtiles][4] of pfr_card_tiles in DEVICE memory; Pq, Pg =
+ *   photo rows, Qcards = query cards.  The records carry absolute card and row numbers: g_tiles may point into the middle of the gallery's
+ *   table, at the first tile that holds a card of the window, with n_gtiles covering the last such tile (a chunked caller visits only the
+ *   tiles of its chunk; records outside the window are skipped).
+ *     out [Qcards][ld] fp32:  out[i][j - col0] = max over photos a of query card i, b of gallery card j of <q_a, g_b>
+ *   for every query card i of the q tiles given and every gallery card j in [col0, col0 + n) that lies in a g tile given; each product is
+ *   the fp32 accumulator of the MFMA; -inf when either card has no photos.  Elements outside the window are not touched (ld >= n).
+ *   Tile rows past a tile's row count never enter a maximum.  Max is exactly associative and commutative and there are no floating-point
+ *   atomics: the result is bit-identical between calls and independent of the tiling.  The kernel trusts the records to describe the
+ *   offsets (it clamps every address derived from them, a mismatch gives wrong maxima, never an access outside q, g or out's rows).
+ *
+ * pfr_card_max_rescore: exact fp32 maxima of listed pairs.  q, g fp32 unit rows (D % 4 == 0, 16-byte aligned), cand [Q][kc] int32 gallery
+ *   cards (kc <= 512; an entry outside [0, Gcards) is padding) -> out [Q][kc] fp32 = the max dot of (query card r, cand[r][t]), -inf for
+ *   padding or an empty card.  One wave per pair; every dot product is accumulated from the rows in the fixed k order of the fp32 path of
+ *   pfr_card_max_scores, so on fp32 rows the two give the same bits.
+ * Argument errors (null or host pointers, bad dtype / D / window) return PFR_ERR_ARG and launch nothing. */
+long pfr_card_tiles(const long* seg, int ncards, int* tiles, int cap);
+int pfr_card_max_scores(const void* q, const long* q_seg, const int* q_tiles, int n_qtiles, int Pq, int Qcards, const void* g,
+                        const long* g_seg, const int* g_tiles, int n_gtiles, int Pg, int dtype, int D, int col0, int n, float* out, int ld,
+                        pfr_stream_t stream);
+int pfr_card_max_rescore(const float* q, const long* q_seg, int Q, const float* g, const long* g_seg, int Gcards, int D, const int* cand,
+                         int kc, float* out, pfr_stream_t stream);
+
 /* head/body fusion of the inference ranking (generate_tsv.py:91-110), in place over `head_scores`.  head_scores,
  * body_scores: fp32 [rows][ld] centroid dot products of a query-card block against gallery cards col0..col0+n.
  * q_flags [rows], g_flags [all gallery cards] (indexed col0 + j): bit 0 = card has head vectors, bit 1 = has body

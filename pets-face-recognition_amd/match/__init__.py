@@ -397,11 +397,207 @@ def card_centroids(emb, seg, compute_dtype=torch.float32):
     return out
 
 
-def card_match(q_emb, q_seg, g_emb, g_seg, k=100, compute_dtype=torch.bfloat16):
-    """Mean-strategy card-vs-card ranking of the reference's inference pipeline (generate_tsv.py:71-78, 91-125, one
-    modality): score(card_q, card_g) = clamp(mean over photo pairs of (cos+1)/2, min=0); → (scores [Q,k], idx [Q,k]),
-    best first.  The mean over the photo cross product equals (⟨centroid_q, centroid_g⟩ + 1)/2, so this is ONE GEMM of
-    card centroids with the running top-k."""
+#: photo rows of one tile of the max-strategy kernel: a card with more photos is refused (pfr_card_tiles, include/pfr_hip.h)
+CARD_MAX_PHOTOS = 128
+_STRATEGIES = ("mean", "max")
+
+
+def _check_strategy(strategy, who):
+    if strategy not in _STRATEGIES:
+        raise PfrError(f"{who}: unknown strategy {strategy!r}, expected one of {_STRATEGIES}")
+
+
+def _card_seg(seg, who):
+    """int64 [ncards+1] row offsets on the host, checked: non-decreasing, no card above CARD_MAX_PHOTOS photos"""
+    seg = torch.as_tensor(seg, dtype=torch.int64).cpu().contiguous()
+    if seg.dim() != 1 or seg.numel() < 1:
+        raise PfrError(f"{who}: seg must hold ncards+1 row offsets")
+    n = seg[1:] - seg[:-1]
+    if n.numel() and int(n.min()) < 0:
+        raise PfrError(f"{who}: row offsets decrease at card {int((n < 0).nonzero()[0])}")
+    if n.numel() and int(n.max()) > CARD_MAX_PHOTOS:
+        c = int((n > CARD_MAX_PHOTOS).nonzero()[0])
+        raise PfrError(f"{who}: card {c} has {int(n[c])} photos, the max strategy takes at most {CARD_MAX_PHOTOS} per card")
+    return seg
+
+
+def card_tiles(seg):
+    """The tile table of pfr_card_tiles (include/pfr_hip.h) for row offsets seg [ncards+1]: whole cards packed greedily into tiles of at
+    most 128 photo rows → int32 [ntiles, 4] host records (first card, card count, first row, row count).  Host arithmetic, no device."""
+    seg = torch.as_tensor(seg, dtype=torch.int64).cpu().contiguous()
+    if seg.dim() != 1 or seg.numel() < 1:
+        raise PfrError("card_tiles: seg must hold ncards+1 row offsets")
+    n = seg.numel() - 1
+    nt = lib.pfr_card_tiles(seg.data_ptr(), n, 0, 0)                   # size query, then fill
+    tiles = torch.empty((max(int(nt), 0), 4), dtype=torch.int32)
+    if nt > 0:
+        nt = lib.pfr_card_tiles(seg.data_ptr(), n, tiles.data_ptr(), int(nt))
+    if nt < 0:
+        raise PfrError(f"pfr_card_tiles failed (rc={int(nt)}): {lib.pfr_last_error().decode()}")
+    return tiles
+
+
+class _CardSide:
+    """one side (query or gallery cards) of the max-strategy kernels on the device: GEMM operand, fp32 rows, offsets and tile table"""
+
+    def __init__(self, emb, seg, T, dev, rescore, who):
+        self.seg_h = _card_seg(seg, who)
+        self.ncards = self.seg_h.numel() - 1
+        x32 = emb.to(dev).float().contiguous()
+        if x32.dim() != 2 or x32.shape[0] < int(self.seg_h[-1]):
+            raise PfrError(f"{who}: emb must be [P, D] with P >= seg[-1] photo rows")
+        self.P, self.D = x32.shape
+        if self.P:
+            xn, _ = _prep_rows(x32, T, False, True)
+            # the fp32 rows of the re-scoring are the fp32 path's own operand rows (the same normalising kernel), so that the scores
+            # card_match returns with bf16 are bit for bit the ones it returns with fp32
+            xf = None if not rescore else (xn if T == torch.float32 else _prep_rows(x32, torch.float32, False, True)[0])
+        else:
+            xn, xf = x32.to(T), (x32 if rescore else None)
+        self.op = _pad_cols(xn.contiguous(), 32 if T == torch.float32 else 64)
+        self.x32 = None if xf is None else _pad_cols(xf.contiguous(), 4)
+        self.tiles_h = card_tiles(self.seg_h)
+        self.first = self.tiles_h[:, 0].long().contiguous()     # first card of every tile (ascending)
+        self.seg = self.seg_h.to(dev)
+        self.tiles = self.tiles_h.to(dev)
+
+    def tile_range(self, c0, n):
+        """tiles that hold the cards [c0, c0 + n)"""
+        t0 = int(torch.searchsorted(self.first, torch.tensor(c0), right=True)) - 1
+        t1 = int(torch.searchsorted(self.first, torch.tensor(c0 + n - 1), right=True))
+        return max(t0, 0), t1
+
+
+def _card_max_chunk(qs, gs, T, c0, n, out, ld):
+    """out [Q][ld] (n valid columns) = max dots of every query card against the gallery cards [c0, c0 + n)"""
+    if qs.P == 0 or gs.P == 0:          # no photo on one side: every pair is −inf (and there may be no D to speak of)
+        out.view(-1, ld)[:, :n] = -float("inf")
+        return
+    t0, t1 = gs.tile_range(c0, n)
+    lib.pfr_card_max_scores(qs.op.data_ptr(), qs.seg.data_ptr(), qs.tiles.data_ptr(), qs.tiles_h.shape[0], qs.P, qs.ncards,
+                            gs.op.data_ptr(), gs.seg.data_ptr(), gs.tiles.data_ptr() + 16 * t0, t1 - t0, gs.P, dtype_id(T), qs.op.shape[1],
+                            c0, n, out.data_ptr(), ld, _stream())
+
+
+def _card_max_dtype(compute_dtype, who):
+    if compute_dtype not in (torch.float32, torch.bfloat16):
+        raise PfrError(f"{who}: compute_dtype must be torch.float32 or torch.bfloat16")
+
+
+def card_max_scores(q_emb, q_seg, g_emb, g_seg, compute_dtype=torch.float32):
+    """Max-strategy card scores before the (x + 1) / 2 map (generate_tsv.py:81-88): → fp32 [Q, G], element (i, j) = the largest dot product
+    of a unit-normalised photo row of query card i with one of gallery card j; −inf when either card has no photos.
+    q_emb [Pq, D], g_emb [Pg, D] photo embeddings (any scale), q_seg [Q+1], g_seg [G+1] row offsets; at most CARD_MAX_PHOTOS photos per card.
+    CUDA tensors: ONE pfr_card_max_scores launch — the photo GEMM in compute_dtype with a segmented-max epilogue, the photo x photo score
+    matrix is never written.  CPU tensors: chunked fp32 matmul with the same definition."""
+    _card_max_dtype(compute_dtype, "card_max_scores")
+    if q_emb.dim() != 2 or g_emb.dim() != 2 or (q_emb.shape[0] and g_emb.shape[0] and q_emb.shape[1] != g_emb.shape[1]):
+        raise PfrError("card_max_scores: q_emb [Pq, D] and g_emb [Pg, D]")
+    if not q_emb.is_cuda:
+        return _card_max_scores_torch(q_emb, _card_seg(q_seg, "card_max_scores"), g_emb, _card_seg(g_seg, "card_max_scores"))
+    dev = q_emb.device
+    qs = _CardSide(q_emb, q_seg, compute_dtype, dev, False, "card_max_scores")
+    gs = _CardSide(g_emb, g_seg, compute_dtype, dev, False, "card_max_scores")
+    Q, G = qs.ncards, gs.ncards
+    ld = (G + 3) // 4 * 4
+    out = torch.empty((Q, ld), dtype=torch.float32, device=dev)
+    if Q and G:
+        _card_max_chunk(qs, gs, compute_dtype, 0, G, out, ld)
+    return out[:, :G] if ld == G else out[:, :G].contiguous()
+
+
+def _card_max_scores_torch(q_emb, q_seg, g_emb, g_seg, chunk=2048):
+    """CPU form of card_max_scores: photo scores of `chunk` query rows at a time, max over the columns of every gallery card, then over
+    the rows of every query card"""
+    unit = lambda x: x.float() / x.float().norm(dim=1, keepdim=True).clamp_min(1e-12)
+    Q, G = q_seg.numel() - 1, g_seg.numel() - 1
+    out = torch.full((Q, G), -float("inf"))
+    Pq, Pg = int(q_seg[-1]), int(g_seg[-1])
+    if Q == 0 or G == 0 or Pq == 0 or Pg == 0:
+        return out
+    q, g = unit(q_emb[:Pq]), unit(g_emb[:Pg])
+    qcard = torch.repeat_interleave(torch.arange(Q), q_seg[1:] - q_seg[:-1])
+    gcard = torch.repeat_interleave(torch.arange(G), g_seg[1:] - g_seg[:-1])
+    base = int(q_seg[0]), int(g_seg[0])
+    q, g = q[base[0]:], g[base[1]:]
+    for r0 in range(0, q.shape[0], chunk):
+        s = q[r0:r0 + chunk] @ g.t()
+        cols = torch.full((s.shape[0], G), -float("inf")).scatter_reduce_(1, gcard[None, :].expand(s.shape[0], -1), s, "amax")
+        out.scatter_reduce_(0, qcard[r0:r0 + chunk, None].expand(-1, G), cols, "amax")
+    return out
+
+
+def _max_scores_to_similarity(dots):
+    """(x + 1) / 2 clamped at 0; a pair without photos (−inf) stays −inf"""
+    return torch.where(torch.isinf(dots) & (dots < 0), dots, ((dots + 1) / 2).clamp_min(0))
+
+
+def _card_match_max(q_emb, q_seg, g_emb, g_seg, k, T, chunk):
+    _card_max_dtype(T, "card_match")
+    if not q_emb.is_cuda:
+        dots = card_max_scores(q_emb, q_seg, g_emb, g_seg)
+        kk = min(k, dots.shape[1])
+        order = torch.argsort(dots, dim=1, descending=True, stable=True)[:, :kk]
+        top = _max_scores_to_similarity(torch.gather(dots, 1, order))
+        sc = torch.full((dots.shape[0], k), -float("inf"))          # [Q, k] as on the device: −inf / −1 past the candidates
+        idx = torch.full((dots.shape[0], k), -1, dtype=torch.int32)
+        sc[:, :kk] = top
+        idx[:, :kk] = torch.where(torch.isinf(top), torch.full_like(order, -1), order).int()
+        return sc, idx
+    if k > 512:
+        raise PfrError(f"card_match: k={k} exceeds the 512-entry running list of the gfx950 top-K kernels")
+    dev = q_emb.device
+    rescore = T != torch.float32
+    kc = min(512, k + max(28, k + k // 2)) if rescore else k
+    qs = _CardSide(q_emb, q_seg, T, dev, rescore, "card_match")
+    gs = _CardSide(g_emb, g_seg, T, dev, rescore, "card_match")
+    Q, G = qs.ncards, gs.ncards
+    sc = torch.full((Q, k), -float("inf"), dtype=torch.float32, device=dev)
+    idx = torch.full((Q, k), -1, dtype=torch.int32, device=dev)
+    if Q == 0 or G == 0:
+        return sc, idx
+    chunk = min(chunk, G)
+    ld = (chunk + 3) // 4 * 4
+    sbuf = torch.empty((Q, ld), dtype=torch.float32, device=dev)
+    state = torch.empty(lib.pfr_topk_state_bytes(Q, kc), dtype=torch.uint8, device=dev)
+    lib.pfr_topk_reset(state.data_ptr(), Q, kc, _stream())
+    for c0 in range(0, G, chunk):
+        n = min(chunk, G - c0)
+        _card_max_chunk(qs, gs, T, c0, n, sbuf, ld)
+        lib.pfr_topk_update(sbuf.data_ptr(), Q, ld, n, c0, kc, state.data_ptr(), 0, _stream())
+    dots = torch.empty((Q, kc), dtype=torch.float32, device=dev)
+    cand = torch.empty((Q, kc), dtype=torch.int32, device=dev)
+    lib.pfr_topk_finish(state.data_ptr(), Q, kc, dots.data_ptr(), cand.data_ptr(), _stream())
+    if rescore:
+        # exact fp32 maxima of the candidates, then score descending with ties to the lower card index
+        lib.pfr_card_max_rescore(qs.x32.data_ptr(), qs.seg.data_ptr(), Q, gs.x32.data_ptr(), gs.seg.data_ptr(), G, qs.x32.shape[1],
+                                 cand.data_ptr(), kc, dots.data_ptr(), _stream())
+        by_idx = torch.argsort(torch.where(cand >= 0, cand, torch.full_like(cand, 2 ** 31 - 1)), dim=1, stable=True)
+        dots, cand = torch.gather(dots, 1, by_idx), torch.gather(cand, 1, by_idx)
+        order = torch.argsort(dots, dim=1, descending=True, stable=True)
+        dots, cand = torch.gather(dots, 1, order), torch.gather(cand, 1, order)
+    kk = min(k, kc)
+    sc[:, :kk] = _max_scores_to_similarity(dots[:, :kk])
+    idx[:, :kk] = torch.where(torch.isinf(sc[:, :kk]), torch.full_like(cand[:, :kk], -1), cand[:, :kk])
+    return sc, idx
+
+
+def card_match(q_emb, q_seg, g_emb, g_seg, k=100, compute_dtype=torch.bfloat16, strategy="mean", chunk=131072):
+    """Card-vs-card ranking of the reference's inference pipeline (generate_tsv.py:71-88, 91-125, one modality); → (scores [Q,k],
+    idx [Q,k]), best first.
+    strategy='mean' (generate_tsv.py:71-78): score(card_q, card_g) = clamp(mean over photo pairs of (cos+1)/2, min=0).  The mean over the
+    photo cross product equals (⟨centroid_q, centroid_g⟩ + 1)/2, so this is ONE GEMM of card centroids with the running top-k.
+    strategy='max' (generate_tsv.py:81-88): score = clamp((maxdot + 1) / 2, min=0) with maxdot the best photo pair's cosine
+    (`card_max_scores`).  (x + 1) / 2 is monotone under rounding, so this is the reference's max over pairs of (cos+1)/2; the clamp differs
+    from the reference (which does not clamp the max) only where rounding puts a cosine below −1.  A gallery card without photos — or
+    every card, for a query card without photos — is no candidate: −inf / −1 at the end of the list.  On the device pfr_card_max_scores
+    runs per chunk of `chunk` gallery cards into the running top-k (k <= 512).  torch.float32 is exact.  torch.bfloat16 selects
+    kc = min(512, k + max(28, k + k // 2)) cards on bf16-input scores, re-scores them exactly in fp32 (pfr_card_max_rescore), re-sorts with
+    ties to the lower index and keeps k: the returned scores are fp32 scores, but the selection is NOT certified — unlike `cosine_topk`,
+    nothing checks that no card outside the kc candidates belongs to the exact top k."""
+    _check_strategy(strategy, "card_match")
+    if strategy == "max":
+        return _card_match_max(q_emb, q_seg, g_emb, g_seg, k, compute_dtype, chunk)
     qc = card_centroids(q_emb, q_seg)
     gc = card_centroids(g_emb, g_seg)
     dots, idx = cosine_topk(qc, gc, k, compute_dtype=compute_dtype, normalize=False)
@@ -425,7 +621,7 @@ def _card_flags(head_seg, body_seg, types, device):
 
 
 def calc_scores(q_head, q_head_seg, q_body, q_body_seg, q_type, g_head, g_head_seg, g_body, g_body_seg, g_type, k=100,
-                thresholds=FUSION_THRESHOLDS, chunk=32768):
+                thresholds=FUSION_THRESHOLDS, chunk=32768, strategy="mean"):
     """Card-vs-card ranking of the reference's inference pipeline WITH its head/body fusion rule
     (generate_tsv.py:91-125 `calc_scores`), on the device.
 
@@ -442,9 +638,13 @@ def calc_scores(q_head, q_head_seg, q_body, q_body_seg, q_type, g_head, g_head_s
     The mean over the photo cross product of (cos+1)/2 is (⟨centroid_q, centroid_g⟩ + 1)/2, so each modality is one fp32
     GEMM of card centroids per gallery chunk; `pfr_card_fuse_scores` applies the rule in place and the running top-k
     kernel keeps the best k.  Ties → lower gallery index (Python's stable `sorted(reverse=True)` keeps dict order).
+    strategy='max': s0 and s1 are the max-strategy scores instead (generate_tsv.py:81-88 in place of :71-78) — the two per-modality score
+    chunks come from pfr_card_max_scores in fp32 instead of the centroid GEMM; the rule, the flags, the thresholds and the top-k are the
+    same.  Its −inf entries (a card without photos of that modality) are exactly the pairs whose flags already zero the modality score.
     → dict(scores [Q,k] fp32, idx [Q,k] int32 (−1 past the end of a short list), count [Q], top1, mean3, mean10 [Q] fp64).
     A query with count 0 gets no row in the reference; with fewer than 3 / 10 entries the reference raises IndexError,
     here the available ones are averaged."""
+    _check_strategy(strategy, "calc_scores")
     dev = q_head.device if q_head.numel() else q_body.device
     if dev.type != "cuda":
         raise PfrError("calc_scores runs on the gfx950 device only (tests use oracle/match_ref.py as the CPU checker)")
@@ -461,8 +661,17 @@ def calc_scores(q_head, q_head_seg, q_body, q_body_seg, q_type, g_head, g_head_s
             return None
         return card_centroids(emb.to(dev), seg)
 
-    qc = (cents(q_head, q_head_seg, Q), cents(q_body, q_body_seg, Q))
-    gc = (cents(g_head, g_head_seg, G), cents(g_body, g_body_seg, G))
+    def side(emb, seg, n):
+        if emb.numel() == 0:
+            return None
+        return _CardSide(emb, seg, torch.float32, dev, False, "calc_scores")
+
+    if strategy == "max":
+        qc = (side(q_head, q_head_seg, Q), side(q_body, q_body_seg, Q))
+        gc = (side(g_head, g_head_seg, G), side(g_body, g_body_seg, G))
+    else:
+        qc = (cents(q_head, q_head_seg, Q), cents(q_body, q_body_seg, Q))
+        gc = (cents(g_head, g_head_seg, G), cents(g_body, g_body_seg, G))
     chunk = min(chunk, G)
     ld = (chunk + 3) // 4 * 4
     sb = [torch.zeros((Q, 1, 1, ld), dtype=torch.float32, device=dev) for _ in range(2)]
@@ -472,7 +681,11 @@ def calc_scores(q_head, q_head_seg, q_body, q_body_seg, q_type, g_head, g_head_s
     for c0 in range(0, G, chunk):
         n = min(chunk, G - c0)
         for m in range(2):
-            if qc[m] is not None and gc[m] is not None:   # a modality nobody has stays 0 and is masked by the flags
+            if qc[m] is None or gc[m] is None:            # a modality nobody has stays 0 and is masked by the flags
+                continue
+            if strategy == "max":
+                _card_max_chunk(qc[m], gc[m], torch.float32, c0, n, sb[m], ld)
+            else:
                 D = qc[m].shape[1]
                 ops.conv2d_fwd(qc[m].view(Q, 1, 1, D), gc[m][c0:c0 + n].view(n, 1, 1, D), out=sb[m])
         lib.pfr_card_fuse_scores(sb[0].data_ptr(), sb[1].data_ptr(), Q, ld, n, c0, qf.data_ptr(), gf.data_ptr(),
@@ -493,11 +706,13 @@ def calc_scores(q_head, q_head_seg, q_body, q_body_seg, q_type, g_head, g_head_s
     return {"scores": sc, "idx": idx, "count": count, "top1": s64[:, 0], "mean3": mean_first(3), "mean10": mean_first(10)}
 
 
-def calc_scores_db(init_db, extra_db, device="cuda", k=100, thresholds=FUSION_THRESHOLDS):
+def calc_scores_db(init_db, extra_db, device="cuda", k=100, thresholds=FUSION_THRESHOLDS, strategy="mean"):
     """`calc_scores(init_db, extra_db)` with the reference's own argument and return types (generate_tsv.py:91-125):
     both dbs map a card path to {'head_vectors': [tensor], 'body_vectors': [tensor], 'type': int}; → list of
-    (query name, top-1 score, mean of best 3, mean of best 10, ','-joined names of the best `k` gallery cards)."""
+    (query name, top-1 score, mean of best 3, mean of best 10, ','-joined names of the best `k` gallery cards).
+    strategy: 'mean' or 'max', as in `calc_scores`."""
     from pathlib import Path
+    _check_strategy(strategy, "calc_scores_db")
 
     def pack(db):
         names, types, head, body, hs, bs = [], [], [], [], [0], [0]
@@ -515,7 +730,7 @@ def calc_scores_db(init_db, extra_db, device="cuda", k=100, thresholds=FUSION_TH
     gn, gh, ghs, gb, gbs, gt = pack(extra_db)
     if not qn or not gn:
         return []
-    r = calc_scores(qh, qhs, qb, qbs, qt, gh, ghs, gb, gbs, gt, k=k, thresholds=thresholds)
+    r = calc_scores(qh, qhs, qb, qbs, qt, gh, ghs, gb, gbs, gt, k=k, thresholds=thresholds, strategy=strategy)
     idx, cnt = r["idx"].cpu(), r["count"].cpu()
     top1, m3, m10 = r["top1"].cpu(), r["mean3"].cpu(), r["mean10"].cpu()
     rows = []
@@ -530,15 +745,17 @@ def calc_scores_db(init_db, extra_db, device="cuda", k=100, thresholds=FUSION_TH
 TSV_COLUMNS = ('query', 'matched_1', 'matched_3', 'matched_10', 'answer')     # generate_tsv.py:129-135
 
 
-def create_table(db, device="cuda", k=100):
+def create_table(db, device="cuda", k=100, strategy="mean"):
     """`create_table(db)` of the reference (generate_tsv.py:128-142): db maps a folder to (initial_base_dict, extra_base_dict);
     every folder's cards are ranked on the device (calc_scores_db) and the rows are collected into one DataFrame with the
-    reference's columns.  `create_table(db).to_csv(path, index=False, sep='\t')` is its TSV (generate_tsv.py:262-264)."""
+    reference's columns.  `create_table(db).to_csv(path, index=False, sep='\t')` is its TSV (generate_tsv.py:262-264).
+    strategy: 'mean' or 'max', as in `calc_scores`."""
+    _check_strategy(strategy, "create_table")
     import pandas as pd
     rows = []
     for big_folder in db:
         init_db, extra_db = db[big_folder]
-        rows.extend(calc_scores_db(init_db, extra_db, device=device, k=k))
+        rows.extend(calc_scores_db(init_db, extra_db, device=device, k=k, strategy=strategy))
     return pd.DataFrame(data=rows, columns=TSV_COLUMNS)
 
 
