@@ -31,10 +31,15 @@ def main(argv=None):
     ap.add_argument('--rerank', nargs=3, default=None, metavar=('K1', 'K2', 'LAMBDA'),
                     help="also report 'Rerank Recall@K=…': Recall@K of the k-reciprocal re-ranked match lists (match.rerank), "
                          'e.g. 20 6 0.3')
+    ap.add_argument('--retrieval', type=int, nargs='*', default=None, metavar='K',
+                    help="also report the retrieval metrics 'mAP', 'mINP', 'CMC@K=…' and 'Mean first rank' from the exact rank of every "
+                         'positive (match.positive_ranks); the CMC ranks K default to 1 5 10')
     args = ap.parse_args(argv)
     config = get_config(args.config)
     if args.rerank is not None:
         config['rerank'] = dict(k1=int(args.rerank[0]), k2=int(args.rerank[1]), lambda_value=float(args.rerank[2]))
+    if args.retrieval is not None:
+        config['retrieval'] = dict(ks=list(args.retrieval) or [1, 5, 10])
     if args.all_pairs_far is not None:
         config['all_pairs_far'] = list(args.all_pairs_far)
     controller = Controller(config)

@@ -551,6 +551,40 @@ int pfr_pair_curve(const float* scores, const int* labels, int P, void* workspac
 int pfr_pair_hist(const void* a, const float* a_scale, const int* a_cls, int Na, const void* b, const float* b_scale, const int* b_cls,
                   int Nb, int dtype, int D, float lo, float inv_w, int bins, unsigned long long* hist, pfr_stream_t stream);
 
+/* ---- exact retrieval ranks (mAP / CMC / mINP): the match GEMM with a RANK-COUNTING epilogue.  The rank of a positive is the number of
+ * items that precede it, so it is counted where the MFMA leaves the scores; nothing Na x Nb is written and nothing is sorted.
+ *   Scores.  a [Na][D], b [Nb][D], a_scale, b_scale, dtype, D: the operands, layouts and D multiples of pfr_pair_hist, and its score
+ *     s(i, j): the fp32 accumulator (PFR_F32, PFR_BF16), or ((float) acc * a_scale[i]) * b_scale[j] (PFR_I8).  b == NULL means b = a
+ *     (b_scale and Nb are then ignored; b_id is still the ids of those rows).
+ *   Order.  Every b row carries a tie-break key b_id[j] (int32; a wrapper passes the caller's original index).  Item (s, id) PRECEDES
+ *     threshold (t, tid) iff  s > t || (s == t && id < tid)  — the order of a stable descending argsort over the original indices.  The
+ *     comparisons are IEEE: a NaN score precedes nothing and nothing precedes a NaN threshold.
+ *   Thresholds and counts.  Per row i the thresholds thr_val[i][k] (fp32), thr_id[i][k] (int32) for k < thr_cnt[i] (int32 [Na], values
+ *     outside [0, ld] are clamped), row stride ld, in any order:
+ *       cnt[i][k] += #{ j in [0, Nb) : b_id[j] != excl[i] and (s(i, j), b_id[j]) precedes (thr_val[i][k], thr_id[i][k]) }
+ *     excl int32 [Na], or NULL for no exclusion (a symmetric wrapper passes the query's own id: a query never ranks itself).
+ *     cnt uint32 [Na][ld]; slots k >= thr_cnt[i] are not touched.  The call ADDS (chunked and sharded callers accumulate into one table;
+ *     the caller zeroes it).  Integer adds only: two calls on the same inputs give the same bits.  Na == 0, Nb == 0 or ld == 0 adds
+ *     nothing and returns 0.
+ *   A launch takes at most pfr_rank_count_max_thr() thresholds per row (host-only query; 64: the thresholds and their 32-bit counters
+ *     of a 128-row tile live in LDS, 128 x ld x 12 bytes next to 35 840 bytes of operands — 134 144 of the CU's 163 840 bytes at 64); a
+ *     caller with longer lists slices them into several launches.  A larger ld returns PFR_ERR_ARG and launches nothing; so do null or
+ *     host pointers, a bad dtype or D, and int8 rows without their scales.
+ *
+ * pfr_pair_scores_gather: out[i][k] = s(i, col[i][k]) for every col[i][k] in [0, Nb) (col int32 [Na][ld], out fp32 [Na][ld], any ld >= 0;
+ *   other entries are padding: nothing is read through them and their out element is not touched).  This is where thresholds come from:
+ *   the threshold of a positive (i, p) must be the very fp32 number the count launch computes for (i, p), or the positive could count
+ *   itself.  THE TWO ENTRY POINTS AGREE BIT FOR BIT on the same operand bits: both run the same tile code — the same staging, 128-byte
+ *   k-steps and MFMA sequence — and the same score expression; the gather multiplies the 128 rows of a row tile with the 128 gathered b
+ *   rows of one k and keeps the diagonal, and an accumulator element depends on its two operand rows and the k order only, not on its
+ *   place in a tile.  Same argument errors as pfr_rank_count. */
+int pfr_rank_count_max_thr(void);
+int pfr_rank_count(const void* a, const float* a_scale, int Na, const void* b, const float* b_scale, const int* b_id, int Nb, int dtype,
+                   int D, const int* excl, const float* thr_val, const int* thr_id, const int* thr_cnt, int ld, unsigned int* cnt,
+                   pfr_stream_t stream);
+int pfr_pair_scores_gather(const void* a, const float* a_scale, int Na, const void* b, const float* b_scale, int Nb, int dtype, int D,
+                           const int* col, int ld, float* out, pfr_stream_t stream);
+
 /* ---- k-reciprocal re-ranking of match lists (Zhong et al., "Re-ranking Person Re-identification with k-reciprocal Encoding", CVPR 2017)
  * on SPARSE rows: nothing N x N is built.  The set is N items with unit-norm fp32 rows emb32 [N][D].
  * Inputs

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import metrics as M
-from ..match import recall_at_k, pair_similarity, pair_histogram
+from ..match import recall_at_k, pair_similarity, pair_histogram, positive_ranks
 
 
 class Controller(nn.Module):
@@ -113,6 +113,21 @@ class Controller(nn.Module):
         rk = recall_at_k(emb, classes, tuple(ks), compute_dtype=dt, rerank=dict(rr))
         return {f'Rerank Recall@K={k}': (x / y if y else float('nan')) for k, (x, y) in rk.items()}
 
+    def _retrieval(self, emb, classes):
+        """Opt-in (config.retrieval = dict(ks=[1, 5, 10])): the re-ID retrieval metrics from the exact rank of every positive of every
+        query among all the other items (match.positive_ranks: the match GEMM with a rank-counting epilogue on the device) — 'mAP',
+        'mINP', 'CMC@K={k}' over ks, 'Mean first rank'.  NaN when no item has a same-class other."""
+        rt = self.config.get('retrieval')
+        if rt is None:
+            return {}
+        ks = [int(k) for k in dict(rt).get('ks', (1, 5, 10))]
+        dt = torch.float32 if not emb.is_cuda else getattr(self.config, 'match_dtype', torch.bfloat16)
+        m = M.RankStats(*positive_ranks(emb, classes, compute_dtype=dt)).metrics(ks)
+        out = {'mAP': m['mAP'], 'mINP': m['mINP']}
+        out.update((f'CMC@K={k}', m[f'CMC@K={k}']) for k in ks)
+        out['Mean first rank'] = m['mean_first_rank']
+        return out
+
     def _all_pairs(self, emb, classes):
         """Opt-in (config.all_pairs_far, a list of FARs): verification metrics over EVERY pair of the validation set from the genuine /
         impostor score histograms (match.pair_histogram: one GEMM with a histogram epilogue on the device) instead of the sampled pair
@@ -141,6 +156,7 @@ class Controller(nn.Module):
             metrics.update({f'Recall@K={k}': (x / y if y else float('nan')) for k, (x, y) in rk.items()})
             metrics.update(self._all_pairs(emb, classes))
             metrics.update(self._rerank_recall(emb, classes, [10, 100]))
+            metrics.update(self._retrieval(emb, classes))
             print('', *[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')
             all_metrics[name] = metrics
         self.last_metrics = all_metrics
@@ -190,6 +206,7 @@ class Controller(nn.Module):
                 metrics[f'TH@FRR={frr}'] = th
             metrics.update(self._all_pairs(emb, classes))
             metrics.update(self._rerank_recall(emb, classes, ks))
+            metrics.update(self._retrieval(emb, classes))
             all_metrics[name] = metrics
             self.last_confmat[name] = confmat
             print(*[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')

@@ -189,6 +189,55 @@ class HistStats:
         return out
 
 
+class RankStats:
+    """Retrieval metrics from the exact ranks of every query's positives (match.positive_ranks): `ranks` int [Nq, Pmax], 1-based,
+    ascending per row, 0 padded; `npos` int [Nq].  A query is valid when it has a positive.  With r_(1) < … < r_(n) the ranks of a valid
+    query:  AP = (1 / n) Σ_k k / r_(k);  INP = n / r_(n);  first = r_(1).  Everything is summed in float64 on the host."""
+
+    def __init__(self, ranks, npos):
+        r = torch.as_tensor(ranks).detach().cpu().long()
+        n = torch.as_tensor(npos).detach().cpu().long().reshape(-1)
+        if r.dim() != 2 or r.shape[0] != n.numel():
+            raise ValueError("RankStats: ranks [Nq, Pmax] with npos [Nq]")
+        if n.numel() and (int(n.max()) > r.shape[1] or int(n.min()) < 0):
+            raise ValueError("RankStats: npos outside 0..Pmax")
+        valid = n > 0
+        r, n = r[valid], n[valid]
+        self.queries = int(n.numel())
+        k = torch.arange(1, r.shape[1] + 1)
+        used = k[None, :] <= n[:, None]
+        if bool((used & (r < 1)).any()):
+            raise ValueError("RankStats: a rank below 1 among the first npos entries of a row")
+        nd = n.double()
+        self.ap = (torch.where(used, k[None, :].double() / r.clamp_min(1).double(), torch.zeros((), dtype=torch.float64))).sum(dim=1) / nd
+        last = torch.gather(r, 1, (n - 1)[:, None]).reshape(-1) if self.queries else n
+        self.inp = nd / last.double()
+        self.first = r[:, 0] if r.shape[1] else n
+
+    def _mean(self, x):
+        return float(x.double().mean()) if self.queries else float('nan')
+
+    def mean_ap(self):
+        return self._mean(self.ap)
+
+    def mean_inp(self):
+        return self._mean(self.inp)
+
+    def cmc(self, k):
+        """share of the valid queries whose best positive is among the first k"""
+        return self._mean(self.first <= int(k))
+
+    def mean_first_rank(self):
+        return self._mean(self.first)
+
+    def metrics(self, ks=(1, 5, 10)):
+        out = {'mAP': self.mean_ap(), 'mINP': self.mean_inp()}
+        out.update((f'CMC@K={int(k)}', self.cmc(k)) for k in ks)
+        out['mean_first_rank'] = self.mean_first_rank()
+        out['queries'] = self.queries
+        return out
+
+
 # ---- function forms (one sort per call)
 def roc_curve(scores, labels):
     return PairStats(scores, labels).roc()
@@ -208,3 +257,7 @@ def best_threshold_accuracy(scores, labels, thresholds, fpr, fnr):
 
 def stats_at_threshold(scores, labels, thr):
     return PairStats(scores, labels).stats_at(thr)
+
+
+def rank_metrics(ranks, npos, ks=(1, 5, 10)):
+    return RankStats(ranks, npos).metrics(ks)

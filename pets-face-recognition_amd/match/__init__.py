@@ -881,6 +881,151 @@ def _pair_histogram_torch(emb, classes, emb_b, classes_b, bins, lo, inv_w, norma
     return hist.view(2, bins + 1)
 
 
+# ---- exact retrieval ranks: mAP / CMC / mINP ----------------------------------------------------------------------------------------
+def rank_count_max_thr():
+    """thresholds per row one pfr_rank_count launch takes (host arithmetic)"""
+    return int(lib.pfr_rank_count_max_thr())
+
+
+def _positive_lists(ca, cb, sym):
+    """The positives of every query, without anything Nq x Nb: a stable sort of the gallery classes makes every class one run.
+    → (col int64 [Nq, Pmax]: gallery indices of the query's same-class items (itself left out when `sym`), ascending, -1 padded;
+       npos int64 [Nq])"""
+    Nq, dev = ca.numel(), ca.device
+    order = torch.argsort(cb, stable=True)
+    scb = cb[order]
+    lo = torch.searchsorted(scb, ca, right=False)
+    n = torch.searchsorted(scb, ca, right=True) - lo
+    npos = n - 1 if sym else n                      # (symmetric: the query is one item of its own run)
+    pmax = int(npos.max()) if Nq else 0
+    k = torch.arange(pmax, device=dev)[None, :]
+    src = k
+    if sym:
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(order.numel(), device=dev)
+        src = k + (k >= (inv - lo)[:, None]).long()  # skip the query's own place in the run
+    ok = k < npos[:, None]
+    pos = (lo[:, None] + src).clamp_max(max(cb.numel() - 1, 0))
+    col = torch.where(ok, order[pos] if cb.numel() else pos, torch.full_like(pos, -1))
+    return col, npos
+
+
+def _precede_counts_torch(s, ids, thr, tid, excl, budget=1 << 24):
+    """the count of pfr_rank_count on a dense block of scores: s [c, Nb] with column ids [Nb], thresholds thr / tid [c, P], excl [c] or
+    None → int64 [c, P]; the compares are the contract's (IEEE: NaN precedes nothing, nothing precedes NaN)"""
+    c, Nb = s.shape
+    P = thr.shape[1]
+    out = torch.zeros((c, P), dtype=torch.int64, device=s.device)
+    keep = None if excl is None else (ids[None, :] != excl[:, None])
+    pk = max(1, budget // max(1, c * Nb))
+    for k0 in range(0, P, pk):
+        t, ti = thr[:, k0:k0 + pk, None], tid[:, k0:k0 + pk, None]
+        pre = (s[:, None, :] > t) | ((s[:, None, :] == t) & (ids[None, None, :] < ti))
+        if keep is not None:
+            pre &= keep[:, None, :]
+        out[:, k0:k0 + pk] = pre.sum(dim=2)
+    return out
+
+
+def _positive_counts_torch(a, b, col, npos, sym, chunk=256):
+    """chunked dense restatement of the device path (any device): per block of query rows one fp32 matmul, the thresholds gathered from it,
+    the contract's compares, a sum — no argsort.  a, b: prepared fp32 rows → cnt int64 [Nq, Pmax]"""
+    Nq, P = col.shape
+    ids = torch.arange(b.shape[0], device=a.device)
+    cnt = torch.zeros((Nq, P), dtype=torch.int64, device=a.device)
+    if P == 0 or b.shape[0] == 0:
+        return cnt
+    for r0 in range(0, Nq, chunk):
+        s = a[r0:r0 + chunk] @ b.t()
+        cc = col[r0:r0 + chunk]
+        thr = torch.gather(s, 1, cc.clamp_min(0))
+        excl = torch.arange(r0, r0 + s.shape[0], device=a.device) if sym else None
+        cnt[r0:r0 + chunk] = _precede_counts_torch(s, ids, thr, cc, excl)
+    return cnt
+
+
+def _ranks_from_counts(cnt, npos):
+    """counts [Nq, Pmax] → 1-based ranks, ascending per row, 0 padded (int32)"""
+    big = torch.iinfo(torch.int64).max
+    ok = torch.arange(cnt.shape[1], device=cnt.device)[None, :] < npos[:, None]
+    r = torch.where(ok, cnt.long() + 1, torch.full_like(cnt.long(), big)).sort(dim=1).values
+    return torch.where(r == big, torch.zeros_like(r), r).int()
+
+
+def positive_ranks(emb, classes, emb_b=None, classes_b=None, compute_dtype=torch.float32, normalize=True):
+    """The exact rank of every positive of every query among ALL the other items — what mAP, mINP and the CMC curve are made of.
+    Symmetric (`emb` [N, D], `classes` [N]): every item queries the N - 1 others, positives = same class, not itself.  Query / gallery
+    (`emb_b`, `classes_b`): the rows of `emb` query the rows of `emb_b`, positives = same class in the gallery, nothing is excluded.
+    Scores are the dot products of the (L2-normalised unless normalize=False) rows in `compute_dtype` (torch.float32, torch.bfloat16,
+    torch.int8), ordered descending with ties to the lower gallery index: rank = 1 + the number of items that precede the positive.
+    → (ranks int32 [Nq, Pmax]: 1-based, ascending per row, 0 padded;  npos int32 [Nq]).
+    CUDA tensors: pfr_pair_scores_gather gives the positives' own scores, pfr_rank_count counts in the epilogue of the match GEMM (one
+    launch per `rank_count_max_thr()` positives of the longest list); no score matrix, no sort.  CPU tensors: chunked dense fp32 matmul
+    with the same compares."""
+    who = "positive_ranks"
+    if compute_dtype not in _PAIR_HIST_DTYPES:
+        raise PfrError(f"{who}: compute_dtype must be one of {_PAIR_HIST_DTYPES}")
+    if (emb_b is None) != (classes_b is None):
+        raise PfrError(f"{who}: emb_b and classes_b come together")
+    if emb.dim() != 2 or classes.numel() != emb.shape[0] or (emb_b is not None and (emb_b.dim() != 2 or emb_b.shape[1] != emb.shape[1]
+                                                                                    or classes_b.numel() != emb_b.shape[0])):
+        raise PfrError(f"{who}: emb [N, D] with classes [N] (and emb_b [Nb, D] with classes_b [Nb])")
+    if max(emb.shape[0], 0 if emb_b is None else emb_b.shape[0]) >= 2 ** 31:
+        raise PfrError(f"{who}: more than 2^31 - 1 rows")
+    dev, sym = emb.device, emb_b is None
+    ca = classes.to(dev).long().reshape(-1)
+    cb = ca if sym else classes_b.to(dev).long().reshape(-1)
+    col, npos = _positive_lists(ca, cb, sym)
+    Nq, P = col.shape
+    if not emb.is_cuda:
+        def rows(x):
+            x = x.float()
+            return x / x.norm(dim=1, keepdim=True).clamp_min(1e-12) if normalize else x
+        a = rows(emb)
+        cnt = _positive_counts_torch(a, a if sym else rows(emb_b), col, npos, sym)
+        return _ranks_from_counts(cnt, npos), npos.int()
+    cnt = torch.zeros((Nq, P), dtype=torch.int32, device=dev)
+    Nb = Nq if sym else emb_b.shape[0]
+    if Nq and Nb and P:
+        a, sa = _hist_operand(emb, compute_dtype, normalize)
+        b = sb = None
+        if not sym:
+            b, sb = _hist_operand(emb_b.to(dev), compute_dtype, normalize)
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        T, Dp = dtype_id(compute_dtype), a.shape[1]
+        ids = torch.arange(Nb, dtype=torch.int32, device=dev)
+        excl = torch.arange(Nq, dtype=torch.int32, device=dev) if sym else None
+        col32 = col.int().contiguous()
+        thr = torch.zeros((Nq, P), dtype=torch.float32, device=dev)
+        lib.pfr_pair_scores_gather(ptr(a), ptr(sa), Nq, ptr(b), ptr(sb), Nb, T, Dp, col32.data_ptr(), P, thr.data_ptr(), _stream())
+        cap = rank_count_max_thr()
+        for k0 in range(0, P, cap):
+            w = min(cap, P - k0)
+            tv, ti = thr[:, k0:k0 + w].contiguous(), col32[:, k0:k0 + w].contiguous()
+            tc = (npos - k0).clamp(0, w).int().contiguous()
+            part = cnt if w == P else torch.zeros((Nq, w), dtype=torch.int32, device=dev)
+            lib.pfr_rank_count(ptr(a), ptr(sa), Nq, ptr(b), ptr(sb), ids.data_ptr(), Nb, T, Dp, ptr(excl), tv.data_ptr(), ti.data_ptr(),
+                               tc.data_ptr(), w, part.data_ptr(), _stream())
+            if part is not cnt:
+                cnt[:, k0:k0 + w] = part
+    return _ranks_from_counts(cnt, npos), npos.int()
+
+
+def retrieval_metrics(emb, classes, emb_b=None, classes_b=None, ks=(1, 5, 10), compute_dtype=torch.float32, normalize=True):
+    """mAP, mINP, the CMC curve at `ks` and the mean first rank over the queries that have a positive, from `positive_ranks` (same
+    arguments).  With r_(1) < … < r_(n) the ranks of a query's n positives: AP = (1 / n) Σ_k k / r_(k), INP = n / r_(n), CMC@K = share of
+    queries with r_(1) <= K (engine.metrics.RankStats; float64 sums on the host).
+    → {'mAP', 'mINP', 'CMC@K={k}' for k in ks, 'mean_first_rank', 'queries'}; no valid query: NaN metrics and queries = 0.
+    Not covered: the camera / junk filtering of the re-ID protocols, and the mAP of a re-ranked order (it needs the re-ranked distance of
+    every item, `rerank` scores candidate lists)."""
+    from ..engine.metrics import RankStats
+    ks = tuple(int(k) for k in ks)
+    if any(k < 1 for k in ks):
+        raise PfrError(f"retrieval_metrics: ks={ks} must be positive")
+    ranks, npos = positive_ranks(emb, classes, emb_b, classes_b, compute_dtype=compute_dtype, normalize=normalize)
+    return RankStats(ranks, npos).metrics(ks)
+
+
 # ---- k-reciprocal re-ranking -----------------------------------------------------------------------------------------------------
 #: workspace limit of `rerank` on the device: the sparse V and V' rows take N * (E + E2) * 8 bytes
 RERANK_WORKSPACE_BUDGET = 16 << 30
