@@ -11,7 +11,7 @@
 //     dW     = A∘G1 + B∘(W·(G2 − M z̄ z̄ᵀ)) + C0 ⊗ (M z̄)                                 G2 = ZᵀZ
 // so neither x = conv3's output nor dx is ever read or written in the backward pass: per block the three passes over the widest
 // tensor of the network (pfr_bn_bwd_apply: read G, read x, write dx) and the two reads of dx by the data- and weight-gradient GEMMs
-// become two reads of G.  Checked against fp64 (tools/bnfree_check.py): dZ as accurate as the materialised form, dW and dγ
+// become two reads of G.  Checked against fp64 (tests/test_bnfree_host.py, tests/test_bnfree_gpu.py): dZ as accurate as the materialised form, dW and dγ
 // 50x more accurate (no bf16 rounding of x and dx in between).  The two kernels here are the small per-channel / per-weight parts.
 #include "pfr_common.h"
 

@@ -719,13 +719,25 @@ def test_halo_staged_3x3_inference_epilogue(case):
     (1, 9, 64, 64, False), (4, 23, 128, 256, True), (2, 56, 64, 256, "two"), (5, 14, 256, 1024, "two"), (3, 11, 128, 512, "two"),
     (2, 56, 128, 256, "inplace"), (3, 28, 256, 512, "inplace"), (5, 14, 512, 1024, "inplace"),
     (2, 56, 128, 256, "sub"), (3, 28, 256, 512, "sub"), (5, 14, 512, 1024, "sub"), (3, 10, 64, 64, "sub"),
+] + [
+    # (..., flags): the same through pfr_conv2d_dgrad_bn_ex / pfr_conv2d_dgrad_bn_sub_ex — 1 = dx stored through the bit mask, 2 = no input
+    # for the first BN (only sum g*mask; needs the masked residual of the block join, so not "inplace")
+    c + (f,) for c in [(2, 56, 64, 256, True), (3, 28, 128, 512, True), (5, 14, 256, 1024, True), (4, 23, 128, 256, True),
+                       (2, 56, 64, 256, "two"), (5, 14, 256, 1024, "two"), (3, 11, 128, 512, "two")] for f in (1, 2, 3)
+] + [
+    (2, 56, 128, 256, "inplace", 1), (3, 28, 256, 512, "inplace", 1), (5, 14, 512, 1024, "inplace", 1),
+    (2, 56, 128, 256, "sub", 3), (3, 28, 256, 512, "sub", 3), (5, 14, 512, 1024, "sub", 3), (3, 10, 64, 64, "sub", 3),
 ])
 def test_streaming_1x1_dgrad_with_bn_backward_sums(case):
     """pfr_conv2d_dgrad_bn in streaming mode (pfr_set_tuning("bnb", 2)): dx must be BIT-identical to the plain data gradient / join,
     and the partial sums must finalise (pfr_bn_bwd_finalize) to the dgamma / dbeta / coefficients of the separate
-    pfr_bn_bwd_reduce pass over the finished gradient — recomputed mask (inner BNs) and bit mask (block-output BN with the join)."""
+    pfr_bn_bwd_reduce pass over the finished gradient — recomputed mask (inner BNs) and bit mask (block-output BN with the join).
+    With flags (the _ex entry points, what the BN-input-free backward asks of its producer): 1 = dx is bit-identical to the plain
+    gradient THROUGH the bit mask, same sums; 2 = bn_x = bn_coef = NULL, row 0 of the partials finalises to the same dbeta and row 1
+    is exactly 0; 3 = both."""
     from pets_face_recognition_amd._hip import lib
-    N, H, C, Co, join = case
+    N, H, C, Co, join = case[:5]
+    flags = case[5] if len(case) > 5 else 0
     two = join == "two"      # + the projection-shortcut BN of the previous block: same gradient, same bit mask, its own input
     inplace = join == "inplace"   # res = dx itself, no residual mask: the main branch adds to what the projection shortcut left there
     sub = join == "sub"           # res = the COMPACT gradient of a stride-2 projection shortcut, added at even (oh, ow) (pfr_conv2d_dgrad_bn_sub)
@@ -783,13 +795,23 @@ def test_streaming_1x1_dgrad_with_bn_backward_sums(case):
         part1 = torch.full((np_, 2, Co), float("nan"), device=DEV)
         part12 = torch.full((np_, 2, Co), float("nan"), device=DEV) if two else None
         dx1 = torch.full((N, H, H, Co), float("nan"), device=DEV, dtype=torch.bfloat16)
+        bnx_in, coef_in = (None, None) if flags & 2 else (bnx, coef)     # flag 2: the first BN's input is not there to be read
         for _ in range(2):
+            if sub and flags:
+                lib.pfr_conv2d_dgrad_bn_sub_ex(dy.data_ptr(), wt.data_ptr(), dx1.data_ptr(), 1, N, H, H, C, Co, H, H, comp.data_ptr(),
+                                               P(bnx_in), P(coef_in), bmask.data_ptr(), part1.data_ptr(), flags, st)
+                continue
             if sub:
                 lib.pfr_conv2d_dgrad_bn_sub(dy.data_ptr(), wt.data_ptr(), dx1.data_ptr(), 1, N, H, H, C, Co, H, H, comp.data_ptr(),
                                             bnx.data_ptr(), coef.data_ptr(), bmask.data_ptr(), part1.data_ptr(), st)
                 continue
             if inplace:
                 dx1.copy_(res)
+            if flags:
+                lib.pfr_conv2d_dgrad_bn_ex(dy.data_ptr(), wt.data_ptr(), dx1.data_ptr(), 1, N, H, H, C, Co, 1, 1, 0, 0, H, H,
+                                           dx1.data_ptr() if inplace else P(res), P(rmask), 0,
+                                           P(bnx_in), P(coef_in), P(bmask), part1.data_ptr(), P(bnx2), P(coef2), P(part12), flags, st)
+                continue
             lib.pfr_conv2d_dgrad_bn(dy.data_ptr(), wt.data_ptr(), dx1.data_ptr(), 1, N, H, H, C, Co, 1, 1, 0, 0, H, H,
                                     dx1.data_ptr() if inplace else P(res), P(rmask), 0,
                                     bnx.data_ptr(), coef.data_ptr(), P(bmask), part1.data_ptr(), P(bnx2), P(coef2), P(part12), st)
@@ -804,16 +826,55 @@ def test_streaming_1x1_dgrad_with_bn_backward_sums(case):
     finally:
         lib.pfr_set_tuning(b"sconv", 1)
         lib.pfr_set_tuning(b"bnb", 0)
-    assert torch.equal(dx0, dx1)
+    if flags & 1:
+        bits = ((bmask.unsqueeze(-1) >> torch.arange(8, device=DEV, dtype=torch.uint8)) & 1).reshape(N, H, H, Co).bool()
+        assert torch.equal(dx1, torch.where(bits, dx0, torch.zeros_like(dx0)))
+    else:
+        assert torch.equal(dx0, dx1)
     sg, sgx = part0[:, 0].abs().sum(0) + 1e-3, part0[:, 1].abs().sum(0) + 1e-3
     assert ((fin1[1] - fin0[1]).abs() / sg).max().item() < 5e-5          # dbeta = sum g
-    assert ((fin1[0] - fin0[0]).abs() / sgx).max().item() < 5e-5         # dgamma = sum g xhat
-    assert torch.allclose(fin1[2], fin0[2], rtol=3e-4, atol=1e-5 * float(fin0[2].abs().max()))
+    if flags & 2:
+        assert bool((part1[:, 1] == 0).all())                             # sum g xhat is not this launch's to give: exactly 0
+    else:
+        assert ((fin1[0] - fin0[0]).abs() / sgx).max().item() < 5e-5         # dgamma = sum g xhat
+        assert torch.allclose(fin1[2], fin0[2], rtol=3e-4, atol=1e-5 * float(fin0[2].abs().max()))
     if two:
         sgx2 = part02[:, 1].abs().sum(0) + 1e-3
         assert ((fin12[1] - fin02[1]).abs() / sg).max().item() < 5e-5
         assert ((fin12[0] - fin02[0]).abs() / sgx2).max().item() < 5e-5
         assert torch.allclose(fin12[2], fin02[2], rtol=3e-4, atol=1e-5 * float(fin02[2].abs().max()))
+
+
+def test_dgrad_bn_flags_need_the_bit_mask():
+    """pfr_conv2d_dgrad_bn_ex / pfr_conv2d_dgrad_bn_sub_ex with flags but without the bit mask raise and launch nothing"""
+    from pets_face_recognition_amd._hip import lib, PfrError
+    N, H, C, Co = 3, 10, 64, 64
+    g = torch.Generator().manual_seed(5)
+    dy = torch.randn(N, H, H, C, generator=g).to(DEV).bfloat16()
+    wt = (torch.randn(Co, 1, 1, C, generator=g) / C ** 0.5).to(DEV).bfloat16()
+    bnx = torch.randn(N, H, H, Co, generator=g).to(DEV).bfloat16()
+    comp = torch.randn(N, H // 2, H // 2, Co, generator=g).to(DEV).bfloat16()
+    coef = torch.ones(4, Co, device=DEV)
+    st = torch.cuda.current_stream().cuda_stream
+    try:
+        lib.pfr_set_tuning(b"sconv", 2)
+        lib.pfr_set_tuning(b"bnb", 2)
+        np_ = lib.pfr_conv2d_dgrad_bn_parts(1, N, H, H, C, Co, 1, 1, 0, H, H)
+        assert np_ > 0
+        part = torch.full((np_, 2, Co), float("nan"), device=DEV)
+        dx = torch.full((N, H, H, Co), float("nan"), device=DEV, dtype=torch.bfloat16)
+        for flags in (1, 2, 3):
+            with pytest.raises(PfrError):
+                lib.pfr_conv2d_dgrad_bn_ex(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), 1, N, H, H, C, Co, 1, 1, 0, 0, H, H, 0, 0, 0,
+                                           bnx.data_ptr(), coef.data_ptr(), 0, part.data_ptr(), 0, 0, 0, flags, st)
+            with pytest.raises(PfrError):
+                lib.pfr_conv2d_dgrad_bn_sub_ex(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), 1, N, H, H, C, Co, H, H, comp.data_ptr(),
+                                               bnx.data_ptr(), coef.data_ptr(), 0, part.data_ptr(), flags, st)
+        torch.cuda.synchronize()
+    finally:
+        lib.pfr_set_tuning(b"sconv", 1)
+        lib.pfr_set_tuning(b"bnb", 0)
+    assert bool(torch.isnan(dx.float()).all()) and bool(torch.isnan(part).all())
 
 
 @pytest.mark.parametrize("case", [
