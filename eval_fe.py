@@ -34,12 +34,17 @@ def main(argv=None):
     ap.add_argument('--retrieval', type=int, nargs='*', default=None, metavar='K',
                     help="also report the retrieval metrics 'mAP', 'mINP', 'CMC@K=…' and 'Mean first rank' from the exact rank of every "
                          'positive (match.positive_ranks); the CMC ranks K default to 1 5 10')
+    ap.add_argument('--cluster', nargs='+', default=None, metavar='T',
+                    help="also report 'Cluster F / precision / recall / BCubed F thr=…' and 'Clusters thr=…': identity clustering (single "
+                         "linkage, match.cluster) at these similarity thresholds; 'opt' stands for the run's optimal threshold, e.g. 0.8 opt")
     args = ap.parse_args(argv)
     config = get_config(args.config)
     if args.rerank is not None:
         config['rerank'] = dict(k1=int(args.rerank[0]), k2=int(args.rerank[1]), lambda_value=float(args.rerank[2]))
     if args.retrieval is not None:
         config['retrieval'] = dict(ks=list(args.retrieval) or [1, 5, 10])
+    if args.cluster is not None:
+        config['cluster'] = dict(thresholds=[t if t == 'opt' else float(t) for t in args.cluster])
     if args.all_pairs_far is not None:
         config['all_pairs_far'] = list(args.all_pairs_far)
     controller = Controller(config)

@@ -585,6 +585,51 @@ int pfr_rank_count(const void* a, const float* a_scale, int Na, const void* b, c
 int pfr_pair_scores_gather(const void* a, const float* a_scale, int Na, const void* b, const float* b_scale, int Nb, int dtype, int D,
                            const int* col, int ld, float* out, pfr_stream_t stream);
 
+/* ---- threshold clustering: range search and single-linkage components from the match GEMM (csrc/pfr_cluster.hip).  Nothing Na x Nb is
+ * written: every score is compared with the threshold where the MFMA leaves it; what qualifies is appended to an edge list, united in a
+ * parent array, or both.
+ *   Scores.  a [Na][D], b [Nb][D], a_scale, b_scale, dtype, D: the operands, layouts and D multiples of pfr_pair_hist.  s(i, j) is the score
+ *     of pfr_pair_hist / pfr_pair_scores_gather, produced by the tile code pfr_pair_scores_gather runs (csrc/pfr_pairtile.h: the same
+ *     staging, 128-byte k-steps, MFMA sequence and score expression): the two AGREE BIT FOR BIT on the same operand bits.  b == NULL:
+ *     symmetric mode, every unordered pair i < j of a is visited once, the diagonal never (b_scale, Nb and b_off are ignored).
+ *   Rule.  A pair qualifies iff  s(i, j) >= thr  as an IEEE comparison: a NaN score never qualifies, thr = -inf takes every non-NaN pair,
+ *     thr = +inf only +inf scores.  Node ids: u = a_off + i, v = b_off + j (symmetric: v = a_off + j) — a caller clusters a set too large
+ *     for one launch block by block.
+ *   Edge output (edge_i != NULL; edge_j and count are then required, edge_s is optional).  *count (u64, device) is INCREASED by the number
+ *     of qualifying pairs of this call: the call adds, the caller zeroes it.  The pair that draws position p < cap is written as
+ *     edge_i[p] = u, edge_j[p] = v, edge_s[p] = s; pairs that draw p >= cap are counted and not written, and nothing is written at or
+ *     beyond cap: *count > cap after the call means "truncated, run again with cap >= *count".  Positions are reserved per wave and tile
+ *     (the lanes' qualifying masks, their population counts, a wave scan, ONE agent-scope integer add by one lane); a wave whose 64 x 64
+ *     part of a tile holds no qualifying score pays one wave vote.  The ORDER of the edges is unspecified; the SET is deterministic.
+ *   Union output (parent != NULL; status is then required).  parent int32 [n_nodes] with 0 <= parent[x] <= x on entry (0, 1, 2, ... is
+ *     the empty forest; the output of an earlier call is valid too: calls accumulate).  For every qualifying pair with both ids in
+ *     [0, n_nodes) the two trees are united, lock-free: every access to parent is an agent-scope relaxed atomic load or compare-exchange
+ *     (a plain store is not seen across XCDs).  A union finds both roots with path halving, hooks the LARGER root under the SMALLER with a
+ *     compare-exchange and, when that fails, goes on from the value read back.  parent[x] <= x therefore holds at every instant and every
+ *     walk strictly descends.
+ *     NO UNBOUNDED LOOP: a union spends at most  6 * n_nodes + 64  loop iterations (find steps and hook retries together: both walks
+ *     only descend and every failed hook descends too, so a correct forest needs fewer than 6 n_nodes — csrc/pfr_cluster.hip).  A union that reaches the cap, or reads a parent outside [0, x], stores a
+ *     non-zero value to *status (int32, device; the caller zeroes it) and gives up on that pair: a bug or a corrupt parent array ends in a
+ *     flag and a wrong answer, never in a hang or an access outside parent.
+ *   Either output may be absent; both absent is PFR_ERR_ARG.  So are null or host pointers among the required arguments, a bad dtype or
+ *     D, int8 rows without their scales, cap < 0, n_nodes < 0, negative offsets, and offsets that pass 2^31 - 1 together with Na / Nb; nothing
+ *     is launched or written then.  Na == 0, Nb == 0 and a symmetric Na == 1 do nothing and return 0.
+ *
+ * pfr_cc_union: the same union over an explicit edge list edge_i / edge_j int32 [E] (from pfr_pairs_above, from top-K lists, from another
+ *   rank).  Self-loops and edges with an id outside [0, n_nodes) are ignored (-1 is padding).  E == 0 does nothing.
+ * pfr_cc_flatten: labels[x] = the root of x = the smallest node id of its component (int32 [n_nodes]).  The kernel only reads parent
+ *   (agent-scope loads, walks bounded by n_nodes) and writes labels with agent-scope stores, so labels MAY ALIAS parent: a walker that
+ *   meets a flattened entry reads either the old parent or the root, both ancestors.  It is a launch of its own: the kernel boundary is
+ *   what makes every hook of the earlier launches visible.  The labels are canonical: two runs give the same bits whatever order the
+ *   unions took.
+ * NOT COVERED.  A threshold so low that the graph is near complete makes the union epilogue do ~N^2 / 2 finds: correct, slow, and not
+ *   measured.  Only single linkage (connected components of the threshold graph): no average linkage, DBSCAN or Chinese whispers. */
+int pfr_pairs_above(const void* a, const float* a_scale, int Na, int a_off, const void* b, const float* b_scale, int Nb, int b_off,
+                    int dtype, int D, float thr, int* edge_i, int* edge_j, float* edge_s, long cap, unsigned long long* count,
+                    int* parent, int n_nodes, int* status, pfr_stream_t stream);
+int pfr_cc_union(int* parent, int n_nodes, const int* edge_i, const int* edge_j, long E, int* status, pfr_stream_t stream);
+int pfr_cc_flatten(int* parent, int n_nodes, int* labels, pfr_stream_t stream);
+
 /* ---- k-reciprocal re-ranking of match lists (Zhong et al., "Re-ranking Person Re-identification with k-reciprocal Encoding", CVPR 2017)
  * on SPARSE rows: nothing N x N is built.  The set is N items with unit-norm fp32 rows emb32 [N][D].
  * Inputs

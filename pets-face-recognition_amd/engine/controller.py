@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import metrics as M
-from ..match import recall_at_k, pair_similarity, pair_histogram, positive_ranks
+from ..match import recall_at_k, pair_similarity, pair_histogram, positive_ranks, cluster
 
 
 class Controller(nn.Module):
@@ -144,6 +144,29 @@ class Controller(nn.Module):
         out.update((f'AllPairs TH@FAR={far}', pts[far][1]) for far in fars)
         return out
 
+    def _cluster(self, emb, classes, ps):
+        """Opt-in (config.cluster = dict(thresholds=[0.8, 'opt', …])): identity clustering of the set at each threshold — single linkage,
+        the connected components of the pairs at or above it (match.cluster: the match GEMM with a union-find epilogue on the device) —
+        scored against the classes (engine.metrics.ClusterStats): pairwise F / precision / recall, BCubed F and the number of clusters.
+        Thresholds are similarities (cos + 1) / 2 like 'Opt thr' and TH@FAR; the string 'opt' is this run's PairStats.opt_threshold().
+        The kernels compare the cosine with float32(2 t - 1): that one rounding is the only difference to comparing similarities."""
+        cl = self.config.get('cluster')
+        if cl is None:
+            return {}
+        thrs = list(dict(cl).get('thresholds', ()))
+        dt = torch.float32 if not emb.is_cuda else getattr(self.config, 'match_dtype', torch.bfloat16)
+        stats = []
+        for t in thrs:
+            sim = float(ps.opt_threshold()) if isinstance(t, str) and t == 'opt' else float(t)
+            stats.append(M.ClusterStats(cluster(emb, 2.0 * sim - 1.0, compute_dtype=dt), classes))
+        out = {}
+        out.update((f'Cluster F thr={t}', st.pairwise()[2]) for t, st in zip(thrs, stats))
+        out.update((f'Cluster precision thr={t}', st.pairwise()[0]) for t, st in zip(thrs, stats))
+        out.update((f'Cluster recall thr={t}', st.pairwise()[1]) for t, st in zip(thrs, stats))
+        out.update((f'Cluster BCubed F thr={t}', st.bcubed()[2]) for t, st in zip(thrs, stats))
+        out.update((f'Clusters thr={t}', st.clusters) for t, st in zip(thrs, stats))
+        return out
+
     def test_epoch_end(self, outputs):
         all_metrics = {}
         for i in range(len(outputs)):
@@ -157,6 +180,7 @@ class Controller(nn.Module):
             metrics.update(self._all_pairs(emb, classes))
             metrics.update(self._rerank_recall(emb, classes, [10, 100]))
             metrics.update(self._retrieval(emb, classes))
+            metrics.update(self._cluster(emb, classes, ps))
             print('', *[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')
             all_metrics[name] = metrics
         self.last_metrics = all_metrics
@@ -207,6 +231,7 @@ class Controller(nn.Module):
             metrics.update(self._all_pairs(emb, classes))
             metrics.update(self._rerank_recall(emb, classes, ks))
             metrics.update(self._retrieval(emb, classes))
+            metrics.update(self._cluster(emb, classes, ps))
             all_metrics[name] = metrics
             self.last_confmat[name] = confmat
             print(*[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')

@@ -238,6 +238,57 @@ class RankStats:
         return out
 
 
+class ClusterStats:
+    """Clustering metrics against class labels: `labels` int [N] (cluster of every item, e.g. match.cluster), `classes` int [N].  Built
+    from the contingency counts n_kc (items of cluster k with class c) of the N (cluster, class) pairs — torch.unique, exact int64
+    arithmetic, nothing cluster x class is built.  With a_k = Σ_c n_kc (cluster sizes) and b_c = Σ_k n_kc (class sizes):
+      pairwise  TP = Σ n_kc (n_kc - 1) / 2;  precision = TP / Σ a_k (a_k - 1) / 2;  recall = TP / Σ b_c (b_c - 1) / 2
+      BCubed    precision = (1 / N) Σ n_kc² / a_k;  recall = (1 / N) Σ n_kc² / b_c       (float64 sums on the host)
+      F = 2 P R / (P + R).  A ratio with a zero denominator is NaN ("nothing to measure")."""
+
+    def __init__(self, labels, classes):
+        k = torch.as_tensor(labels).detach().cpu().long().reshape(-1)
+        c = torch.as_tensor(classes).detach().cpu().long().reshape(-1)
+        if k.numel() != c.numel():
+            raise ValueError("ClusterStats: labels [N] with classes [N]")
+        self.n = int(k.numel())
+        uk, ik, a = torch.unique(k, return_inverse=True, return_counts=True)
+        uc, ic, b = torch.unique(c, return_inverse=True, return_counts=True)
+        # one int64 key per item: (cluster rank, class rank)
+        key, n = torch.unique(ik * max(int(uc.numel()), 1) + ic, return_counts=True)
+        ak, bc = a[key // max(int(uc.numel()), 1)], b[key % max(int(uc.numel()), 1)]
+        pairs = lambda x: int((x * (x - 1) // 2).sum())
+        self.tp, self.cluster_pairs, self.class_pairs = pairs(n), pairs(a), pairs(b)
+        self.clusters = int(uk.numel())
+        self.singletons = int((a == 1).sum())
+        n2 = n.double() * n.double()
+        self._b3p = float((n2 / ak.double()).sum()) / self.n if self.n else float('nan')
+        self._b3r = float((n2 / bc.double()).sum()) / self.n if self.n else float('nan')
+
+    @staticmethod
+    def _ratio(x, y):
+        return x / y if y else float('nan')
+
+    @staticmethod
+    def _f(p, r):
+        return 2.0 * p * r / (p + r) if p + r > 0 else float('nan')      # (a NaN operand fails the compare)
+
+    def pairwise(self):
+        """(precision, recall, F)"""
+        p, r = self._ratio(self.tp, self.cluster_pairs), self._ratio(self.tp, self.class_pairs)
+        return p, r, self._f(p, r)
+
+    def bcubed(self):
+        """(precision, recall, F)"""
+        return self._b3p, self._b3r, self._f(self._b3p, self._b3r)
+
+    def metrics(self):
+        p, r, f = self.pairwise()
+        bp, br, bf = self.bcubed()
+        return {'pairwise_precision': p, 'pairwise_recall': r, 'pairwise_f': f, 'bcubed_precision': bp, 'bcubed_recall': br,
+                'bcubed_f': bf, 'clusters': self.clusters, 'singletons': self.singletons}
+
+
 # ---- function forms (one sort per call)
 def roc_curve(scores, labels):
     return PairStats(scores, labels).roc()
@@ -261,3 +312,7 @@ def stats_at_threshold(scores, labels, thr):
 
 def rank_metrics(ranks, npos, ks=(1, 5, 10)):
     return RankStats(ranks, npos).metrics(ks)
+
+
+def cluster_metrics(labels, classes):
+    return ClusterStats(labels, classes).metrics()

@@ -1026,6 +1026,168 @@ def retrieval_metrics(emb, classes, emb_b=None, classes_b=None, ks=(1, 5, 10), c
     return RankStats(ranks, npos).metrics(ks)
 
 
+# ---- threshold clustering: range search and single-linkage components ----------------------------------------------------------------
+#: edge capacity of the first pfr_pairs_above launch of `pairs_above` (12 bytes per edge); a second launch takes the exact count
+PAIRS_ABOVE_DEFAULT_CAP = 1 << 22
+
+
+def _fp32(x):
+    """a Python float rounded once to fp32 (what the kernels compare with)"""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def _check_pair_sets(who, emb, emb_b, compute_dtype):
+    if compute_dtype not in _PAIR_HIST_DTYPES:
+        raise PfrError(f"{who}: compute_dtype must be one of {_PAIR_HIST_DTYPES}")
+    if emb.dim() != 2 or (emb_b is not None and (emb_b.dim() != 2 or emb_b.shape[1] != emb.shape[1])):
+        raise PfrError(f"{who}: emb [N, D] (and emb_b [Nb, D])")
+    if max(emb.shape[0], 0 if emb_b is None else emb_b.shape[0]) >= 2 ** 31:
+        raise PfrError(f"{who}: more than 2^31 - 1 rows")
+
+
+def _pairs_above_torch(emb, emb_b, thr, normalize, max_pairs=None, chunk=2048):
+    """chunked fp32 matmul with the comparison rule of pfr_pairs_above (s >= thr in IEEE arithmetic: NaN never qualifies)"""
+    def rows(x):
+        x = x.float()
+        return x / x.norm(dim=1, keepdim=True).clamp_min(1e-12) if normalize else x
+    a = rows(emb)
+    sym = emb_b is None
+    b = a if sym else rows(emb_b)
+    jb = torch.arange(b.shape[0])
+    ii, jj, ss, total = [], [], [], 0
+    for r0 in range(0, a.shape[0], chunk):
+        s = a[r0:r0 + chunk] @ b.t()
+        ok = s >= thr
+        if sym:
+            ok &= torch.arange(r0, r0 + s.shape[0])[:, None] < jb[None, :]
+        i, j = ok.nonzero(as_tuple=True)
+        total += i.numel()
+        if max_pairs is not None and total > max_pairs:
+            continue                                  # (keep counting: the error names the whole count)
+        ii.append(i + r0); jj.append(j); ss.append(s[i, j])
+    if max_pairs is not None and total > max_pairs:
+        raise PfrError(f"pairs_above: {total} pairs at or above the threshold, max_pairs={max_pairs}")
+    cat = lambda ts, dt: torch.cat(ts) if ts else torch.zeros(0, dtype=dt)
+    return cat(ii, torch.int64), cat(jj, torch.int64), cat(ss, torch.float32)
+
+
+def pairs_above(emb, threshold, emb_b=None, compute_dtype=torch.float32, normalize=True, max_pairs=None):
+    """Range search (duplicate detection): EVERY pair whose score is at or above `threshold` — all unordered pairs i < j of `emb` [N, D],
+    or with `emb_b` all Na x Nb pairs of the two sets.  The score is the dot product of the (L2-normalised unless normalize=False) rows
+    in `compute_dtype` (torch.float32, torch.bfloat16, torch.int8), the score of `pair_histogram`; `threshold` is on that dot product and
+    is rounded once to fp32.  A pair qualifies iff score >= threshold in IEEE arithmetic (a NaN score never does).
+    → (i int64 [E], j int64 [E], score fp32 [E]) sorted by (i, j).
+    CUDA tensors: ONE pfr_pairs_above launch (the match GEMM with a compacting-append epilogue, nothing N x N is written) with a default
+    capacity; when more pairs qualify, one more launch with the exact count, never a third.  `max_pairs`: a PfrError that names the count
+    instead of a larger allocation.  CPU tensors: chunked fp32 matmul, same rule."""
+    who = "pairs_above"
+    _check_pair_sets(who, emb, emb_b, compute_dtype)
+    if max_pairs is not None and int(max_pairs) < 0:
+        raise PfrError(f"{who}: max_pairs={max_pairs} must be >= 0")
+    max_pairs = None if max_pairs is None else int(max_pairs)
+    thr = _fp32(threshold)
+    if not emb.is_cuda:
+        return _pairs_above_torch(emb, emb_b, thr, normalize, max_pairs)
+    dev, sym = emb.device, emb_b is None
+    Na, Nb = emb.shape[0], emb.shape[0] if sym else emb_b.shape[0]
+    npairs = Na * (Na - 1) // 2 if sym else Na * Nb
+    empty = (torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
+             torch.zeros(0, dtype=torch.float32, device=dev))
+    if npairs == 0:
+        return empty
+    a, sa = _hist_operand(emb, compute_dtype, normalize)
+    b = sb = None
+    if not sym:
+        b, sb = _hist_operand(emb_b.to(dev), compute_dtype, normalize)
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    cap = max(1, min(npairs, PAIRS_ABOVE_DEFAULT_CAP if max_pairs is None else min(PAIRS_ABOVE_DEFAULT_CAP, max_pairs)))
+    for attempt in (0, 1):
+        ei = torch.empty(cap, dtype=torch.int32, device=dev)
+        ej = torch.empty(cap, dtype=torch.int32, device=dev)
+        es = torch.empty(cap, dtype=torch.float32, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        lib.pfr_pairs_above(ptr(a), ptr(sa), Na, 0, ptr(b), ptr(sb), 0 if sym else Nb, 0, dtype_id(compute_dtype), a.shape[1], thr,
+                            ei.data_ptr(), ej.data_ptr(), es.data_ptr(), cap, count.data_ptr(), 0, 0, 0, _stream())
+        n = int(count.item())
+        if max_pairs is not None and n > max_pairs:
+            raise PfrError(f"{who}: {n} pairs at or above the threshold, max_pairs={max_pairs}")
+        if n <= cap:
+            break
+        if attempt == 1:
+            raise PfrError(f"{who}: the second launch counted {n} pairs for a capacity of {cap} (the set is deterministic: a bug)")
+        cap = n
+    i, j, s = ei[:n].long(), ej[:n].long(), es[:n]
+    order = torch.argsort(i * Nb + j)
+    return i[order], j[order], s[order]
+
+
+def _host_components(n, i, j):
+    """host union-find (path halving, larger root under the smaller) over the edges (i, j) -> int64 labels [n] = component minimum"""
+    parent = list(range(n))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    for u, v in zip(i.tolist(), j.tolist()):
+        ru, rv = find(u), find(v)
+        if ru != rv:
+            parent[max(ru, rv)] = min(ru, rv)
+    return torch.tensor([find(x) for x in range(n)], dtype=torch.int64)
+
+
+def cluster(emb, threshold, compute_dtype=torch.float32, normalize=True, chunk=None):
+    """Identity clustering at a threshold: single linkage = the connected components of the graph whose edges are the pairs of
+    `pairs_above(emb, threshold, …)` (same score, same rule).  → labels int64 [N]: the smallest index of the item's component.
+    CUDA tensors: pfr_pairs_above with the union-find epilogue and NO edge list (one launch, or with `chunk` one launch per (row block,
+    column block) of that many rows with node offsets), then pfr_cc_flatten; a non-zero status word of the union-find's loop caps raises a
+    PfrError.  CPU tensors: a host union-find over the edges of the CPU `pairs_above`.
+    Not covered: a threshold so low that the graph is near complete costs ~N^2 / 2 finds on the device (correct, slow, not measured); only
+    single linkage — no average linkage, DBSCAN or Chinese whispers."""
+    who = "cluster"
+    _check_pair_sets(who, emb, None, compute_dtype)
+    if chunk is not None and int(chunk) < 1:
+        raise PfrError(f"{who}: chunk={chunk} must be >= 1")
+    N = emb.shape[0]
+    if not emb.is_cuda:
+        i, j, _ = _pairs_above_torch(emb, None, _fp32(threshold), normalize)
+        return _host_components(N, i, j)
+    dev = emb.device
+    parent = torch.arange(N, dtype=torch.int32, device=dev)
+    if N < 2:
+        return parent.long()
+    thr = _fp32(threshold)
+    a, sa = _hist_operand(emb, compute_dtype, normalize)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    T, Dp = dtype_id(compute_dtype), a.shape[1]
+    step = N if chunk is None else int(chunk)
+    sp = lambda r0: 0 if sa is None else sa[r0:].data_ptr()
+    for r0 in range(0, N, step):
+        nr = min(step, N - r0)
+        for c0 in range(r0, N, step):
+            nc = min(step, N - c0)
+            if c0 == r0:     # the block's own pairs: symmetric mode
+                lib.pfr_pairs_above(a[r0:].data_ptr(), sp(r0), nr, r0, 0, 0, 0, 0, T, Dp, thr, 0, 0, 0, 0, 0, parent.data_ptr(), N,
+                                    status.data_ptr(), _stream())
+            else:
+                lib.pfr_pairs_above(a[r0:].data_ptr(), sp(r0), nr, r0, a[c0:].data_ptr(), sp(c0), nc, c0, T, Dp, thr, 0, 0, 0, 0, 0,
+                                    parent.data_ptr(), N, status.data_ptr(), _stream())
+    labels = torch.empty(N, dtype=torch.int32, device=dev)
+    lib.pfr_cc_flatten(parent.data_ptr(), N, labels.data_ptr(), _stream())
+    if int(status.item()) != 0:
+        raise PfrError(f"{who}: the union-find gave up on a pair (status {int(status.item())}): a loop reached its iteration cap")
+    return labels.long()
+
+
+def cluster_metrics(labels, classes):
+    """Clustering against the class labels (engine.metrics.ClusterStats): pairwise precision / recall / F, BCubed precision / recall / F,
+    `clusters` and `singletons`, from the contingency counts of the N (cluster, class) pairs in exact int64 arithmetic; nothing
+    cluster x class is built.  A ratio with a zero denominator is NaN."""
+    from ..engine.metrics import ClusterStats
+    return ClusterStats(labels, classes).metrics()
+
+
 # ---- k-reciprocal re-ranking -----------------------------------------------------------------------------------------------------
 #: workspace limit of `rerank` on the device: the sparse V and V' rows take N * (E + E2) * 8 bytes
 RERANK_WORKSPACE_BUDGET = 16 << 30
