@@ -57,6 +57,25 @@ int pfr_get_tuning(const char* key, int* value);
 /* bumped by every pfr_set_tuning call that CHANGES a knob: launch plans that baked a kernel choice in (statistics-partial granularity,
  * partial-row counts) are rebuilt by their owners when the epoch they were built under is over */
 int pfr_tuning_epoch(void);
+/* Launch identity for tests that force a kernel with the knobs above: the kernel that took the calling thread's LAST launch of the
+ * convolution family (pfr_conv2d_fwd / _dgrad_* / pfr_gemm_act* / pfr_conv1x1_* / pfr_conv2d_wgrad; 0 before the first).  Host
+ * bookkeeping only (a thread-local the launchers store just before they launch): no device work, dispatch never reads it.
+ *   id = family << 24 | detail
+ *   family 1 tile kernel (pfr_igemm.hip)      detail: bits 0-2 tile (rows x couts) 0:128x128 1:64x128 2:128x64 3:64x64 4:256x256 5:256x128,
+ *                                                     bit 3 (8) 128-byte k-steps (KCH 8; clear: KCH 4), bit 4 (16) FAST (C a k-step multiple),
+ *                                                     bit 5 (32) PRO (fused operand prologue), bit 6 (64) EPRE (operand-row epilogue),
+ *                                                     bit 7 (128) BNB (BatchNorm-backward sums), bit 8 (256) parity-class data gradient
+ *   family 2 persistent kernel (pfr_igemm_p.hip)      bits 0-2 tile 0..3 as above, bit 3 KCH 8, bit 4 lean epilogue, bit 8 parity classes
+ *                                                     (only the lean path — bf16 output, whole tiles, no post-ops — has 128-byte k-steps: the
+ *                                                     general kernel runs KCH 4 and reports bit 3 clear whatever "igemm_pkch" is)
+ *   family 3 streaming 1x1 (pfr_sconv.hip)            bits 0-3 epilogue: 0 plain 1 join / accumulate 2 bias(+ReLU) 3 bias + residual,
+ *                                                     4-8 the BatchNorm-backward forms; bit 4 statistics; bit 5 four-wave column slices
+ *   family 4 halo-staged 3x3 (pfr_sconv3.hip), 5 halo-staged stem (pfr_sstem.hip):  bit 0 statistics, bit 1 inference epilogue
+ *   family 6 streaming Linear (pfr_slin.hip)          bits 0-2 epilogue: 0 plain 1 bias 2 bias + residual 3 GELU 4 GELU backward; bits 4-11 panel
+ *   family 7 weight-gradient tile (pfr_wgrad.hip)     bits 0-1 the "wgrad_tile" number (bit 0: 64 couts, bit 1: 64 k columns; clear: 128),
+ *                                                     bit 2 fused prologue, bits 8-23 splits
+ *   family 8 256x256 weight-gradient tile, 9 streaming 1x1 weight gradient, 10 halo-staged 3x3 weight gradient:  bits 8-23 slabs written */
+int pfr_debug_last_conv_kernel(void);
 
 /* C-side executor of a pre-built launch plan (csrc/pfr_plan.hip): the host keeps a step's fixed list of C-ABI calls (fixed device
  * pointers) in a plan and replays it with ONE call instead of one interpreter round trip per launch.  An entry is appended with

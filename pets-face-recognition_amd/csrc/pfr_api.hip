@@ -6,6 +6,9 @@
 static thread_local char g_err[512] = "";
 
 thread_local hipEvent_t pfr_tls_stop_event = nullptr;
+thread_local int pfr_tls_last_conv_kernel = 0;
+// the kernel the calling thread's last convolution / weight-gradient launch took (encoding: include/pfr_hip.h); no device work
+extern "C" int pfr_debug_last_conv_kernel(void) { return pfr_tls_last_conv_kernel; }
 
 void pfr_set_error(const char* fmt, ...) {
   va_list ap;

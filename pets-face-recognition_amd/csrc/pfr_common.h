@@ -89,6 +89,20 @@ static inline bool pfr_lds_attr_needed(std::atomic<unsigned long long>& done, un
 // follows, instead of a separate hipEventRecord whose marker packet delays the next kernel of the stream by ~7 us.
 extern thread_local hipEvent_t pfr_tls_stop_event;
 
+// Launch identity of the convolution family (pfr_debug_last_conv_kernel; the encoding is documented once, in include/pfr_hip.h):
+// every host-side launcher of a convolution / weight-gradient kernel stores (family << 24 | detail) here just before it launches.
+// Host bookkeeping only: no device work, and nothing in dispatch reads it back.
+enum PfrConvKernel {
+  PFR_CK_NONE, PFR_CK_TILE, PFR_CK_PERSISTENT, PFR_CK_SCONV, PFR_CK_SCONV3, PFR_CK_SSTEM, PFR_CK_SLIN, PFR_CK_WGRAD_TILE, PFR_CK_WGRAD_BIG,
+  PFR_CK_SWGRAD, PFR_CK_WGRAD9
+};
+extern thread_local int pfr_tls_last_conv_kernel;
+static inline void pfr_note_conv_kernel(int family, int detail) { pfr_tls_last_conv_kernel = (family << 24) | detail; }
+// tile index shared by the tile and the persistent kernel (rows x couts): 0:128x128 1:64x128 2:128x64 3:64x64 4:256x256 5:256x128
+constexpr int pfr_ck_tile(int bq, int bp) {
+  return bq == 256 ? (bp == 256 ? 4 : 5) : (bq == 128 ? (bp == 128 ? 0 : 2) : (bp == 128 ? 1 : 3));
+}
+
 #define PFR_CHECK_ARG(cond, ...)            \
   do {                                      \
     if (!(cond)) {                          \

@@ -934,6 +934,14 @@ static int launch_tile_k(IgemmParams& p, hipStream_t st) {
 #ifdef PFR_IGEMM_TRACE
   if (p.dbg & 16) grid.x = (grid.x + 3) / 4 * 8;   // experiment: the tiles run on XCDs 0-3 only (blocks of XCDs 4-7 exit at once)
 #endif
+  {   // launch identity (pfr_debug_last_conv_kernel): the flavour chosen by the branches below
+    const bool pro = p.pro_scale != nullptr;
+    const bool bnb = !pro && sizeof(T) == sizeof(TO) && p.bnb_part[0];
+    const bool epre = !pro && !bnb && sizeof(T) == 2 && sizeof(TO) == 2 && fast && (p.res_mask || p.accumulate) && p.act != 3 &&
+                      p.Cout % 8 == 0 && p.ldy % 8 == 0;
+    pfr_note_conv_kernel(PFR_CK_TILE, pfr_ck_tile(BQ, BP) | (KCH == 8 ? 8 : 0) | (fast ? 16 : 0) | (pro ? 32 : 0) | (epre ? 64 : 0) |
+                                          (bnb ? 128 : 0) | (p.pclass ? 256 : 0));
+  }
   if (p.pro_scale) {
     if (fast) hipLaunchKernelGGL((igemm_kernel<T, TO, BQ, BP, true, true, KCH, NW, WP, 2>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((igemm_kernel<T, TO, BQ, BP, true, false, KCH, NW, WP, 2>), grid, block, 0, st, p);

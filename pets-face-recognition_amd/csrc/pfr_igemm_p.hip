@@ -744,6 +744,8 @@ static int launch_p(IgemmParams& p, hipStream_t st) {
                       (size_t)p.M * p.ldy * sizeof(TO) < ((size_t)1 << 31);
     if (lean) {
       const int g_p_pf = pfr_knob(KNOB_IGEMM_PPF);
+      const bool lean_k8 = g_p_pf == 3 ? false : (g_p_pf == 2 && p.C % (8 * DT<T>::KPACK) == 0) ? true : (g_p_pf >= 1 ? false : k8);
+      pfr_note_conv_kernel(PFR_CK_PERSISTENT, pfr_ck_tile(BQ, BP) | (lean_k8 ? 8 : 0) | 16 | (p.pclass ? 256 : 0));
       if (g_p_pf == 3) {
         hipLaunchKernelGGL((igemm_p_kernel<T, TO, BQ, BP, 4, 4, true, false, true>), g, dim3(320), 0, st, p, total);
       } else if (g_p_pf == 2 && p.C % (8 * DT<T>::KPACK) == 0) {
@@ -757,6 +759,7 @@ static int launch_p(IgemmParams& p, hipStream_t st) {
       return PFR_OK;
     }
   }
+  pfr_note_conv_kernel(PFR_CK_PERSISTENT, pfr_ck_tile(BQ, BP) | (p.pclass ? 256 : 0));
   hipLaunchKernelGGL((igemm_p_kernel<T, TO, BQ, BP, 4, 4, false>), g, blk, 0, st, p, total);
   PFR_CHECK_LAUNCH();
   return PFR_OK;

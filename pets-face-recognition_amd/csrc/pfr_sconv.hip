@@ -736,6 +736,7 @@ template <int TP, bool STATS, int EP = 0>
 static int sconv_launch_ns(SconvParams& sp, const SconvPlan& pl, hipStream_t st) {
   const int lds = pl.np * sp.K * 2 + 8 * pl.ns * 4096;
   const dim3 grid(256), block(512);
+  pfr_note_conv_kernel(PFR_CK_SCONV, EP | (STATS ? 16 : 0) | (TP == 4 ? 32 : 0));
 #define PFR_SCONV_GO(NSV)                                                                                       \
   do {                                                                                                          \
     auto kern = sconv_kernel<TP, NSV, STATS, EP>;                                                                     \

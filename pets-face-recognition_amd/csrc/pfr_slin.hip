@@ -423,6 +423,7 @@ static int slin_launch(IgemmParams& p, int dtype, int out_dtype, float* colsum, 
     if (scratch_ok.load(std::memory_order_relaxed) != 1) return 1;                         \
     static std::atomic<unsigned long long> attr{0};                                        \
     PFR_MAX_LDS_ONCE(attr, 160 * 1024, (const void*)slin_kernel<NTV, EPV>);                \
+    pfr_note_conv_kernel(PFR_CK_SLIN, (int)(EPV) | (np << 4));                             \
     hipLaunchKernelGGL((slin_kernel<NTV, EPV>), grid, block, lds, st, sp);                 \
   } while (0)
 #define PFR_SLIN_EP(NTV)                                                                   \

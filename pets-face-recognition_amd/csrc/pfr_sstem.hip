@@ -373,6 +373,7 @@ int sstem_try_launch(IgemmParams& p, int dtype, int out_dtype, hipStream_t st) {
   const dim3 grid((unsigned)((sp.nblk + bpw - 1) / bpw)), block(256);
   static std::atomic<unsigned long long> attr_set{0};
   PFR_MAX_LDS_ONCE(attr_set, 160 * 1024, (const void*)sstem_kernel<true>, (const void*)sstem_kernel<false>, (const void*)sstem_kernel<false, true>);
+  pfr_note_conv_kernel(PFR_CK_SSTEM, (p.stats_part ? 1 : 0) | (infer ? 2 : 0));
   if (infer) hipLaunchKernelGGL((sstem_kernel<false, true>), grid, block, lds, st, sp);
   else if (p.stats_part) hipLaunchKernelGGL(sstem_kernel<true>, grid, block, lds, st, sp);
   else hipLaunchKernelGGL(sstem_kernel<false>, grid, block, lds, st, sp);

@@ -1102,6 +1102,7 @@ static int launch_wgrad(WgradParams& p, hipStream_t st) {
   p.tilesP = (p.Cout + BP - 1) / BP;
   p.tilesQ = (p.KK + BQ - 1) / BQ;
   const dim3 grid((unsigned)(p.tilesP * p.tilesQ * p.splits));
+  pfr_note_conv_kernel(PFR_CK_WGRAD_TILE, (BP == 64 ? 1 : 0) | (BQ == 64 ? 2 : 0) | (p.pro_scale ? 4 : 0) | (p.splits << 8));
   if (p.pro_scale)
     hipLaunchKernelGGL((wgrad_kernel<T, BP, BQ, true>), grid, dim3(256), 0, st, p);
   else if (p.v2 && sizeof(T) == 2 && wgrad_v3()) {
@@ -1218,10 +1219,12 @@ extern "C" int pfr_conv2d_wgrad(const void* x, const void* dy, float* dw, float*
     n9 = wgrad9_launch(x, dy, p.dw, N, H, W, C, Cout, R, S, stride, pad, p.lddy, stream);
   if (n9 < 0) { pfr_set_error("pfr_conv2d_wgrad: launch failed"); return PFR_ERR_HIP; }
   if (n9 > 0) {
+    pfr_note_conv_kernel(PFR_CK_WGRAD9, n9 << 8);
     p.splits = n9;
     rc = PFR_OK;
   } else if (dtype == PFR_BF16 && p.v2 && p.simple && !direct && p.lddy % 8 == 0 && (long)p.M * p.lddy * 2 < (1L << 31) &&
       (long)p.M * p.KK * 2 < (1L << 31) && swgrad_plan(p.M, Cout, p.KK, &spl)) {
+    pfr_note_conv_kernel(PFR_CK_SWGRAD, spl.nsplit << 8);
     rc = swgrad_launch(p, spl, workspace, stream);
     if (rc != PFR_OK) return rc;
     p.splits = spl.nsplit;
@@ -1231,6 +1234,7 @@ extern "C" int pfr_conv2d_wgrad(const void* x, const void* dy, float* dw, float*
     constexpr int lds = PFR_WGRAD_NST * 32 * (256 + 256) * 2;
     static std::atomic<unsigned long long> attr{0};
     PFR_MAX_LDS_ONCE(attr, lds, (const void*)wgrad3_kernel<256, 256, 8, 2>);
+    pfr_note_conv_kernel(PFR_CK_WGRAD_BIG, p.splits << 8);
     hipLaunchKernelGGL((wgrad3_kernel<256, 256, 8, 2>), dim3((unsigned)(p.tilesP * p.tilesQ * p.splits)), dim3(512), lds, stream, p);
     PFR_CHECK_LAUNCH();
     rc = PFR_OK;
