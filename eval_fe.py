@@ -37,6 +37,10 @@ def main(argv=None):
     ap.add_argument('--cluster', nargs='+', default=None, metavar='T',
                     help="also report 'Cluster F / precision / recall / BCubed F thr=…' and 'Clusters thr=…': identity clustering (single "
                          "linkage, match.cluster) at these similarity thresholds; 'opt' stands for the run's optimal threshold, e.g. 0.8 opt")
+    ap.add_argument('--dbscan', nargs='+', default=None, metavar=('MIN_SAMPLES', 'T'),
+                    help="also report 'DBSCAN F / precision / recall / BCubed F / clusters / noise thr=…': DBSCAN identity clustering "
+                         "(match.dbscan) with MIN_SAMPLES items (the item itself included) per core neighbourhood at these similarity "
+                         "thresholds; 'opt' stands for the run's optimal threshold, e.g. 4 0.8 opt")
     args = ap.parse_args(argv)
     config = get_config(args.config)
     if args.rerank is not None:
@@ -45,6 +49,10 @@ def main(argv=None):
         config['retrieval'] = dict(ks=list(args.retrieval) or [1, 5, 10])
     if args.cluster is not None:
         config['cluster'] = dict(thresholds=[t if t == 'opt' else float(t) for t in args.cluster])
+    if args.dbscan is not None:
+        if len(args.dbscan) < 2:
+            ap.error('--dbscan needs MIN_SAMPLES and at least one threshold')
+        config['dbscan'] = dict(thresholds=[t if t == 'opt' else float(t) for t in args.dbscan[1:]], min_samples=int(args.dbscan[0]))
     if args.all_pairs_far is not None:
         config['all_pairs_far'] = list(args.all_pairs_far)
     controller = Controller(config)

@@ -642,12 +642,57 @@ int pfr_pair_scores_gather(const void* a, const float* a_scale, int Na, const vo
  *   what makes every hook of the earlier launches visible.  The labels are canonical: two runs give the same bits whatever order the
  *   unions took.
  * NOT COVERED.  A threshold so low that the graph is near complete makes the union epilogue do ~N^2 / 2 finds: correct, slow, and not
- *   measured.  Only single linkage (connected components of the threshold graph): no average linkage, DBSCAN or Chinese whispers. */
+ *   measured.  Single linkage only (connected components of the threshold graph); DBSCAN is the next section; no average linkage or
+ *   Chinese whispers. */
 int pfr_pairs_above(const void* a, const float* a_scale, int Na, int a_off, const void* b, const float* b_scale, int Nb, int b_off,
                     int dtype, int D, float thr, int* edge_i, int* edge_j, float* edge_s, long cap, unsigned long long* count,
                     int* parent, int n_nodes, int* status, pfr_stream_t stream);
 int pfr_cc_union(int* parent, int n_nodes, const int* edge_i, const int* edge_j, long E, int* status, pfr_stream_t stream);
 int pfr_cc_flatten(int* parent, int n_nodes, int* labels, pfr_stream_t stream);
+
+/* ---- DBSCAN identity clustering from the match GEMM (csrc/pfr_dbscan.hip): two passes of the score GEMM of pfr_pairs_above — a degree
+ * epilogue and a link epilogue — and a label pass.  Nothing N x N and no edge list is written.
+ *   Scores, dtypes, operand preparation, the schedule and the qualifying rule are EXACTLY those of pfr_pairs_above (rc_tile_gemm / rc_score
+ *     of csrc/pfr_pairtile.h: the bits of pfr_pair_scores_gather;  s >= thr  as an IEEE comparison, so a NaN score never qualifies).
+ *     b == NULL: symmetric mode, every unordered pair i < j of a once; otherwise every pair of the two sets (the caller passes DISJOINT
+ *     blocks of one node set).  Node ids: u = a_off + i, v = b_off + j (symmetric: v = a_off + j), all below n_nodes.
+ *   Definition, over the unordered pairs i < j of ONE node set:
+ *     deg[x]  = the number of OTHER nodes whose score with x qualifies.
+ *     x is CORE iff deg[x] >= min_neighbors;  min_neighbors = min_samples - 1: the point itself counts towards min_samples (scikit-learn).
+ *     CLUSTERS are the connected components of the core nodes over the qualifying core-core pairs; a cluster's label is its SMALLEST
+ *       CORE INDEX.
+ *     A non-core node with at least one qualifying core neighbour is a BORDER node: it takes the cluster of the core neighbour with the
+ *       HIGHEST score, ties go to the SMALLEST index; -0.0 is canonicalised to +0.0 (s + 0.0f) before the comparison.  (This rule is
+ *       this library's: scikit-learn gives a border node to whichever cluster reaches it first in its visiting order.)
+ *     Every other node is NOISE: label -1.
+ *     The result does not depend on scheduling, chunking or the number of calls: two runs give the same labels.
+ * pfr_neighbor_count: for every visited qualifying pair (u, v), deg[u] += 1 and deg[v] += 1 (int32 [n_nodes], agent-scope relaxed atomic
+ *   adds; deg is ACCUMULATED, the caller zeroes it, block launches add up).  The adds are reduced inside the wave first: a column's count
+ *   is the population count of the lane's mask bits plus the same from the lane 32 away, a row's count is a wave vote over the 32 lanes
+ *   that share the row; one add per touched row or column per wave and tile.
+ * pfr_dbscan_link: deg is the finished output of pfr_neighbor_count (an earlier launch; read with plain loads).  parent int32 [n_nodes] as
+ *   for pfr_pairs_above (0, 1, 2, ... on entry, calls accumulate), best u64 [n_nodes] zeroed by the caller, status int32 zeroed by the
+ *   caller.  For every visited qualifying pair: both core -> the union of pfr_pairs_above (same loop cap of 6 * n_nodes + 64 iterations,
+ *   same *status != 0 when it is reached or a parent outside [0, x] is read: never a hang, never a stray access); exactly one core c, the
+ *   other node x -> an agent-scope atomic maximum on best[x] with the key
+ *       (ord(s) << 32) | (0xffffffff - c),   ord(s) = bits(s + 0.0f) with all bits flipped when negative, the sign bit flipped otherwise
+ *   (an order-preserving map of the floats to uint32), so that the maximum is "highest score, then smallest index"; best[x] == 0 means "no
+ *   core neighbour": every real key is > 0.  Neither core -> nothing.
+ * pfr_dbscan_labels: one thread per node.  Core -> the root of its tree (the read-only walk of pfr_cc_flatten, at most n_nodes steps,
+ *   every parent range-checked); border -> the root of the core decoded from best (a key that decodes outside [0, n_nodes) is noise, never
+ *   an index); noise -> -1.  labels int32 [n_nodes] must not alias the inputs.  A launch of its own, after every pfr_dbscan_link launch.
+ * Errors (PFR_ERR_ARG, nothing launched or written): those of pfr_pairs_above — null or host pointers, a bad dtype or D, int8 rows
+ *   without their scales, negative sizes or offsets — and  a_off + Na > n_nodes,  b_off + Nb > n_nodes  (no node is skipped silently),
+ *   min_neighbors < 0.  Na == 0, Nb == 0, a symmetric Na == 1 (and n_nodes == 0 for the label pass) do nothing and return 0.
+ * NOT COVERED.  Two-set (gallery against query) DBSCAN, average linkage, HDBSCAN / OPTICS, Chinese whispers; a threshold so low that the
+ *   graph is near complete (correct, slow, not measured: as pfr_pairs_above). */
+int pfr_neighbor_count(const void* a, const float* a_scale, int Na, int a_off, const void* b, const float* b_scale, int Nb, int b_off,
+                       int dtype, int D, float thr, int* deg, int n_nodes, pfr_stream_t stream);
+int pfr_dbscan_link(const void* a, const float* a_scale, int Na, int a_off, const void* b, const float* b_scale, int Nb, int b_off,
+                    int dtype, int D, float thr, const int* deg, int min_neighbors, int* parent, unsigned long long* best, int n_nodes,
+                    int* status, pfr_stream_t stream);
+int pfr_dbscan_labels(const int* parent, const int* deg, const unsigned long long* best, int min_neighbors, int n_nodes, int* labels,
+                      pfr_stream_t stream);
 
 /* ---- k-reciprocal re-ranking of match lists (Zhong et al., "Re-ranking Person Re-identification with k-reciprocal Encoding", CVPR 2017)
  * on SPARSE rows: nothing N x N is built.  The set is N items with unit-norm fp32 rows emb32 [N][D].

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import metrics as M
-from ..match import recall_at_k, pair_similarity, pair_histogram, positive_ranks, cluster
+from ..match import recall_at_k, pair_similarity, pair_histogram, positive_ranks, cluster, dbscan
 
 
 class Controller(nn.Module):
@@ -167,6 +167,30 @@ class Controller(nn.Module):
         out.update((f'Clusters thr={t}', st.clusters) for t, st in zip(thrs, stats))
         return out
 
+    def _dbscan(self, emb, classes, ps):
+        """Opt-in (config.dbscan = dict(thresholds=[0.8, 'opt', …], min_samples=4)): DBSCAN identity clustering of the set at each
+        threshold (match.dbscan: two passes of the match GEMM on the device), scored against the classes with every noise item as a
+        cluster of its own (engine.metrics.ClusterStats(noise=-1)): pairwise F / precision / recall, BCubed F, the number of clusters and
+        the number of noise items.  Thresholds are similarities with the conversion and the 'opt' of `_cluster`."""
+        db = self.config.get('dbscan')
+        if db is None:
+            return {}
+        db = dict(db)
+        thrs, ms = list(db.get('thresholds', ())), db.get('min_samples', 4)
+        dt = torch.float32 if not emb.is_cuda else getattr(self.config, 'match_dtype', torch.bfloat16)
+        stats = []
+        for t in thrs:
+            sim = float(ps.opt_threshold()) if isinstance(t, str) and t == 'opt' else float(t)
+            stats.append(M.ClusterStats(dbscan(emb, 2.0 * sim - 1.0, min_samples=ms, compute_dtype=dt), classes, noise=-1))
+        out = {}
+        out.update((f'DBSCAN F thr={t}', st.pairwise()[2]) for t, st in zip(thrs, stats))
+        out.update((f'DBSCAN precision thr={t}', st.pairwise()[0]) for t, st in zip(thrs, stats))
+        out.update((f'DBSCAN recall thr={t}', st.pairwise()[1]) for t, st in zip(thrs, stats))
+        out.update((f'DBSCAN BCubed F thr={t}', st.bcubed()[2]) for t, st in zip(thrs, stats))
+        out.update((f'DBSCAN clusters thr={t}', st.clusters) for t, st in zip(thrs, stats))
+        out.update((f'DBSCAN noise thr={t}', st.noise) for t, st in zip(thrs, stats))
+        return out
+
     def test_epoch_end(self, outputs):
         all_metrics = {}
         for i in range(len(outputs)):
@@ -181,6 +205,7 @@ class Controller(nn.Module):
             metrics.update(self._rerank_recall(emb, classes, [10, 100]))
             metrics.update(self._retrieval(emb, classes))
             metrics.update(self._cluster(emb, classes, ps))
+            metrics.update(self._dbscan(emb, classes, ps))
             print('', *[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')
             all_metrics[name] = metrics
         self.last_metrics = all_metrics
@@ -232,6 +257,7 @@ class Controller(nn.Module):
             metrics.update(self._rerank_recall(emb, classes, ks))
             metrics.update(self._retrieval(emb, classes))
             metrics.update(self._cluster(emb, classes, ps))
+            metrics.update(self._dbscan(emb, classes, ps))
             all_metrics[name] = metrics
             self.last_confmat[name] = confmat
             print(*[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')

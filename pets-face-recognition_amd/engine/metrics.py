@@ -244,14 +244,24 @@ class ClusterStats:
     arithmetic, nothing cluster x class is built.  With a_k = Σ_c n_kc (cluster sizes) and b_c = Σ_k n_kc (class sizes):
       pairwise  TP = Σ n_kc (n_kc - 1) / 2;  precision = TP / Σ a_k (a_k - 1) / 2;  recall = TP / Σ b_c (b_c - 1) / 2
       BCubed    precision = (1 / N) Σ n_kc² / a_k;  recall = (1 / N) Σ n_kc² / b_c       (float64 sums on the host)
-      F = 2 P R / (P + R).  A ratio with a zero denominator is NaN ("nothing to measure")."""
+      F = 2 P R / (P + R).  A ratio with a zero denominator is NaN ("nothing to measure").
+    `noise` (e.g. -1 for match.dbscan): the items with that label belong to no cluster — each is scored as a cluster of ONE (no predicted
+    pair, BCubed precision 1), not all of them as one big cluster; `self.noise` is their count, `clusters` and `singletons` leave them
+    out, and metrics() appends a 'noise' key.  noise=None: nothing changes."""
 
-    def __init__(self, labels, classes):
+    def __init__(self, labels, classes, noise=None):
         k = torch.as_tensor(labels).detach().cpu().long().reshape(-1)
         c = torch.as_tensor(classes).detach().cpu().long().reshape(-1)
         if k.numel() != c.numel():
             raise ValueError("ClusterStats: labels [N] with classes [N]")
         self.n = int(k.numel())
+        self.noise = None
+        if noise is not None:
+            is_noise = k == int(noise)
+            self.noise = int(is_noise.sum())
+            if self.noise:      # every noise item gets a label of its own: ranks after the clusters' (torch.unique below sees ranks only)
+                k = torch.unique(k, return_inverse=True)[1]
+                k[is_noise] = self.n + torch.arange(self.noise)
         uk, ik, a = torch.unique(k, return_inverse=True, return_counts=True)
         uc, ic, b = torch.unique(c, return_inverse=True, return_counts=True)
         # one int64 key per item: (cluster rank, class rank)
@@ -259,8 +269,8 @@ class ClusterStats:
         ak, bc = a[key // max(int(uc.numel()), 1)], b[key % max(int(uc.numel()), 1)]
         pairs = lambda x: int((x * (x - 1) // 2).sum())
         self.tp, self.cluster_pairs, self.class_pairs = pairs(n), pairs(a), pairs(b)
-        self.clusters = int(uk.numel())
-        self.singletons = int((a == 1).sum())
+        self.clusters = int(uk.numel()) - (self.noise or 0)
+        self.singletons = int((a == 1).sum()) - (self.noise or 0)
         n2 = n.double() * n.double()
         self._b3p = float((n2 / ak.double()).sum()) / self.n if self.n else float('nan')
         self._b3r = float((n2 / bc.double()).sum()) / self.n if self.n else float('nan')
@@ -285,8 +295,11 @@ class ClusterStats:
     def metrics(self):
         p, r, f = self.pairwise()
         bp, br, bf = self.bcubed()
-        return {'pairwise_precision': p, 'pairwise_recall': r, 'pairwise_f': f, 'bcubed_precision': bp, 'bcubed_recall': br,
-                'bcubed_f': bf, 'clusters': self.clusters, 'singletons': self.singletons}
+        out = {'pairwise_precision': p, 'pairwise_recall': r, 'pairwise_f': f, 'bcubed_precision': bp, 'bcubed_recall': br,
+               'bcubed_f': bf, 'clusters': self.clusters, 'singletons': self.singletons}
+        if self.noise is not None:
+            out['noise'] = self.noise
+        return out
 
 
 # ---- function forms (one sort per call)

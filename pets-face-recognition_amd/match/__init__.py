@@ -1144,7 +1144,7 @@ def cluster(emb, threshold, compute_dtype=torch.float32, normalize=True, chunk=N
     column block) of that many rows with node offsets), then pfr_cc_flatten; a non-zero status word of the union-find's loop caps raises a
     PfrError.  CPU tensors: a host union-find over the edges of the CPU `pairs_above`.
     Not covered: a threshold so low that the graph is near complete costs ~N^2 / 2 finds on the device (correct, slow, not measured); only
-    single linkage — no average linkage, DBSCAN or Chinese whispers."""
+    single linkage here — `dbscan` is the density-based variant (noise, core points); no average linkage or Chinese whispers."""
     who = "cluster"
     _check_pair_sets(who, emb, None, compute_dtype)
     if chunk is not None and int(chunk) < 1:
@@ -1160,24 +1160,147 @@ def cluster(emb, threshold, compute_dtype=torch.float32, normalize=True, chunk=N
     thr = _fp32(threshold)
     a, sa = _hist_operand(emb, compute_dtype, normalize)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    T, Dp = dtype_id(compute_dtype), a.shape[1]
-    step = N if chunk is None else int(chunk)
-    sp = lambda r0: 0 if sa is None else sa[r0:].data_ptr()
-    for r0 in range(0, N, step):
-        nr = min(step, N - r0)
-        for c0 in range(r0, N, step):
-            nc = min(step, N - c0)
-            if c0 == r0:     # the block's own pairs: symmetric mode
-                lib.pfr_pairs_above(a[r0:].data_ptr(), sp(r0), nr, r0, 0, 0, 0, 0, T, Dp, thr, 0, 0, 0, 0, 0, parent.data_ptr(), N,
-                                    status.data_ptr(), _stream())
-            else:
-                lib.pfr_pairs_above(a[r0:].data_ptr(), sp(r0), nr, r0, a[c0:].data_ptr(), sp(c0), nc, c0, T, Dp, thr, 0, 0, 0, 0, 0,
-                                    parent.data_ptr(), N, status.data_ptr(), _stream())
+    _block_launches(lib.pfr_pairs_above, a, sa, N, chunk, (dtype_id(compute_dtype), a.shape[1], thr),
+                    (0, 0, 0, 0, 0, parent.data_ptr(), N, status.data_ptr(), _stream()))
     labels = torch.empty(N, dtype=torch.int32, device=dev)
     lib.pfr_cc_flatten(parent.data_ptr(), N, labels.data_ptr(), _stream())
     if int(status.item()) != 0:
         raise PfrError(f"{who}: the union-find gave up on a pair (status {int(status.item())}): a loop reached its iteration cap")
     return labels.long()
+
+
+def _check_chunk(who, chunk):
+    if chunk is not None and int(chunk) < 1:
+        raise PfrError(f"{who}: chunk={chunk} must be >= 1")
+
+
+def _block_launches(fn, a, sa, N, chunk, head, tail):
+    """one `fn` launch per (row block, column block) of the upper triangle with node offsets — the blocks of `cluster`; `head` are the
+    arguments between b_off and the outputs (dtype, D, thr), `tail` the outputs and what follows them"""
+    step = N if chunk is None else int(chunk)
+    sp = lambda r0: 0 if sa is None else sa[r0:].data_ptr()
+    for r0 in range(0, N, step):
+        nr = min(step, N - r0)
+        for c0 in range(r0, N, step):
+            if c0 == r0:     # the block's own pairs: symmetric mode
+                fn(a[r0:].data_ptr(), sp(r0), nr, r0, 0, 0, 0, 0, *head, *tail)
+            else:
+                fn(a[r0:].data_ptr(), sp(r0), nr, r0, a[c0:].data_ptr(), sp(c0), min(step, N - c0), c0, *head, *tail)
+
+
+def _neighbor_counts_dev(a, sa, N, T, thr, chunk):
+    deg = torch.zeros(N, dtype=torch.int32, device=a.device)
+    _block_launches(lib.pfr_neighbor_count, a, sa, N, chunk, (T, a.shape[1], thr), (deg.data_ptr(), N, _stream()))
+    return deg
+
+
+def _unit_rows_f32(emb, normalize):
+    x = emb.float()
+    return x / x.norm(dim=1, keepdim=True).clamp_min(1e-12) if normalize else x
+
+
+def _neighbor_counts_torch(emb, thr, normalize, chunk=2048):
+    """degrees from the chunks of `_pairs_above_torch`'s rule (s >= thr, NaN never, self excluded) -> int64 [N]"""
+    a = _unit_rows_f32(emb, normalize)
+    N = a.shape[0]
+    deg = torch.zeros(N, dtype=torch.int64)
+    for r0 in range(0, N, chunk):
+        ok = (a[r0:r0 + chunk] @ a.t()) >= thr
+        ok &= torch.arange(r0, r0 + ok.shape[0])[:, None] != torch.arange(N)[None, :]
+        deg[r0:r0 + ok.shape[0]] = ok.sum(dim=1)
+    return deg
+
+
+def neighbor_counts(emb, threshold, compute_dtype=torch.float32, normalize=True, chunk=None):
+    """How crowded is every item's neighbourhood: → int64 [N], the number of OTHER items of `emb` [N, D] whose score with the item is at or
+    above `threshold` (the score and the rule of `pairs_above`; the item itself is excluded).  CUDA tensors: pfr_neighbor_count, the match
+    GEMM with a degree epilogue (one launch, or with `chunk` one per (row block, column block) as in `cluster`); nothing N x N is written.
+    CPU tensors: chunked fp32 matmul, same rule."""
+    who = "neighbor_counts"
+    _check_pair_sets(who, emb, None, compute_dtype)
+    _check_chunk(who, chunk)
+    thr = _fp32(threshold)
+    if not emb.is_cuda:
+        return _neighbor_counts_torch(emb, thr, normalize)
+    N = emb.shape[0]
+    if N < 2:
+        return torch.zeros(N, dtype=torch.int64, device=emb.device)
+    a, sa = _hist_operand(emb, compute_dtype, normalize)
+    return _neighbor_counts_dev(a, sa, N, dtype_id(compute_dtype), thr, chunk).long()
+
+
+def _dbscan_torch(emb, thr, min_neighbors, normalize, chunk=2048):
+    """the contract of pfr_dbscan_link / pfr_dbscan_labels on the host: degrees, a union-find over the core-core edges, and for every
+    non-core item the core neighbour with the largest (score, -index) — -0.0 canonicalised by s + 0.0 — or noise"""
+    a = _unit_rows_f32(emb, normalize)
+    N = a.shape[0]
+    core = _neighbor_counts_torch(emb, thr, normalize, chunk) >= min_neighbors
+    idx = torch.arange(N)
+    ii, jj = [], []
+    best = torch.full((N,), -1, dtype=torch.int64)
+    for r0 in range(0, N, chunk):
+        s = a[r0:r0 + chunk] @ a.t()
+        rows = idx[r0:r0 + s.shape[0]]
+        ok = (s >= thr) & (rows[:, None] != idx[None, :]) & core[None, :]          # qualifying pairs whose column is core
+        i, j = (ok & core[rows][:, None] & (rows[:, None] < idx[None, :])).nonzero(as_tuple=True)
+        ii.append(i + r0); jj.append(j)
+        sc = torch.where(ok, s + 0.0, torch.full_like(s, float("-inf")))
+        top = sc.max(dim=1, keepdim=True).values
+        first = (ok & (sc == top)).int().argmax(dim=1)                              # (argmax of a 0/1 row: the first, i.e. smallest, index)
+        has = ok.any(dim=1) & ~core[rows]
+        best[rows[has]] = first[has]
+    comp = _host_components(N, torch.cat(ii) if ii else torch.zeros(0, dtype=torch.int64), torch.cat(jj) if jj else torch.zeros(0, dtype=torch.int64))
+    labels = torch.where(core, comp, torch.full_like(comp, -1))
+    border = best >= 0
+    labels[border] = comp[best[border]]
+    return labels, core
+
+
+def dbscan(emb, threshold, min_samples=4, compute_dtype=torch.float32, normalize=True, chunk=None, return_core=False):
+    """DBSCAN identity clustering at a threshold (the definition of include/pfr_hip.h): an item is CORE when at least `min_samples` items —
+    itself included, as in scikit-learn — score at or above `threshold` with it (the score and the rule of `pairs_above`); clusters are the
+    connected components of the core items over the qualifying core-core pairs, labelled by their smallest core index; a non-core item with
+    a qualifying core neighbour is a BORDER item of the cluster of its highest-scoring core neighbour (ties: the smallest index); every
+    other item is NOISE, label -1.  → labels int64 [N] (and the bool core mask [N] with return_core=True).  Unlike single linkage
+    (`cluster`), one stray item that scores above the threshold against two animals does not merge them unless it is core itself, and items
+    that belong to nothing are not counted as clusters.  `dbscan(x, t, min_samples=1)` equals `cluster(x, t)`: every item is core.
+    CUDA tensors: two passes of the match GEMM — pfr_neighbor_count (degree epilogue), then pfr_dbscan_link (union-find over core-core
+    pairs, an atomic maximum for the border items) — and pfr_dbscan_labels; nothing N x N and no edge list is written; with `chunk` one
+    launch per (row block, column block) for BOTH passes, as in `cluster`; a non-zero status word raises a PfrError.  CPU tensors: chunked
+    fp32 matmul and a host union-find, same rule.
+    Not covered: two-set DBSCAN, average linkage, HDBSCAN / OPTICS; a near-complete graph is correct and slow, as for `cluster`."""
+    who = "dbscan"
+    _check_pair_sets(who, emb, None, compute_dtype)
+    _check_chunk(who, chunk)
+    if isinstance(min_samples, bool) or not isinstance(min_samples, int) or min_samples < 1:
+        raise PfrError(f"{who}: min_samples={min_samples!r} must be an int >= 1")
+    mn = min_samples - 1
+    thr = _fp32(threshold)
+    N = emb.shape[0]
+    if not emb.is_cuda:
+        labels, core = _dbscan_torch(emb, thr, mn, normalize)
+        return (labels, core) if return_core else labels
+    dev = emb.device
+    if N < 2:
+        core = torch.full((N,), mn == 0, dtype=torch.bool, device=dev)
+        labels = torch.where(core, torch.arange(N, device=dev), torch.full((N,), -1, dtype=torch.int64, device=dev))
+        return (labels, core) if return_core else labels
+    if mn >= 2 ** 31:
+        raise PfrError(f"{who}: min_samples={min_samples} does not fit int32")
+    a, sa = _hist_operand(emb, compute_dtype, normalize)
+    T = dtype_id(compute_dtype)
+    head = (T, a.shape[1], thr)
+    deg = _neighbor_counts_dev(a, sa, N, T, thr, chunk)
+    parent = torch.arange(N, dtype=torch.int32, device=dev)
+    best = torch.zeros(N, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _block_launches(lib.pfr_dbscan_link, a, sa, N, chunk, head, (deg.data_ptr(), mn, parent.data_ptr(), best.data_ptr(), N, status.data_ptr(),
+                                                                _stream()))
+    labels = torch.empty(N, dtype=torch.int32, device=dev)
+    lib.pfr_dbscan_labels(parent.data_ptr(), deg.data_ptr(), best.data_ptr(), mn, N, labels.data_ptr(), _stream())
+    if int(status.item()) != 0:
+        raise PfrError(f"{who}: the union-find gave up on a pair (status {int(status.item())}): a loop reached its iteration cap")
+    return (labels.long(), deg >= mn) if return_core else labels.long()
 
 
 def cluster_metrics(labels, classes):
