@@ -74,7 +74,10 @@ int pfr_tuning_epoch(void);
  *   family 6 streaming Linear (pfr_slin.hip)          bits 0-2 epilogue: 0 plain 1 bias 2 bias + residual 3 GELU 4 GELU backward; bits 4-11 panel
  *   family 7 weight-gradient tile (pfr_wgrad.hip)     bits 0-1 the "wgrad_tile" number (bit 0: 64 couts, bit 1: 64 k columns; clear: 128),
  *                                                     bit 2 fused prologue, bits 8-23 splits
- *   family 8 256x256 weight-gradient tile, 9 streaming 1x1 weight gradient, 10 halo-staged 3x3 weight gradient:  bits 8-23 slabs written */
+ *   family 8 256x256 weight-gradient tile, 9 streaming 1x1 weight gradient, 10 halo-staged 3x3 weight gradient:  bits 8-23 slabs written
+ *   family 11 match filter (pfr_match_scores_filter / _i8): bits 0-2 tile (0 or 4), bit 3 KCH 8, bit 4 (16) several tiles per workgroup,
+ *                                                     bit 5 (32) L2-blocked tile order ("match_order"), bits 6-7 element type 0 f32 1 bf16
+ *                                                     2 i8, bits 8-11 query tiles per super-step of the blocked order (0: linear order) */
 int pfr_debug_last_conv_kernel(void);
 
 /* C-side executor of a pre-built launch plan (csrc/pfr_plan.hip): the host keeps a step's fixed list of C-ABI calls (fixed device

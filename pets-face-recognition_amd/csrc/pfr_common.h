@@ -94,7 +94,7 @@ extern thread_local hipEvent_t pfr_tls_stop_event;
 // Host bookkeeping only: no device work, and nothing in dispatch reads it back.
 enum PfrConvKernel {
   PFR_CK_NONE, PFR_CK_TILE, PFR_CK_PERSISTENT, PFR_CK_SCONV, PFR_CK_SCONV3, PFR_CK_SSTEM, PFR_CK_SLIN, PFR_CK_WGRAD_TILE, PFR_CK_WGRAD_BIG,
-  PFR_CK_SWGRAD, PFR_CK_WGRAD9
+  PFR_CK_SWGRAD, PFR_CK_WGRAD9, PFR_CK_MATCH_FILTER
 };
 extern thread_local int pfr_tls_last_conv_kernel;
 static inline void pfr_note_conv_kernel(int family, int detail) { pfr_tls_last_conv_kernel = (family << 24) | detail; }

@@ -1407,6 +1407,9 @@ static int launch_filter_k(IgemmParams& p, hipStream_t st) {
     p.fo_qg = qg;
     p.fo_gg = wpx / qg;
   }
+  // launch identity (pfr_debug_last_conv_kernel): tile, tiles per workgroup, tile order, element type
+  pfr_note_conv_kernel(PFR_CK_MATCH_FILTER, pfr_ck_tile(BQ, BP) | (KCH == 8 ? 8 : 0) | (total > slots ? 16 : 0) | (p.fo_qg > 0 ? 32 : 0) |
+                                                ((sizeof(T) == 4 ? 0 : (sizeof(T) == 2 ? 1 : 2)) << 6) | (p.fo_qg << 8));
   hipLaunchKernelGGL((igemm_kernel<T, float, BQ, BP, false, true, KCH, NW, WP, 2, true>), grid, block, 0, st, p);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
