@@ -41,8 +41,13 @@ def main(argv=None):
                     help="also report 'DBSCAN F / precision / recall / BCubed F / clusters / noise thr=…': DBSCAN identity clustering "
                          "(match.dbscan) with MIN_SAMPLES items (the item itself included) per core neighbourhood at these similarity "
                          "thresholds; 'opt' stands for the run's optimal threshold, e.g. 4 0.8 opt")
+    ap.add_argument('--quality', action='store_true',
+                    help="also report 'Quality mean norm' (mean length of the embeddings, match.embedding_quality) and 'Quality AUC' (how "
+                         "well the smaller length of a genuine pair tells the high-scoring pairs from the low-scoring ones)")
     args = ap.parse_args(argv)
     config = get_config(args.config)
+    if args.quality:
+        config['quality'] = True
     if args.rerank is not None:
         config['rerank'] = dict(k1=int(args.rerank[0]), k2=int(args.rerank[1]), lambda_value=float(args.rerank[2]))
     if args.retrieval is not None:

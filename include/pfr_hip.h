@@ -386,6 +386,39 @@ int pfr_margin_ce_adaptive(const float* cos, const int64_t* label, int B, int C,
 int pfr_margin_bwd_adaptive(const float* cos, const int64_t* label, int B, int C, int ldc, int kind, float s, float m, float eps,
                             const float* row_margin, const float* state_used, const float* dlogits, void* dcos, int dcos_dtype,
                             pfr_stream_t stream);
+/* MagFace (Meng et al., CVPR 2021; not in the reference): the margin grows with the embedding's length a = clamp(|x|, l_a, u_a),
+ * m = (u_m - l_m) / (u_a - l_a) * (a - l_a) + l_m, and g(a) = a / u_a^2 + 1 / a is a regulariser on the length.  The first head here
+ * whose gradient has a radial part: d loss / d |x| flows through m on the target logit and through g.
+ * pfr_magface_prepare: inv_norm [B] as pfr_l2norm_fwd wrote it (|x| = 1 / inv_norm, taken in fp32) -> row_margin [B][2] = {m, dm / d|x|}
+ *   and row_reg [B][2] = {g(a), dg / d|x|}; both derivatives are 0 where the clamp is active (|x| < l_a or |x| > u_a; |x| equal to a
+ *   bound counts as inside, as torch.clamp's autograd does).  Per-row arithmetic in fp64 rounded once, no sums, nothing read by the host.
+ * pfr_margin_ce_magface: pfr_margin_ce_adaptive's row kernel (same logits / loss_rows / row_stats / grad_scale* / dcos conventions, plain
+ *   and focal cross-entropy, class weights, label smoothing) with the MagFace margin: cos clamped to [-1, 1]; target
+ *   phi = cos * cos m - sqrt(1 - cos^2) * sin m where cos > 0 (easy_margin != 0: else cos) or cos > cos(pi - m) (easy_margin == 0: else
+ *   cos - m sin m), l_t = s * phi.  dnorm [B] fp32 or NULL = d(reduced loss) / d|x| with dcos's gradient scale:
+ *   (d loss / d l_t) * s * (d phi / d m) * row_margin[i][1]  +  reg_scale * (*grad_scale_dev) * row_reg[i][1],
+ *   d phi / d m = -sin(theta + m) where the margin is applied, else 0 (easy) or -(sin m + m cos m) (hard).  reg_scale is lambda_g / B
+ *   for a mean reduction and lambda_g for 'sum'; row_reg may be NULL when reg_scale is 0.
+ * pfr_margin_bwd_magface: pfr_margin_bwd_adaptive for this margin, dcos = s * dlogits * d l / d cos, and
+ *   dnorm[i] = dlogits[i][t_i] * s * (d phi / d m) * row_margin[i][1] + reg_scale * (*reg_scale_dev or 1) * row_reg[i][1].
+ * pfr_magface_loss: pfr_loss_reduce plus the regulariser in one launch of one workgroup, fixed order: out_reg = lambda_g * sum_i
+ *   row_reg[i][0] / (1 for reduction 1 'sum', else n), out_loss = sum(loss_rows) / d + out_reg (d as pfr_loss_reduce).  loss_rows NULL:
+ *   out_reg alone (out_loss / out_inv_denom may then be NULL).
+ * pfr_l2norm_bwd_radial: pfr_l2norm_bwd plus the radial term, dx = inv_norm * (dxn - xn (xn . dxn)) + dnorm[row] * x[row] * inv_norm[row],
+ *   in one pass; same dtypes and `accumulate`.  dnorm NULL: pfr_l2norm_bwd's kernel itself, the same bits. */
+int pfr_magface_prepare(const float* inv_norm, int B, float l_a, float u_a, float l_m, float u_m, float* row_margin, float* row_reg,
+                        pfr_stream_t stream);
+int pfr_margin_ce_magface(const float* cos, const int64_t* label, int B, int C, int ldc, int easy_margin, float s, float gamma,
+                          const float* class_weight, float label_smoothing, const float* row_margin, const float* row_reg,
+                          float reg_scale, float grad_scale, const float* grad_scale_dev, const float* grad_scale_dev2, float* logits,
+                          float* loss_rows, float* row_stats, void* dcos, int dcos_dtype, float* dnorm, pfr_stream_t stream);
+int pfr_margin_bwd_magface(const float* cos, const int64_t* label, int B, int C, int ldc, int easy_margin, float s,
+                           const float* row_margin, const float* row_reg, float reg_scale, const float* reg_scale_dev,
+                           const float* dlogits, void* dcos, int dcos_dtype, float* dnorm, pfr_stream_t stream);
+int pfr_magface_loss(const float* loss_rows, const float* row_stats, const float* row_reg, int n, int reduction, float lambda_g,
+                     float* out_loss, float* out_inv_denom, float* out_reg, pfr_stream_t stream);
+int pfr_l2norm_bwd_radial(const void* x, int in_dtype, const float* inv_norm, const float* dxn, const float* dnorm, void* dx,
+                          int out_dtype, int rows, int D, int accumulate, pfr_stream_t stream);
 
 /* ---- optimiser steps over flat fp32 master buffers (configs/dog_fe/fe_dogs_config.py:123-133; body_dog_fe.py:121-131) */
 int pfr_sgd_step(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,

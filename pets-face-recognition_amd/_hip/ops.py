@@ -491,6 +491,91 @@ def margin_bwd_adaptive(cosv, label, C, kind, s, m, eps, row_margin, state_used,
     return dcos
 
 
+def magface_prepare(inv_norm, l_a, u_a, l_m, u_m):
+    """inv_norm [B] (l2norm_fwd) -> (row_margin [B, 2] = {m, dm/d|x|}, row_reg [B, 2] = {g(a), dg/d|x|}); the derivatives are 0 where
+    |x| lies outside [l_a, u_a]"""
+    if not 0.0 < l_a < u_a:
+        raise PfrError(f"magface_prepare: need 0 < l_a < u_a, got {l_a}, {u_a}")
+    _chk(inv_norm, "magface_prepare: inv_norm")
+    if inv_norm.dim() != 1 or inv_norm.dtype != torch.float32:
+        raise PfrError("magface_prepare: inv_norm must be an fp32 [B] tensor")
+    B = inv_norm.numel()
+    row_margin = torch.empty((B, 2), dtype=torch.float32, device=inv_norm.device)
+    row_reg = torch.empty((B, 2), dtype=torch.float32, device=inv_norm.device)
+    lib.pfr_magface_prepare(_p(inv_norm), B, float(l_a), float(u_a), float(l_m), float(u_m), _p(row_margin), _p(row_reg), _stream())
+    return row_margin, row_reg
+
+
+def margin_ce_magface(cosv, label, C, easy_margin, s, row_margin, row_reg, reg_scale=0.0, gamma=0.0, class_weight=None, label_smoothing=0.0,
+                      grad_scale=1.0, grad_scale_dev=None, grad_scale_dev2=None, want_logits=True, want_stats=True, dcos_dtype=None):
+    """margin_ce_adaptive for MagFace -> (logits, loss_rows, row_stats [B, 4], dcos, dnorm [B]); dnorm (with dcos only) is
+    d loss / d |x| at dcos's gradient scale, the regulariser's reg_scale * grad_scale_dev * dg/d|x| included"""
+    _chk_cos_label(cosv, label, C, "margin_ce_magface")
+    B, ldc = cosv.shape
+    _chk_f32(row_margin, (B, 2), cosv.device, "margin_ce_magface: row_margin")
+    if row_reg is not None:
+        _chk_f32(row_reg, (B, 2), cosv.device, "margin_ce_magface: row_reg")
+    _chk_class_vector(class_weight, C, cosv.device, "margin_ce_magface: class_weight")
+    if dcos_dtype not in (None, torch.float32, torch.bfloat16):
+        raise PfrError(f"margin_ce_magface: dcos dtype must be fp32 or bf16, got {dcos_dtype}")
+    logits = torch.empty((B, C), dtype=torch.float32, device=cosv.device) if want_logits else None
+    loss_rows = torch.empty(B, dtype=torch.float32, device=cosv.device)
+    stats = torch.empty((B, 4), dtype=torch.float32, device=cosv.device) if want_stats else None
+    dcos = None if dcos_dtype is None else torch.zeros((B, ldc), dtype=dcos_dtype, device=cosv.device)
+    dnorm = None if dcos_dtype is None else torch.empty(B, dtype=torch.float32, device=cosv.device)
+    lib.pfr_margin_ce_magface(_p(cosv), _p(label), B, C, ldc, int(bool(easy_margin)), float(s), float(gamma), _p(class_weight),
+                              float(label_smoothing), _p(row_margin), _p(row_reg), float(reg_scale), float(grad_scale), _p(grad_scale_dev),
+                              _p(grad_scale_dev2), _p(logits), _p(loss_rows), _p(stats), _p(dcos),
+                              PFR_F32 if dcos is None else dtype_id(dcos.dtype), _p(dnorm), _stream())
+    return logits, loss_rows, stats, dcos, dnorm
+
+
+def margin_bwd_magface(cosv, label, C, easy_margin, s, row_margin, row_reg, reg_scale, reg_scale_dev, dlogits, dcos_dtype):
+    """dlogits [B, C] fp32 -> (dcos [B, ldc] (pad columns 0), dnorm [B]) through the MagFace margin; dnorm also carries
+    reg_scale * reg_scale_dev * dg/d|x| (reg_scale_dev: the regulariser's incoming gradient, a device scalar, or None = 1)"""
+    _chk_cos_label(cosv, label, C, "margin_bwd_magface")
+    B, ldc = cosv.shape
+    _chk_f32(row_margin, (B, 2), cosv.device, "margin_bwd_magface: row_margin")
+    if row_reg is not None:
+        _chk_f32(row_reg, (B, 2), cosv.device, "margin_bwd_magface: row_reg")
+    _chk_f32(dlogits, (B, C), cosv.device, "margin_bwd_magface: dlogits")
+    if dcos_dtype not in (torch.float32, torch.bfloat16):
+        raise PfrError(f"margin_bwd_magface: dcos dtype must be fp32 or bf16, got {dcos_dtype}")
+    dcos = torch.zeros((B, ldc), dtype=dcos_dtype, device=cosv.device)
+    dnorm = torch.empty(B, dtype=torch.float32, device=cosv.device)
+    lib.pfr_margin_bwd_magface(_p(cosv), _p(label), B, C, ldc, int(bool(easy_margin)), float(s), _p(row_margin), _p(row_reg),
+                               float(reg_scale), _p(reg_scale_dev), _p(dlogits), _p(dcos), dtype_id(dcos_dtype), _p(dnorm), _stream())
+    return dcos, dnorm
+
+
+def magface_loss(loss_rows, row_stats, row_reg, reduction, lambda_g):
+    """loss_reduce with MagFace's regulariser -> (loss incl. the regulariser, 1 / denominator, regulariser), device scalars;
+    loss_rows None -> (None, None, regulariser)"""
+    n = row_reg.shape[0]
+    dev = row_reg.device
+    reg = torch.empty((), dtype=torch.float32, device=dev)
+    out = inv = None
+    if loss_rows is not None:
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        inv = torch.empty((), dtype=torch.float32, device=dev)
+    lib.pfr_magface_loss(_p(loss_rows), _p(row_stats), _p(row_reg), n, LOSS_REDUCTIONS[reduction], float(lambda_g), _p(out), _p(inv), _p(reg),
+                         _stream())
+    return out, inv, reg
+
+
+def l2norm_bwd_radial(x, inv, dxn, dnorm, out_dtype, out=None, accumulate=False):
+    """l2norm_bwd plus dnorm[row] * x[row] / |x[row]| in the same pass; dnorm None is l2norm_bwd itself"""
+    rows, D = x.shape
+    assert dxn.dtype == torch.float32
+    if dnorm is not None:
+        _chk_f32(dnorm, (rows,), x.device, "l2norm_bwd_radial: dnorm")
+    if out is None:
+        out = torch.empty((rows, D), dtype=out_dtype, device=x.device)
+    lib.pfr_l2norm_bwd_radial(_p(x), dtype_id(x.dtype), _p(inv), _p(dxn), _p(dnorm), _p(out), dtype_id(out.dtype), rows, D, int(accumulate),
+                              _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ optimisers
 def sgd_step(p, g, mom, shadow, lr, momentum, weight_decay, grad_scale=1.0, first_step=False):
     lib.pfr_sgd_step(_p(p), _p(g), _p(mom), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),

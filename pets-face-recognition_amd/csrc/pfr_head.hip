@@ -728,10 +728,18 @@ extern "C" int pfr_subcenter_scatter(const void* dcos, int dtype, const uint8_t*
 // One small launch (margin_prepare_kernel) turns the batch into the per-row margins / the scalar t and moves the module's EMA buffers on
 // the device; the row kernel below is margin_ce_kernel with the margin kind as a second compile-time switch.  What a step used
 // (state_used, row_margin) is a per-call copy: the backward of a step never reads the buffers a later forward may have moved.
-enum { MK_ADAFACE = 0, MK_CURRICULAR = 1 };
+// MagFace (Meng et al., CVPR 2021; not in the reference either) is the third kind: the margin is a function of the row's length like
+// AdaFace's, but the length is trained: the row kernel also writes d loss / d |x| (dnorm), which pfr_l2norm_bwd_radial adds to the
+// tangent embedding gradient.  It has an entry point of its own (pfr_margin_ce_magface): the two above keep their argument lists.
+enum { MK_ADAFACE = 0, MK_CURRICULAR = 1, MK_MAGFACE = 2 };
 struct AdaptiveParams {
   float s, m, eps, gamma;
   float cos_m, sin_m, th, mm;   // CurricularFace: ArcFace's hard margin on the target
+  // MagFace only: easy / hard fallback, the regulariser's gradient scale (lambda_g / B or lambda_g), {g, dg/d|x|} per row, the output
+  int easy = 0;
+  float reg_scale = 0.f;
+  const float* row_reg = nullptr;
+  float* dnorm = nullptr;
 };
 
 // 256 threads, fixed tree: the same bits every launch
@@ -845,6 +853,21 @@ __device__ __forceinline__ void adaptive_row(float craw, int row, const Adaptive
     phi = cosf(tc) - g_add;
     const bool flat = tp < lo || tp > hi || craw < a || craw > b;   // a clip or the clamp is active: no gradient
     dphi = flat ? 0.f : sinf(tc) / sqrtf(fmaxf(1.f - ct * ct, 0.f));  // sin(theta) >= sqrt(2 eps) > 0 inside the clamp
+  } else if constexpr (KIND == MK_MAGFACE) {
+    // the row's own margin m and d m / d |x| (pfr_magface_prepare); cosf / sinf run here, once per row
+    const float m = row_margin[2 * (size_t)row], slope = row_margin[2 * (size_t)row + 1];
+    const float cm = cosf(m), sm = sinf(m);
+    const float ct = fminf(fmaxf(craw, -1.f), 1.f);
+    const float sine = sqrtf(fmaxf(1.f - ct * ct, 0.f));
+    const float ph = ct * cm - sine * sm;
+    const float dph = cm + (sine > 0.f ? sm * ct / sine : 0.f);
+    const bool take = ap.easy ? (ct > 0.f) : (ct > -cm);          // cos(pi - m) = -cos m
+    phi = take ? ph : (ap.easy ? ct : ct - m * sm);
+    dphi = (craw < -1.f || craw > 1.f) ? 0.f : (take ? dph : 1.f);
+    // d phi / d m: -sin(theta + m) under the margin, the derivative of -m sin m on the hard fallback
+    const float dpm = take ? -(ct * sm + sine * cm) : (ap.easy ? 0.f : -(sm + m * cm));
+    a = dpm * slope;    // d phi / d |x|
+    b = 0.f;
   } else {
     const float ct = fminf(fmaxf(craw, -1.f), 1.f);
     const float sine = sqrtf(fmaxf(1.f - ct * ct, 0.f));
@@ -862,6 +885,7 @@ template <int KIND>
 __device__ __forceinline__ float adaptive_neg(float c, float a, float b) {
   if constexpr (KIND == MK_ADAFACE) return fminf(fmaxf(c, a), b);
   const float cc = fminf(fmaxf(c, -1.f), 1.f);
+  if constexpr (KIND == MK_MAGFACE) return cc;
   return cc > b ? cc * (a + cc) : cc;
 }
 // ... and its derivative
@@ -869,10 +893,13 @@ template <int KIND>
 __device__ __forceinline__ float adaptive_dneg(float c, float a, float b) {
   if constexpr (KIND == MK_ADAFACE) return (c < a || c > b) ? 0.f : 1.f;
   if (c < -1.f || c > 1.f) return 0.f;
+  if constexpr (KIND == MK_MAGFACE) return 1.f;
   return c > b ? fmaf(2.f, c, a) : 1.f;
 }
 
-// margin_ce_kernel (same passes, same row_stats / gscale conventions, same dcos dtypes) with the margin kind as a compile-time switch
+// margin_ce_kernel (same passes, same row_stats / gscale conventions, same dcos dtypes) with the margin kind as a compile-time switch.
+// MagFace: thread 0 also writes dnorm[row] = (d loss / d l_t) * s * d phi / d |x| + the regulariser's lambda_g * g'(a) with its own
+// scale (it is a mean over B whatever the criterion divides by): the target's softmax value is one more expf per row.
 template <typename TG, int CRIT, int KIND>
 __global__ __launch_bounds__(1024) void margin_ce_adaptive_kernel(const float* __restrict__ cosv, const int64_t* __restrict__ label,
                                                                  AdaptiveParams ap, const float* __restrict__ row_margin,
@@ -881,6 +908,8 @@ __global__ __launch_bounds__(1024) void margin_ce_adaptive_kernel(const float* _
                                                                  float gscale, const float* __restrict__ gscale_dev, CritParams cp) {
   static_assert(CRIT == CRIT_PLAIN || CRIT == CRIT_WCE, "the learnable alpha is not fused with the adaptive margins");
   __shared__ float sh[16];
+  float rscale = 0.f;
+  if constexpr (KIND == MK_MAGFACE) rscale = gscale_dev ? ap.reg_scale * gscale_dev[0] : ap.reg_scale;
   if (gscale_dev) gscale *= gscale_dev[0];
   if (CRIT == CRIT_WCE && cp.gscale_dev2) gscale *= cp.gscale_dev2[0];
   const int row = blockIdx.x;
@@ -915,6 +944,13 @@ __global__ __launch_bounds__(1024) void margin_ce_adaptive_kernel(const float* _
     if (threadIdx.x == 0 && loss_rows) loss_rows[row] = lossv;
     if (threadIdx.x == 0 && cp.row_stats) reinterpret_cast<f32x4*>(cp.row_stats)[row] = f32x4{lse, f, lt, 1.f};
     const float gs = gscale * f;
+    if constexpr (KIND == MK_MAGFACE) {
+      if (threadIdx.x == 0 && ap.dnorm) {
+        float r = (expf(lt - lse) - 1.f) * ap.s * gs * ma;
+        if (ap.row_reg) r = fmaf(rscale, ap.row_reg[2 * (size_t)row + 1], r);
+        ap.dnorm[row] = r;
+      }
+    }
     for (int j = threadIdx.x; j < C; j += nt) {
       const float c = cr[j];
       const float l = (j == t) ? lt : ap.s * adaptive_neg<KIND>(c, ma, mb);
@@ -962,6 +998,15 @@ __global__ __launch_bounds__(1024) void margin_ce_adaptive_kernel(const float* _
     }
     if (threadIdx.x == 0 && loss_rows) loss_rows[row] = lossv;
     if (threadIdx.x == 0 && cp.row_stats) reinterpret_cast<f32x4*>(cp.row_stats)[row] = f32x4{lse, S, lt, wt};
+    if constexpr (KIND == MK_MAGFACE) {
+      if (threadIdx.x == 0 && ap.dnorm) {
+        float d = S * expf(lt - lse) - hard;
+        if (e != 0.f) d -= soft * wt;
+        float r = d * ap.s * gscale * ma;
+        if (ap.row_reg) r = fmaf(rscale, ap.row_reg[2 * (size_t)row + 1], r);
+        ap.dnorm[row] = r;
+      }
+    }
     for (int j = threadIdx.x; j < C; j += nt) {
       const float c = cr[j];
       const float l = (j == t) ? lt : ap.s * adaptive_neg<KIND>(c, ma, mb);
@@ -1056,6 +1101,174 @@ extern "C" int pfr_margin_bwd_adaptive(const float* cosv, const int64_t* label, 
   if (kind == MK_ADAFACE) { if (dcos_dtype == PFR_BF16) MBA(bf16_t, MK_ADAFACE); else MBA(float, MK_ADAFACE); }
   else { if (dcos_dtype == PFR_BF16) MBA(bf16_t, MK_CURRICULAR); else MBA(float, MK_CURRICULAR); }
 #undef MBA
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// ---- MagFace: the per-row margins and regulariser values, the row kernel's entry, the standalone backward, the loss with the
+// regulariser, and the embedding backward with the radial term.
+// prepare: every row on its own (no sums), fp64 arithmetic on the fp32 |x| = 1 / inv_norm, rounded once
+__global__ __launch_bounds__(256) void magface_prepare_kernel(const float* __restrict__ inv_norm, int B, float l_a, float u_a, float l_m,
+                                                              float u_m, float* __restrict__ row_margin, float* __restrict__ row_reg) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B) return;
+  const float n = 1.f / inv_norm[i];
+  const bool inside = n >= l_a && n <= u_a;      // torch.clamp's autograd: the bounds themselves pass the gradient
+  const double a = fmin(fmax((double)n, (double)l_a), (double)u_a);
+  const double slope = ((double)u_m - (double)l_m) / ((double)u_a - (double)l_a);
+  const double ua2 = (double)u_a * (double)u_a;
+  reinterpret_cast<f32x2*>(row_margin)[i] = f32x2{(float)(slope * (a - (double)l_a) + (double)l_m), inside ? (float)slope : 0.f};
+  reinterpret_cast<f32x2*>(row_reg)[i] = f32x2{(float)(a / ua2 + 1.0 / a), inside ? (float)(1.0 / ua2 - 1.0 / (a * a)) : 0.f};
+}
+
+extern "C" int pfr_magface_prepare(const float* inv_norm, int B, float l_a, float u_a, float l_m, float u_m, float* row_margin,
+                                   float* row_reg, hipStream_t st) {
+  PFR_CHECK_ARG(inv_norm && row_margin && row_reg, "pfr_magface_prepare: null pointer");
+  PFR_CHECK_ARG(B > 0, "pfr_magface_prepare: bad shape B=%d", B);
+  PFR_CHECK_ARG(l_a > 0.f && u_a > l_a, "pfr_magface_prepare: need 0 < l_a < u_a, got %g, %g", (double)l_a, (double)u_a);
+  hipLaunchKernelGGL(magface_prepare_kernel, dim3((B + 255) / 256), dim3(256), 0, st, inv_norm, B, l_a, u_a, l_m, u_m, row_margin, row_reg);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+extern "C" int pfr_margin_ce_magface(const float* cosv, const int64_t* label, int B, int C, int ldc, int easy_margin, float s, float gamma,
+                                     const float* class_weight, float label_smoothing, const float* row_margin, const float* row_reg,
+                                     float reg_scale, float grad_scale, const float* grad_scale_dev, const float* grad_scale_dev2,
+                                     float* logits, float* loss_rows, float* row_stats, void* dcos, int dcos_dtype, float* dnorm,
+                                     hipStream_t st) {
+  PFR_CHECK_ARG(cosv && label && row_margin, "pfr_margin_ce_magface: null pointer (row_margin is what pfr_magface_prepare wrote)");
+  PFR_CHECK_ARG(B > 0 && C > 0 && (ldc <= 0 || ldc >= C), "pfr_margin_ce_magface: bad shape B=%d C=%d ldc=%d", B, C, ldc);
+  PFR_CHECK_ARG(label_smoothing >= 0.f && label_smoothing <= 1.f, "pfr_margin_ce_magface: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  PFR_CHECK_ARG(dcos_dtype == PFR_F32 || dcos_dtype == PFR_BF16, "pfr_margin_ce_magface: bad dcos dtype %d", dcos_dtype);
+  PFR_CHECK_ARG(row_reg || reg_scale == 0.f, "pfr_margin_ce_magface: reg_scale %g without row_reg", (double)reg_scale);
+  const bool wce = class_weight || label_smoothing != 0.f;
+  if (wce && gamma != 0.f) { pfr_set_error("pfr_margin_ce_magface: focal gamma excludes class_weight / label_smoothing"); return PFR_ERR_UNSUPPORTED; }
+  PFR_CHECK_ARG(wce || !grad_scale_dev2, "pfr_margin_ce_magface: grad_scale_dev2 belongs to the weighted mean only");
+  AdaptiveParams ap;
+  adaptive_params(ap, s, 0.f, 0.f, gamma);
+  ap.easy = easy_margin != 0;
+  ap.reg_scale = reg_scale;
+  ap.row_reg = row_reg;
+  ap.dnorm = dnorm;
+  if (ldc <= 0) ldc = C;
+  CritParams cp{nullptr, class_weight, label_smoothing, row_stats, grad_scale_dev2};
+  if (wce) launch_margin_ce_adaptive<CRIT_WCE, MK_MAGFACE>(cosv, label, B, C, ldc, ap, row_margin, nullptr, grad_scale, grad_scale_dev, logits, loss_rows, dcos, dcos_dtype, cp, st);
+  else launch_margin_ce_adaptive<CRIT_PLAIN, MK_MAGFACE>(cosv, label, B, C, ldc, ap, row_margin, nullptr, grad_scale, grad_scale_dev, logits, loss_rows, dcos, dcos_dtype, cp, st);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// margin_bwd_adaptive_kernel for MagFace, plus dnorm (thread 0)
+template <typename TG>
+__global__ __launch_bounds__(256) void margin_bwd_magface_kernel(const float* __restrict__ cosv, const int64_t* __restrict__ label,
+                                                                 AdaptiveParams ap, const float* __restrict__ row_margin,
+                                                                 const float* __restrict__ reg_scale_dev, const float* __restrict__ dlogits,
+                                                                 TG* __restrict__ dcos, int C, int ldc) {
+  const int row = blockIdx.x;
+  const float* cr = cosv + (size_t)row * ldc;
+  const int t = (int)label[row];
+  float phi, dphi, ma, mb;
+  adaptive_row<MK_MAGFACE>(cr[t], row, ap, row_margin, nullptr, phi, dphi, ma, mb);
+  if (threadIdx.x == 0 && ap.dnorm) {
+    float r = dlogits[(size_t)row * C + t] * ap.s * ma;
+    if (ap.row_reg) r = fmaf(reg_scale_dev ? ap.reg_scale * reg_scale_dev[0] : ap.reg_scale, ap.row_reg[2 * (size_t)row + 1], r);
+    ap.dnorm[row] = r;
+  }
+  for (int j = threadIdx.x; j < C; j += 256) {
+    const float d = dlogits[(size_t)row * C + j] * ap.s * ((j == t) ? dphi : adaptive_dneg<MK_MAGFACE>(cr[j], ma, mb));
+    dcos[(size_t)row * ldc + j] = from_f32<TG>(d);
+  }
+}
+extern "C" int pfr_margin_bwd_magface(const float* cosv, const int64_t* label, int B, int C, int ldc, int easy_margin, float s,
+                                      const float* row_margin, const float* row_reg, float reg_scale, const float* reg_scale_dev,
+                                      const float* dlogits, void* dcos, int dcos_dtype, float* dnorm, hipStream_t st) {
+  PFR_CHECK_ARG(cosv && label && dlogits && dcos && row_margin, "pfr_margin_bwd_magface: null pointer");
+  PFR_CHECK_ARG(B > 0 && C > 0 && (ldc <= 0 || ldc >= C), "pfr_margin_bwd_magface: bad shape B=%d C=%d ldc=%d", B, C, ldc);
+  PFR_CHECK_ARG(dcos_dtype == PFR_F32 || dcos_dtype == PFR_BF16, "pfr_margin_bwd_magface: bad dcos dtype %d", dcos_dtype);
+  PFR_CHECK_ARG(row_reg || reg_scale == 0.f, "pfr_margin_bwd_magface: reg_scale %g without row_reg", (double)reg_scale);
+  AdaptiveParams ap;
+  adaptive_params(ap, s, 0.f, 0.f, 0.f);
+  ap.easy = easy_margin != 0;
+  ap.reg_scale = reg_scale;
+  ap.row_reg = row_reg;
+  ap.dnorm = dnorm;
+  if (ldc <= 0) ldc = C;
+  if (dcos_dtype == PFR_BF16)
+    hipLaunchKernelGGL(margin_bwd_magface_kernel<bf16_t>, dim3(B), dim3(256), 0, st, cosv, label, ap, row_margin, reg_scale_dev, dlogits, (bf16_t*)dcos, C, ldc);
+  else
+    hipLaunchKernelGGL(margin_bwd_magface_kernel<float>, dim3(B), dim3(256), 0, st, cosv, label, ap, row_margin, reg_scale_dev, dlogits, (float*)dcos, C, ldc);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// loss_reduce_kernel with the regulariser: out = sum(rows) / d + lambda_g * sum_i g(a_i) / (n, or 1 for 'sum'); the same strides and
+// the same block_reduce_sum, so the criterion term has pfr_loss_reduce's bits
+__global__ void magface_loss_kernel(const float* __restrict__ x, const float* __restrict__ row_stats, const float* __restrict__ row_reg,
+                                    float* __restrict__ out, float* __restrict__ out_inv, float* __restrict__ out_reg, int n, int reduction,
+                                    float lambda_g) {
+  __shared__ float sh[4];
+  float a = 0.f, d = 0.f, g = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    if (x) a += x[i];
+    if (x && reduction == 2) d += row_stats[4 * (size_t)i + 3];
+    g += row_reg[2 * (size_t)i];
+  }
+  a = block_reduce_sum(a, sh);
+  g = block_reduce_sum(g, sh);
+  if (reduction == 2 && x) d = block_reduce_sum(d, sh);
+  else d = reduction == 0 ? (float)n : 1.f;
+  if (threadIdx.x == 0) {
+    const float reg = lambda_g * g / (reduction == 1 ? 1.f : (float)n);
+    if (out_reg) out_reg[0] = reg;
+    if (x) out[0] = a / d + reg;
+    if (x && out_inv) out_inv[0] = 1.f / d;
+  }
+}
+extern "C" int pfr_magface_loss(const float* loss_rows, const float* row_stats, const float* row_reg, int n, int reduction, float lambda_g,
+                                float* out_loss, float* out_inv_denom, float* out_reg, hipStream_t st) {
+  PFR_CHECK_ARG(row_reg && n > 0 && (loss_rows ? out_loss != nullptr : out_reg != nullptr), "pfr_magface_loss: bad args");
+  PFR_CHECK_ARG(reduction >= 0 && reduction <= 2, "pfr_magface_loss: bad reduction mode %d", reduction);
+  PFR_CHECK_ARG(reduction != 2 || !loss_rows || row_stats, "pfr_magface_loss: the weighted mean needs row_stats");
+  hipLaunchKernelGGL(magface_loss_kernel, dim3(1), dim3(256), 0, st, loss_rows, row_stats, row_reg, out_loss, out_inv_denom, out_reg, n, reduction, lambda_g);
+  PFR_CHECK_LAUNCH();
+  return PFR_OK;
+}
+
+// l2norm_bwd_kernel plus dnorm[row] * x / |x|: one wave per row, the same two passes over the row
+template <typename TI, typename TOo>
+__global__ __launch_bounds__(256) void l2norm_bwd_radial_kernel(const TI* __restrict__ x, const float* __restrict__ inv_norm,
+                                                                const float* __restrict__ dxn, const float* __restrict__ dnorm,
+                                                                TOo* __restrict__ dx, int rows, int D, int accumulate) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float inv = inv_norm[row], dn = dnorm[row];
+  const TI* xr = x + (size_t)row * D;
+  const float* gr = dxn + (size_t)row * D;
+  float dot = 0.f;
+  for (int d = lane; d < D; d += 64) dot = fmaf(to_f32(xr[d]) * inv, gr[d], dot);
+  dot = wave_sum(dot);
+  for (int d = lane; d < D; d += 64) {
+    const float xh = to_f32(xr[d]) * inv;
+    float v = fmaf(dn, xh, inv * (gr[d] - xh * dot));
+    if (accumulate) v += to_f32(dx[(size_t)row * D + d]);
+    dx[(size_t)row * D + d] = from_f32<TOo>(v);
+  }
+}
+
+extern "C" int pfr_l2norm_bwd_radial(const void* x, int in_dtype, const float* inv_norm, const float* dxn, const float* dnorm, void* dx,
+                                     int out_dtype, int rows, int D, int accumulate, hipStream_t st) {
+  if (!dnorm) return pfr_l2norm_bwd(x, in_dtype, inv_norm, dxn, dx, out_dtype, rows, D, accumulate, st);
+  PFR_CHECK_ARG(x && inv_norm && dxn && dx, "pfr_l2norm_bwd_radial: null pointer");
+  PFR_CHECK_ARG(rows > 0 && D > 0, "pfr_l2norm_bwd_radial: bad shape rows=%d D=%d", rows, D);
+  const dim3 grid((rows + 3) / 4), block(256);
+#define L2R(TI, TOo) hipLaunchKernelGGL((l2norm_bwd_radial_kernel<TI, TOo>), grid, block, 0, st, (const TI*)x, inv_norm, dxn, dnorm, (TOo*)dx, rows, D, accumulate)
+  if (in_dtype == PFR_F32 && out_dtype == PFR_F32) L2R(float, float);
+  else if (in_dtype == PFR_BF16 && out_dtype == PFR_BF16) L2R(bf16_t, bf16_t);
+  else if (in_dtype == PFR_BF16 && out_dtype == PFR_F32) L2R(bf16_t, float);
+  else if (in_dtype == PFR_F32 && out_dtype == PFR_BF16) L2R(float, bf16_t);
+  else { pfr_set_error("pfr_l2norm_bwd_radial: bad dtypes"); return PFR_ERR_UNSUPPORTED; }
+#undef L2R
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }

@@ -68,7 +68,10 @@ class Controller(nn.Module):
         return aug(x)
 
     def training_step(self, batch, batch_idx=0):
-        return self.model_loss(self._images(batch['x'], True), batch['label'])['loss']
+        out = self.model_loss(self._images(batch['x'], True), batch['label'])
+        # a MagFace head's length regulariser (part of the loss already): kept for the Trainer's loss line
+        self.last_regulariser = out.get('loss_g') if isinstance(out, dict) else None
+        return out['loss']
 
     def validation_step(self, batch, batch_idx=0, dataset_idx=0):
         return {'emb': self.model_loss(self._images(batch['x'], False)), 'label': batch['label'], 'index': batch['index']}
@@ -191,6 +194,16 @@ class Controller(nn.Module):
         out.update((f'DBSCAN noise thr={t}', st.noise) for t, st in zip(thrs, stats))
         return out
 
+    def _quality(self, emb, scores, labels, pair_generator):
+        """Opt-in (config.quality = True): the embeddings' lengths as a quality score (match.embedding_quality; a MagFace head trains
+        them): 'Quality mean norm', and 'Quality AUC', how well min(|a|, |b|) tells the high-scoring genuine pairs from the low-scoring
+        ones (match.quality_report)."""
+        if not self.config.get('quality'):
+            return {}
+        from ..match import quality_report
+        ci = pair_generator.corrected_indices
+        return quality_report(emb, scores, labels, [a for a, _ in ci], [b for _, b in ci])
+
     def test_epoch_end(self, outputs):
         all_metrics = {}
         for i in range(len(outputs)):
@@ -206,6 +219,7 @@ class Controller(nn.Module):
             metrics.update(self._retrieval(emb, classes))
             metrics.update(self._cluster(emb, classes, ps))
             metrics.update(self._dbscan(emb, classes, ps))
+            metrics.update(self._quality(emb, scores, labels, pair_generator))
             print('', *[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')
             all_metrics[name] = metrics
         self.last_metrics = all_metrics
@@ -258,6 +272,7 @@ class Controller(nn.Module):
             metrics.update(self._retrieval(emb, classes))
             metrics.update(self._cluster(emb, classes, ps))
             metrics.update(self._dbscan(emb, classes, ps))
+            metrics.update(self._quality(emb, scores, labels, pair_generator))
             all_metrics[name] = metrics
             self.last_confmat[name] = confmat
             print(*[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')

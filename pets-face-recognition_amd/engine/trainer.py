@@ -299,6 +299,7 @@ class Trainer:
         self._loop_state = {}
         lr_history = []
         history = []
+        reg_history = []     # a MagFace head's regulariser at the steps of `history`
         gn_history = []
         first_epoch = 0
         ckpt_path = ckpt_path or self.resume_from_checkpoint
@@ -349,8 +350,11 @@ class Trainer:
                 if self.global_step % self.log_every_n_steps == 0 or bi == 0:
                     lv = float(loss.detach())
                     history.append(lv)
+                    reg = getattr(controller, 'last_regulariser', None)
+                    if reg is not None:
+                        reg_history.append(float(reg.detach()))
                     if self.rank == 0:
-                        print(f'epoch {epoch} step {self.global_step} loss {lv:.5f}')
+                        print(f'epoch {epoch} step {self.global_step} loss {lv:.5f}' + (f' loss_g {reg_history[-1]:.5f}' if reg is not None else ''))
             if t_mark is not None and n_mark:
                 if device.type == 'cuda':
                     torch.cuda.synchronize(device)
@@ -374,6 +378,7 @@ class Trainer:
                 self._save_checkpoint(controller, optims, scheds, epoch, swalr)
         self.lr_history = lr_history
         self.loss_history = history
+        self.regulariser_history = reg_history
         self.grad_norm_history = gn_history
         return controller
 

@@ -1,16 +1,16 @@
 """`SoftmaxBasedMetricLearning` — backbone + cosine-margin head + criterion, with the reference's constructor
 signature, attribute names (`module`, `add_margin`, `focal_loss`) and forward contract
 (/root/reference/losses/__init__.py:8-46): `forward(img, label=None)` returns the embedding tensor when `label is
-None`, else `{'loss', 'emb', 'logits'}` (a Partial FC training forward adds `'classes'` and `'local_label'`); a list/tuple of
-images is embedded one by one and concatenated."""
+None`, else `{'loss', 'emb', 'logits'}` (a Partial FC training forward adds `'classes'` and `'local_label'`, a MagFace head
+`'loss_g'`: the length regulariser that `'loss'` already contains); a list/tuple of images is embedded one by one and concatenated."""
 import torch
 import torch.nn as nn
 
-from .large_margin import ArcMarginProduct, AddMarginProduct, AdaFaceProduct, CurricularFaceProduct, _MarginHead
+from .large_margin import ArcMarginProduct, AddMarginProduct, AdaFaceProduct, CurricularFaceProduct, MagFaceProduct, _MarginHead
 from .losses import FocalLoss, describe_criterion
 
 
-_ADAPTIVE_HEADS = {"adaface": AdaFaceProduct, "curricular": CurricularFaceProduct}
+_ADAPTIVE_HEADS = {"adaface": AdaFaceProduct, "curricular": CurricularFaceProduct, "magface": MagFaceProduct}
 
 
 class SoftmaxBasedMetricLearning(nn.Module):
@@ -25,7 +25,8 @@ class SoftmaxBasedMetricLearning(nn.Module):
             pfc = dict(sample_rate=sample_rate, sparse_grad=sparse_grad)
         # sub_centers (not in the reference): K centres per class in the head, see losses/large_margin.py; `logits` stay [B, num_class]
         # margin (not in the reference): None = arc_margin / easy_margin choose the head as ever; 'adaface' / 'curricular' build
-        # AdaFaceProduct / CurricularFaceProduct(s=s, **margin_kwargs) (their own default m unless margin_kwargs sets one)
+        # AdaFaceProduct / CurricularFaceProduct(s=s, **margin_kwargs) (their own default m unless margin_kwargs sets one); 'magface'
+        # builds MagFaceProduct(s=s, **margin_kwargs) and the returned loss includes its regulariser, also returned alone as 'loss_g'
         if margin in _ADAPTIVE_HEADS:
             self.add_margin = _ADAPTIVE_HEADS[margin](embedding_size, num_class, s=s, sub_centers=sub_centers, **pfc, **(margin_kwargs or {}))
         elif margin is not None:
@@ -36,6 +37,8 @@ class SoftmaxBasedMetricLearning(nn.Module):
             self.add_margin = AddMarginProduct(embedding_size, num_class, s=s, m=m, sub_centers=sub_centers, **pfc)
         loss_kwargs = loss_kwargs or {}
         self.focal_loss = FocalLoss(num_class=num_class, **loss_kwargs) if is_focal else nn.CrossEntropyLoss(**loss_kwargs)
+        if margin == "magface" and getattr(self.focal_loss, "reduction", "mean") not in ("mean", "sum"):
+            raise ValueError("margin='magface' adds a scalar regulariser to the loss: the criterion's reduction must be 'mean' or 'sum'")
         if self.add_margin.sample_rate < 1.0 and (getattr(self.focal_loss, "adaptive_flag", False)
                                                    or getattr(self.focal_loss, "weight", None) is not None):
             raise ValueError("sample_rate < 1 (Partial FC) is not combined with a learnable focal alpha or a class weight: both are "
@@ -62,7 +65,20 @@ class SoftmaxBasedMetricLearning(nn.Module):
             return None
         return crit
 
+    def _unfused_magface(self, tensor, label, partial):
+        """MagFace outside the fused path: the head returns (logits, lambda_g * mean g); 'sum' takes the regulariser as a sum too"""
+        logits, reg = self.add_margin.forward_with_regulariser(tensor, label, partial)
+        if getattr(self.focal_loss, "reduction", "mean") == "sum":
+            reg = reg * tensor.shape[0]
+        out = {'loss': self.focal_loss(logits, label if partial is None else partial.local_label) + reg, 'emb': tensor, 'logits': logits,
+               'loss_g': reg.detach()}
+        if partial is not None:
+            out.update(classes=partial.index, local_label=partial.local_label)
+        return out
+
     def _unfused(self, tensor, label, partial=None):
+        if isinstance(self.add_margin, MagFaceProduct):
+            return self._unfused_magface(tensor, label, partial)
         if partial is not None:     # Partial FC: logits [B, S], the criterion sees the labels' positions among the sampled classes
             logits = self.add_margin(tensor, label, partial)
             loss = self.focal_loss(logits, partial.local_label)
@@ -86,6 +102,14 @@ class SoftmaxBasedMetricLearning(nn.Module):
         from ._head_hip import MarginCEFunction, resolve_dtype
         dt = head.compute_dtype or getattr(self.module, "compute_dtype", None)
         adaptive = head.hip_adaptive()
+        if adaptive is not None and adaptive.mag is not None:
+            loss, logits, reg = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit, resolve_dtype(dt),
+                                                       self.return_logits, None, 1 if partial is not None else head.sub_centers,
+                                                       None if partial is not None else head._count(), adaptive, partial)
+            out = {'loss': loss, 'emb': tensor, 'logits': logits if self.return_logits else None, 'loss_g': reg}
+            if partial is not None:
+                out.update(classes=partial.index, local_label=partial.local_label)
+            return out
         if partial is not None:
             loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
                                                   resolve_dtype(dt), self.return_logits, None, 1, None, adaptive, partial)

@@ -41,9 +41,10 @@ def _cosine_fwd(emb, weight, T, pfc=None):
     return cos.view(B, Cp), (xn, wnT, inv_x, inv_w, wn_full)
 
 
-def _cosine_bwd(dcos, emb, weight, saved, T, pfc=None, param=None):
+def _cosine_bwd(dcos, emb, weight, saved, T, pfc=None, param=None, dnorm=None):
     """dcos [B, Cpad] (compute dtype) → (demb f32 [B,D], dweight f32 [C,D]).  `pfc`: dcos is [B, Spad] over the sampled centres and the
-    weight gradient exists for those rows only, see _partial_weight_grad"""
+    weight gradient exists for those rows only, see _partial_weight_grad.  `dnorm` (fp32 [B], MagFace): d loss / d |emb| per row, added
+    as dnorm · emb / |emb| in the pass that writes the tangent gradient"""
     xn, wnT, inv_x, inv_w, wn_full = saved
     B, D = emb.shape
     C = weight.shape[0]
@@ -60,7 +61,10 @@ def _cosine_bwd(dcos, emb, weight, saved, T, pfc=None, param=None):
         dxn = torch.empty((B, 1, 1, D), dtype=torch.float32, device=emb.device)
         ops.conv2d_fwd(dcos.view(B, 1, 1, Cp), wnT.view(D, 1, 1, Cp), out=dxn)
     dwn = ops.conv2d_wgrad(xn.view(B, 1, 1, D), dcos.view(B, 1, 1, Cp), 1, 1, 1, 0)  # [Cp,1,1,D] f32
-    demb = ops.l2norm_bwd(emb, inv_x, dxn.view(B, D), torch.float32)
+    if dnorm is None:
+        demb = ops.l2norm_bwd(emb, inv_x, dxn.view(B, D), torch.float32)
+    else:
+        demb = ops.l2norm_bwd_radial(emb, inv_x, dxn.view(B, D), dnorm, torch.float32)
     if pfc is not None:
         return demb, _partial_weight_grad(weight, inv_w, dwn.view(Cp, D), pfc, param)
     dw = ops.l2norm_bwd(weight, inv_w, dwn.view(Cp, D), torch.float32, out=torch.empty_like(weight))
@@ -114,11 +118,25 @@ def _check_partial(pfc, K, alpha, class_weight):
         raise PfrError("Partial FC: index must be an int32 and local_label an int64 CUDA tensor (_MarginHead.sample)")
 
 
-class AdaptiveMargin(namedtuple("AdaptiveMargin", "kind h momentum eps state update")):
-    """What the head functions need of an adaptive-margin head (losses/large_margin.py: AdaFaceProduct, CurricularFaceProduct): the kind
-    ('adaface' / 'curricular'), AdaFace's h and clamp eps, the EMA momentum (AdaFace's t_alpha), the module's persistent one-element
-    buffers ((batch_mean, batch_std) / (t,)) and whether this forward moves them (training mode)."""
+class AdaptiveMargin(namedtuple("AdaptiveMargin", "kind h momentum eps state update mag", defaults=(None,))):
+    """What the head functions need of an adaptive-margin head (losses/large_margin.py: AdaFaceProduct, CurricularFaceProduct,
+    MagFaceProduct): the kind ('adaface' / 'curricular' / 'magface'), AdaFace's h and clamp eps, the EMA momentum (AdaFace's t_alpha), the
+    module's persistent one-element buffers ((batch_mean, batch_std) / (t,) / ()) and whether this forward moves them (training mode);
+    `mag`: the MagFace description of kind 'magface', which has no state and uses none of h, momentum, eps."""
     __slots__ = ()
+
+
+class MagFace(namedtuple("MagFace", "l_a u_a l_m u_m lambda_g easy")):
+    """MagFaceProduct's constants: the norm and margin ranges, the regulariser's weight, easy / hard fallback of the target"""
+    __slots__ = ()
+
+
+def magface(l_a, u_a, l_m, u_m, lambda_g, easy):
+    return AdaptiveMargin("magface", 0.0, 0.0, 0.0, (), False, MagFace(float(l_a), float(u_a), float(l_m), float(u_m), float(lambda_g), bool(easy)))
+
+
+def _magface_reduction(crit):
+    return "mean" if crit.is_plain else ("sum" if crit.reduction == "sum" else "weighted_mean")
 
 
 def _prepare_adaptive(ad, m, inv_x, cos, label):
@@ -138,6 +156,8 @@ class MarginCEFunction(torch.autograd.Function):
     `adaptive` (an AdaptiveMargin, `mode` is then its kind): one more small launch after the pooling prepares the step's margins and moves
     the head's buffers, the row kernel is the adaptive instantiation; row_margin / state_used are saved per call, so this step's backward
     is independent of forwards that ran after it.  The learnable alpha is not fused with these margins (losses/__init__.py:_fusable).
+    Kind 'magface' (adaptive.mag): its own prepare / row-kernel / loss entries; the function then returns (loss, logits, regulariser), the
+    loss including the regulariser, and the backward hands the row kernel's d loss / d |emb| to the radial embedding backward.
     `pfc` (a losses.large_margin.PartialFC = (index, local_label, sparse, cache)): Partial FC, the same launches on the S sampled centres
     [B, Spad] with the gathered normalisation kernels in place of the full ones; `logits` are [B, S].  The weight's gradient is dense with
     zero unsampled rows, or with pfc.sparse None, the rows being left on `weight.row_grad` (_partial_weight_grad)."""
@@ -157,10 +177,22 @@ class MarginCEFunction(torch.autograd.Function):
         arg = None
         if K > 1:
             cos, arg = _pool_fwd(cos, C, K, T, label, count)
-        stats = inv_denom = row_margin = state_used = None
-        if adaptive is not None:
-            if alpha is not None:
-                raise PfrError("the fused head does not combine a learnable focal alpha with an adaptive margin")
+        stats = inv_denom = row_margin = state_used = reg = None
+        mag = None if adaptive is None else adaptive.mag
+        if adaptive is not None and alpha is not None:
+            raise PfrError("the fused head does not combine a learnable focal alpha with an adaptive margin")
+        if mag is not None:
+            # MagFace: the margins and g / g' per row from the inverse norms, the row kernel, then the criterion's reduction and the
+            # regulariser lambda_g · mean g(a) in one launch; row_reg rides in state_used's slot of the saved tensors
+            row_margin, state_used = ops.magface_prepare(saved[2], mag.l_a, mag.u_a, mag.l_m, mag.u_m)
+            logits, loss_rows, stats, _, _ = ops.margin_ce_magface(cos, label, C, mag.easy, s, row_margin, state_used, gamma=crit.gamma,
+                                                                   class_weight=crit.weight, label_smoothing=crit.smoothing,
+                                                                   want_logits=want_logits, want_stats=not crit.is_plain)
+            red = _magface_reduction(crit)
+            loss, inv_denom, reg = ops.magface_loss(loss_rows, stats, state_used, red, mag.lambda_g)
+            if red != "weighted_mean":
+                inv_denom = None
+        elif adaptive is not None:
             row_margin, state_used = _prepare_adaptive(adaptive, m, saved[2], cos, label)
             logits, loss_rows, stats, _ = ops.margin_ce_adaptive(cos, label, C, mode, s, m, adaptive.eps, row_margin, state_used,
                                                                  gamma=crit.gamma, class_weight=crit.weight, label_smoothing=crit.smoothing,
@@ -185,20 +217,32 @@ class MarginCEFunction(torch.autograd.Function):
             else:   # F.cross_entropy's 'mean' divides by the sum of the targets' weights (= B without weights)
                 loss, inv_denom = ops.loss_reduce(loss_rows, stats, "weighted_mean")
         ctx.save_for_backward(emb, w, label, cos, alpha, crit.weight, stats, inv_denom, arg, row_margin, state_used, *saved)
-        ctx.cfg = (mode, s, m, crit, T, C, K, None if adaptive is None else adaptive.eps)
+        ctx.cfg = (mode, s, m, crit, T, C, K, None if adaptive is None or mag is not None else adaptive.eps)
+        ctx.mag = mag
         if logits is None:
             logits = torch.empty(0, device=emb.device)
         ctx.mark_non_differentiable(logits)
+        if mag is not None:     # the regulariser's value (already part of `loss`), for logging
+            ctx.mark_non_differentiable(reg)
+            return loss, logits, reg
         return loss, logits
 
     @staticmethod
-    def backward(ctx, dloss, _dlogits):
+    def backward(ctx, dloss, _dlogits, _dreg=None):
         emb, w, label, cos, alpha, cweight, stats, inv_denom, arg, row_margin, state_used, *saved = ctx.saved_tensors
         mode, s, m, crit, T, C, K, ad_eps = ctx.cfg
         B = emb.shape[0]
         dloss = dloss.contiguous().float()
-        dalpha = None
-        if ad_eps is not None:
+        dalpha = dnorm = None
+        if ctx.mag is not None:
+            mag = ctx.mag
+            red = _magface_reduction(crit)
+            _, _, _, dcos, dnorm = ops.margin_ce_magface(cos, label, C, mag.easy, s, row_margin, state_used,
+                                                         reg_scale=mag.lambda_g * (1.0 if red == "sum" else 1.0 / B), gamma=crit.gamma,
+                                                         class_weight=cweight, label_smoothing=crit.smoothing,
+                                                         grad_scale=1.0 / B if crit.is_plain else 1.0, grad_scale_dev=dloss,
+                                                         grad_scale_dev2=inv_denom, want_logits=False, want_stats=False, dcos_dtype=T)
+        elif ad_eps is not None:
             _, _, _, dcos = ops.margin_ce_adaptive(cos, label, C, mode, s, m, ad_eps, row_margin, state_used, gamma=crit.gamma,
                                                    class_weight=cweight, label_smoothing=crit.smoothing,
                                                    grad_scale=1.0 / B if crit.is_plain else 1.0, grad_scale_dev=dloss,
@@ -216,7 +260,7 @@ class MarginCEFunction(torch.autograd.Function):
                 dalpha = ops.alpha_grad(cos, label, alpha, stats, C, s, grad_scale=gs, grad_scale_dev=dloss)
         if K > 1:
             dcos = ops.subcenter_scatter(dcos, arg, K, ld_sub=_cpad(C * K, T))
-        demb, dw = _cosine_bwd(dcos, emb, w, saved, T, ctx.pfc, ctx.param)
+        demb, dw = _cosine_bwd(dcos, emb, w, saved, T, ctx.pfc, ctx.param, dnorm)
         return demb, dw, None, None, None, None, None, None, None, dalpha, None, None, None, None
 
 
@@ -237,25 +281,37 @@ class MarginFunction(torch.autograd.Function):
         arg = None
         if K > 1:
             cos, arg = _pool_fwd(cos, C, K, T, label, count)
-        row_margin = state_used = None
-        if adaptive is not None:
+        row_margin = state_used = reg = None
+        mag = None if adaptive is None else adaptive.mag
+        if mag is not None:
+            # MagFace returns (logits, regulariser): lambda_g · mean g(a), a differentiable output whose gradient joins dnorm
+            row_margin, state_used = ops.magface_prepare(saved[2], mag.l_a, mag.u_a, mag.l_m, mag.u_m)
+            logits, _, _, _, _ = ops.margin_ce_magface(cos, label, C, mag.easy, s, row_margin, state_used, want_logits=True, want_stats=False)
+            _, _, reg = ops.magface_loss(None, None, state_used, "mean", mag.lambda_g)
+        elif adaptive is not None:
             row_margin, state_used = _prepare_adaptive(adaptive, m, saved[2], cos, label)
             logits, _, _, _ = ops.margin_ce_adaptive(cos, label, C, mode, s, m, adaptive.eps, row_margin, state_used, want_logits=True,
                                                      want_stats=False)
         else:
             logits, _, _ = ops.margin_ce(cos, label, C, mode, s, m, want_logits=True)
         ctx.save_for_backward(emb, w, label, cos, arg, row_margin, state_used, *saved)
-        ctx.cfg = (mode, s, m, T, C, K, None if adaptive is None else adaptive.eps)
-        return logits
+        ctx.cfg = (mode, s, m, T, C, K, None if adaptive is None or mag is not None else adaptive.eps)
+        ctx.mag = mag
+        return logits if mag is None else (logits, reg)
 
     @staticmethod
-    def backward(ctx, dlogits):
+    def backward(ctx, dlogits, dreg=None):
         from .._hip import lib, dtype_id
         emb, w, label, cos, arg, row_margin, state_used, *saved = ctx.saved_tensors
         mode, s, m, T, C, K, ad_eps = ctx.cfg
         B, Cp = cos.shape
         dlogits = dlogits.contiguous().float()
-        if ad_eps is not None:
+        dnorm = None
+        if ctx.mag is not None:
+            dreg = None if dreg is None else dreg.contiguous().float()
+            dcos, dnorm = ops.margin_bwd_magface(cos, label, C, ctx.mag.easy, s, row_margin, state_used, ctx.mag.lambda_g / emb.shape[0],
+                                                 dreg, dlogits, T)
+        elif ad_eps is not None:
             dcos = ops.margin_bwd_adaptive(cos, label, C, mode, s, m, ad_eps, row_margin, state_used, dlogits, T)
         else:
             dcos = torch.zeros((B, Cp), dtype=T, device=emb.device)
@@ -263,7 +319,7 @@ class MarginFunction(torch.autograd.Function):
                                dlogits.data_ptr(), dcos.data_ptr(), dtype_id(T), torch.cuda.current_stream().cuda_stream)
         if K > 1:
             dcos = ops.subcenter_scatter(dcos, arg, K, ld_sub=_cpad(C * K, T))
-        demb, dw = _cosine_bwd(dcos, emb, w, saved, T, ctx.pfc, ctx.param)
+        demb, dw = _cosine_bwd(dcos, emb, w, saved, T, ctx.pfc, ctx.param, dnorm)
         return demb, dw, None, None, None, None, None, None, None, None, None
 
 

@@ -10,7 +10,8 @@ sub-cosines.  K = 1 (the default) is the reference's head, bit for bit.
 
 Beyond the reference as well: `AdaFaceProduct` (Kim et al., CVPR 2022: the margin follows the sample's feature norm) and
 `CurricularFaceProduct` (Huang et al., CVPR 2020: hard negatives are re-weighted by a factor that grows with training), both with
-persistent one-element statistics buffers.
+persistent one-element statistics buffers; and `MagFaceProduct` (Meng et al., CVPR 2021), whose margin follows the embedding's length
+and whose loss carries a regulariser on it: the one head whose gradient has a radial part (its docstring is the definition).
 
 Beyond the reference too: `sample_rate < 1` (Partial FC, An et al., CVPR 2022): a training-mode forward scores the batch's own classes plus
 random negatives, `int(sample_rate * out_features)` centres in all (`_MarginHead.sample`); `sparse_grad=True` leaves the gradient of those
@@ -293,6 +294,69 @@ class AdaFaceProduct(_AdaptiveMarginHead):
         phi = torch.cos((theta + g_ang).clip(eps, math.pi - eps)) - g_add
         hot = F.one_hot(label, c.shape[1]).bool()
         return self.s * torch.where(hot, phi[:, None], c)
+
+
+class MagFaceProduct(_AdaptiveMarginHead):
+    """MagFace (Meng et al., CVPR 2021; the arithmetic of the published models/magface.py): the angular margin grows with the length of the
+    raw embedding, and a regulariser on that length is part of the loss, so that |x| is trained into a per-sample quality score.
+    Per row i, with the class cosines c_ij (after sub-centre pooling, clamped to [-1, 1]) and the label t_i:
+        a_i = clamp(|x_i|, l_a, u_a)
+        m_i = (u_m - l_m) / (u_a - l_a) * (a_i - l_a) + l_m
+        phi_i = c * cos m_i - sqrt(1 - c^2) * sin m_i = cos(theta + m_i),  c = c_{i t_i}
+        target_i = phi_i where c > 0, else c                                  (easy_margin=True, the default)
+                 = phi_i where c > cos(pi - m_i), else c - m_i * sin m_i      (easy_margin=False)
+        logits_ij = s * target_i for j = t_i, s * c_ij elsewhere
+        loss = criterion(logits, t) + lambda_g * mean_i g(a_i),  g(a) = a / u_a^2 + 1 / a      (lambda_g * sum_i g(a_i) with reduction='sum')
+    Focal gamma, class weights and label smoothing act on the criterion term only.
+    Unlike every other head here the gradient runs THROUGH the length: d loss / d a_i = (d loss / d logits_{i t_i}) * s * d target_i /
+    d m_i * (u_m - l_m) / (u_a - l_a) + lambda_g * g'(a_i) / B, g'(a) = 1 / u_a^2 - 1 / a^2, with d target / d m = -sin(theta + m) under
+    the margin, 0 on the easy fallback and -(sin m + m cos m) on the hard one; it is exactly 0 where |x_i| lies outside [l_a, u_a]
+    (the clamp is active; |x_i| equal to a bound counts as inside).  The embedding gradient is the tangent term of the other heads plus
+    (d loss / d a_i) * x_i / |x_i|; the class weights get no new term.  No buffers, no state: the state dict is an ArcFace head's.
+    `forward` returns the logits; `forward_with_regulariser` returns (logits, lambda_g * mean_i g(a_i)).  CUDA inputs run on
+    pfr_magface_prepare / pfr_margin_ce_magface / pfr_l2norm_bwd_radial; the CPU path below is this definition in torch ops."""
+    _mode = "magface"
+
+    def __init__(self, in_features, out_features, s=64.0, l_a=10.0, u_a=110.0, l_m=0.45, u_m=0.8, lambda_g=35.0, easy_margin=True,
+                 sub_centers=1, sample_rate=1.0, sparse_grad=False, **_):
+        if not 0.0 < l_a < u_a:
+            raise ValueError(f"MagFace: need 0 < l_a < u_a, got l_a={l_a}, u_a={u_a}")
+        super().__init__(in_features, out_features, s, float(l_m), sub_centers, sample_rate, sparse_grad)   # .m: the base margin l_m
+        self.l_a, self.u_a, self.l_m, self.u_m = float(l_a), float(u_a), float(l_m), float(u_m)
+        self.lambda_g, self.easy_margin = float(lambda_g), bool(easy_margin)
+
+    def hip_adaptive(self):
+        from ._head_hip import magface
+        return magface(self.l_a, self.u_a, self.l_m, self.u_m, self.lambda_g, self.easy_margin)
+
+    def forward(self, input, label, partial=None):
+        return self.forward_with_regulariser(input, label, partial)[0]
+
+    def forward_with_regulariser(self, input, label, partial=None):
+        if partial is None:
+            partial = self._partial(label)
+        if input.is_cuda:
+            from ._head_hip import MarginFunction, resolve_dtype
+            if partial is not None:
+                return MarginFunction.apply(input, self.weight, label, self.hip_mode(), self.s, self.m, resolve_dtype(self.compute_dtype),
+                                            1, None, self.hip_adaptive(), partial)
+            return MarginFunction.apply(input, self.weight, label, self.hip_mode(), self.s, self.m, resolve_dtype(self.compute_dtype),
+                                        self.sub_centers, self._count(), self.hip_adaptive())
+        if partial is not None:
+            label = partial.local_label
+        label = label.view(-1).long()
+        c = self._cpu_cosine(input, label, partial).clamp(-1.0, 1.0)
+        a = input.norm(dim=1).clamp(self.l_a, self.u_a).to(c.dtype)
+        m = (self.u_m - self.l_m) / (self.u_a - self.l_a) * (a - self.l_a) + self.l_m
+        ct = c.gather(1, label[:, None]).squeeze(1)
+        phi = ct * torch.cos(m) - torch.sqrt((1.0 - ct * ct).clamp_min(0.0)) * torch.sin(m)
+        if self.easy_margin:
+            target = torch.where(ct > 0, phi, ct)
+        else:
+            target = torch.where(ct > torch.cos(math.pi - m), phi, ct - m * torch.sin(m))
+        hot = F.one_hot(label, c.shape[1]).bool()
+        reg = self.lambda_g * (a / self.u_a ** 2 + 1.0 / a).mean()
+        return self.s * torch.where(hot, target[:, None], c), reg
 
 
 class CurricularFaceProduct(_AdaptiveMarginHead):

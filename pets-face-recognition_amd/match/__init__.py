@@ -384,6 +384,42 @@ def pair_similarity(emb, idx_a, idx_b, eps=1e-8):
     return out
 
 
+def embedding_quality(emb):
+    """fp32 [N]: the length |emb_i| of every raw embedding, the per-photo quality score of a MagFace-trained extractor (losses/
+    large_margin.py MagFaceProduct).  CUDA rows: the reciprocal of the inverse norms the match's row normalisation writes
+    (pfr_l2norm_fwd's inv_norm, so the score is the |x| the training head saw); CPU rows: torch's norm."""
+    if emb.dim() != 2:
+        raise ValueError(f"embedding_quality: expected [N, D] embeddings, got {tuple(emb.shape)}")
+    e = emb.float().contiguous()
+    if not e.is_cuda or e.shape[0] == 0:
+        return e.norm(dim=1)
+    return ops.l2norm_fwd(e, torch.bfloat16)[2].reciprocal()
+
+
+def quality_report(emb, scores, pair_labels, idx_a, idx_b):
+    """{'Quality mean norm', 'Quality AUC'} of validation embeddings and their scored pairs.  'Quality AUC': over the GENUINE pairs
+    (pair_labels == 1), the ROC AUC of "the pair's score is above the genuine pairs' median" against the pair's quality min(|a|, |b|),
+    i.e. the probability that a high-scoring genuine pair has the higher smaller-norm than a low-scoring one (0.5: the length says
+    nothing about which genuine pairs match well; NaN with fewer than two genuine pairs or constant scores).  Host arithmetic."""
+    q = embedding_quality(emb).double().cpu()
+    out = {'Quality mean norm': float(q.mean()) if q.numel() else float('nan'), 'Quality AUC': float('nan')}
+    lab = torch.as_tensor(pair_labels).cpu().reshape(-1) == 1
+    ia = torch.as_tensor(idx_a, dtype=torch.int64)[lab]
+    ib = torch.as_tensor(idx_b, dtype=torch.int64)[lab]
+    s = torch.as_tensor(scores).detach().double().cpu().reshape(-1)[lab]
+    if s.numel() < 2:
+        return out
+    pq = torch.minimum(q[ia], q[ib])
+    high = s > s.median()
+    n1, n0 = int(high.sum()), int((~high).sum())
+    if n1 == 0 or n0 == 0:
+        return out
+    # Mann-Whitney U of the qualities, ties counted half
+    d = pq[high][:, None] - pq[~high][None, :]
+    out['Quality AUC'] = float(((d > 0).double().sum() + 0.5 * (d == 0).double().sum()) / (n1 * n0))
+    return out
+
+
 def card_centroids(emb, seg, compute_dtype=torch.float32):
     """Mean of the L2-normalised photo embeddings per card.  emb [P, D]; seg: int64 [ncards+1] row offsets."""
     seg = torch.as_tensor(seg, dtype=torch.int64, device=emb.device).contiguous()

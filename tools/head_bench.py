@@ -7,6 +7,9 @@ bf16 and fp32 compute, two variants per criterion interleaved round by round so 
 The adaptive margins (AdaFace, CurricularFace; default criterion) are two more rows; their second variant is
   torch     the head as a chain of torch ops on the same device (the modules' own CPU formulation, losses/large_margin.py, run on the
             device tensors, then FocalLoss's torch arithmetic): there is no unfused margin kernel of that kind to fall back to.
+The 'magface' row (MagFace: the one head with a gradient through the embedding's length) has three interleaved variants: fused, torch
+(MagFaceProduct's CPU definition run on the device, regulariser included) and adaface (the fused AdaFace head of the same shape in the
+same rounds, the closest fused relative: one prepare launch, the same row kernel, no radial term).
 Prints one JSON line per (criterion, dtype): median / min ms of forward + backward per variant and the peak of
 torch.cuda.max_memory_allocated over one forward + backward above what was allocated before it.
   python tools/head_bench.py [--rounds 8] [--steps 20] [--warmup 10] [--only default] [--variants fused]"""
@@ -32,8 +35,23 @@ CRITERIA = {
     "smooth0.1": (False, dict(label_smoothing=0.1)),
     "adaface": (True, dict()),
     "curricular": (True, dict()),
+    "magface": (True, dict()),
 }
-ADAPTIVE = ("adaface", "curricular")
+ADAPTIVE = ("adaface", "curricular", "magface")
+
+
+def _magface_torch(head, emb, label):
+    """MagFaceProduct.forward_with_regulariser's CPU branch (the definition in torch ops) on device tensors -> (logits, regulariser)"""
+    import math
+    F = nn.functional
+    c = (F.normalize(emb) @ F.normalize(head.weight).t()).clamp(-1.0, 1.0)
+    a = emb.norm(dim=1).clamp(head.l_a, head.u_a)
+    m = (head.u_m - head.l_m) / (head.u_a - head.l_a) * (a - head.l_a) + head.l_m
+    ct = c.gather(1, label[:, None]).squeeze(1)
+    phi = ct * torch.cos(m) - torch.sqrt((1.0 - ct * ct).clamp_min(0.0)) * torch.sin(m)
+    target = torch.where(ct > 0, phi, ct) if head.easy_margin else torch.where(ct > torch.cos(math.pi - m), phi, ct - m * torch.sin(m))
+    hot = F.one_hot(label, c.shape[1]).bool()
+    return head.s * torch.where(hot, target[:, None], c), head.lambda_g * (a / head.u_a ** 2 + 1.0 / a).mean()
 
 
 def main():
@@ -58,6 +76,8 @@ def main():
             continue
         margin = name if name in ADAPTIVE else None
         variants = [("torch" if margin and v == "fallback" else v) for v in args.variants.split(",")]
+        if name == "magface" and "fused" in variants:
+            variants.append("adaface")
         kw = dict(kw)
         if kw.get("weight"):
             kw["weight"] = 0.25 + 2.0 * torch.rand(C, generator=g)
@@ -65,17 +85,27 @@ def main():
             wrap = SoftmaxBasedMetricLearning(nn.Identity(), C, D, is_focal=is_focal, loss_kwargs=kw, arc_margin=True, margin=margin).to(dev)
             wrap.add_margin.compute_dtype = dt
             params = [emb] + list(wrap.parameters())
+            if "adaface" in variants:
+                ada = SoftmaxBasedMetricLearning(nn.Identity(), C, D, is_focal=is_focal, loss_kwargs=kw, margin="adaface").to(dev)
+                ada.add_margin.compute_dtype = dt
+                params += list(ada.parameters())
 
             def step(variant):
                 for p in params:
                     p.grad = None
                 if variant == "fused":
                     loss = wrap(emb, label)["loss"]
+                elif variant == "adaface":
+                    loss = ada(emb, label)["loss"]
                 elif variant == "torch":
                     head = wrap.add_margin
-                    logits = head._adaptive_logits(emb, head._cpu_cosine(emb, label), label)
+                    reg = 0.0
+                    if name == "magface":
+                        logits, reg = _magface_torch(head, emb, label)
+                    else:
+                        logits = head._adaptive_logits(emb, head._cpu_cosine(emb, label), label)
                     ce = nn.functional.cross_entropy(logits, label, reduction="none")
-                    loss = ((1 - torch.exp(-ce)) ** wrap.focal_loss.gamma * ce).mean()
+                    loss = ((1 - torch.exp(-ce)) ** wrap.focal_loss.gamma * ce).mean() + reg
                 else:
                     logits = wrap.add_margin(emb, label)
                     if is_focal and kw.get("alpha"):
