@@ -41,6 +41,10 @@ def main(argv=None):
                     help="also report 'DBSCAN F / precision / recall / BCubed F / clusters / noise thr=…': DBSCAN identity clustering "
                          "(match.dbscan) with MIN_SAMPLES items (the item itself included) per core neighbourhood at these similarity "
                          "thresholds; 'opt' stands for the run's optimal threshold, e.g. 4 0.8 opt")
+    ap.add_argument('--open-set', type=float, nargs='+', default=None, metavar='F',
+                    help="also report 'OpenSet rank1', 'OpenSet DIR@FPIR=F', 'OpenSet TH@FPIR=F' and 'OpenSet suspects': open-set "
+                         "identification (match.class_extremes: every item searched against all the others) at these false-positive "
+                         "identification rates, e.g. 0.1 0.01")
     ap.add_argument('--quality', action='store_true',
                     help="also report 'Quality mean norm' (mean length of the embeddings, match.embedding_quality) and 'Quality AUC' (how "
                          "well the smaller length of a genuine pair tells the high-scoring pairs from the low-scoring ones)")
@@ -58,6 +62,8 @@ def main(argv=None):
         if len(args.dbscan) < 2:
             ap.error('--dbscan needs MIN_SAMPLES and at least one threshold')
         config['dbscan'] = dict(thresholds=[t if t == 'opt' else float(t) for t in args.dbscan[1:]], min_samples=int(args.dbscan[0]))
+    if args.open_set is not None:
+        config['open_set'] = dict(fpir=list(args.open_set))
     if args.all_pairs_far is not None:
         config['all_pairs_far'] = list(args.all_pairs_far)
     controller = Controller(config)

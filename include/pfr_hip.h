@@ -730,6 +730,57 @@ int pfr_dbscan_link(const void* a, const float* a_scale, int Na, int a_off, cons
 int pfr_dbscan_labels(const int* parent, const int* deg, const unsigned long long* best, int min_neighbors, int n_nodes, int* labels,
                       pfr_stream_t stream);
 
+/* ---- open-set identification from the match GEMM (csrc/pfr_extremes.hip): per node the BEST MATE (highest same-class score), the BEST
+ * IMPOSTOR (highest other-class score) and the WEAKEST MATE (lowest same-class score), each with its partner's index.  These are the
+ * two numbers per probe that FNIR@FPIR / DIR@FAR needs, and what label cleaning and hard-pair mining read.  Nothing N x N is written.
+ *   Operands, scores, schedule.  EXACTLY those of pfr_pairs_above / pfr_neighbor_count: rc_tile_gemm / rc_score of csrc/pfr_pairtile.h, so
+ *     a score has the bits of pfr_pair_scores_gather; dtypes fp32, bf16 and int8 with row scales, the same D rules; persistent workgroups
+ *     walk 128 x 128 tiles in 16 x 16 super-tiles, upper triangle only in symmetric mode.  b == NULL: symmetric mode, every unordered
+ *     pair i < j of a is visited once and the diagonal never — an item is never its own mate (cls_b, b_scale, Nb, b_off and both_sides are
+ *     ignored).  Otherwise every pair of the two sets is visited.
+ *   Node ids.  u = a_off + i, v = b_off + j (symmetric: v = a_off + j).
+ *   Classes.  cls_a int32 [Na], cls_b int32 [Nb]: the class of each row.  The pair (i, j) is a MATE pair iff cls_a[i] == cls_b[j] and
+ *     cls_a[i] >= 0; every other pair is an IMPOSTOR pair.  A NEGATIVE class means "unlabelled / distractor": such a row has no mates and
+ *     is an impostor to everyone, other distractors (of the same negative value too) included.
+ *   Updates.  A pair whose score is NaN updates nothing (the gate is s == s).  Every other visited pair updates node u with partner v; in
+ *     symmetric mode, or when both_sides != 0, it also updates node v with partner u.  With both_sides != 0 the caller passes DISJOINT
+ *     blocks of one node set (as for pfr_dbscan_link: a set too large for one launch, block by block).  both_sides == 0 is the
+ *     probe-against-gallery form: only the a side has outputs, v is merely the stored partner index.
+ *   Keys.  best_pos, best_neg, worst_pos: u64 [n_nodes], ZEROED BY THE CALLER; calls accumulate, so block launches combine.  Every update
+ *     is an agent-scope relaxed atomic maximum with the key
+ *         best_pos[x], best_neg[x]:  ( ord(s) << 32) | (0xffffffff - partner)     — the maximum is the HIGHEST score, then the SMALLEST partner
+ *         worst_pos[x]:              (~ord(s) << 32) | (0xffffffff - partner)     — the maximum is the LOWEST score, then the SMALLEST partner
+ *     ord(s) = bits(s + 0.0f) with all bits flipped when negative, the sign bit flipped otherwise (the order-preserving uint32 of the
+ *     DBSCAN border key: -0.0 is canonicalised to +0.0, csrc/pfr_scorekey.h); ~ is the 32-bit complement.  A mate pair updates best_pos
+ *     and worst_pos, an impostor pair best_neg.  Key 0 means "no such pair": every real key is > 0 because partner < 2^31.  worst_pos
+ *     may be NULL: it is then not computed; best_pos and best_neg are required.  The result depends on neither scheduling, chunking nor
+ *     the number of calls: two runs give the same bits.
+ *   Cost.  The atomics are reduced first.  A FILTER: per tile every row and column reads its node's current best_neg key once (agent-scope
+ *     relaxed load; stale is safe, keys only grow) and an impostor score below it is dropped; one wave vote ends a wave in which nothing
+ *     is left.  A WAVE REDUCTION of what is left: at most one atomic maximum per touched row or column, per kind, per wave and tile.
+ *     Mate pairs are not filtered: the cost grows with the share of mate pairs (a set of few huge classes is correct and slow).
+ * pfr_extremes_decode: one thread per key, keys u64 [n] -> score fp32 [n], index int32 [n].  kind 0: a max-key (best_pos, best_neg);
+ *   kind 1: a min-key (worst_pos: the ~ is undone).  A non-zero key gives score = the float whose ord is stored, index = the partner;
+ *   key 0 gives index = -1 and score = -inf (kind 0) or +inf (kind 1).  A key that decodes to an index >= 2^31 is treated as key 0 and is
+ *   never used as an index.
+ * Errors (PFR_ERR_ARG, nothing launched or written): those of pfr_neighbor_count — null or host pointers among the required arguments, a
+ *   bad dtype or D, int8 rows without their scales, negative sizes or offsets, a_off + Na > n_nodes, b_off + Nb > n_nodes when the b side
+ *   is written (symmetric mode, both_sides != 0), offsets that pass 2^31 - 1 together with Na / Nb — plus a null cls_a, a null cls_b in
+ *   two-set mode, and for the decoding n < 0 and a kind outside {0, 1}.  Na == 0, Nb == 0, a symmetric Na == 1 and n == 0 do nothing
+ *   and return 0.
+ * Metrics on top (host arithmetic, engine.metrics.OpenSetStats of the Python package; every probe searched against all the others,
+ *   leave-one-out).  Rank order is (score descending, index ascending).  MATED probes M = {x : best_pos index >= 0}; x is a HIT iff its
+ *   best mate ranks before its best impostor, or it has no impostor.  rank1 = hits / |M|.  NON-MATED searches: every probe with an
+ *   impostor, searched against the gallery without its own class — its top score is its best_neg score; n = their number;
+ *   FPIR(t) = #{best_neg score >= t} / n;  t(f) = the smallest fp32 t with #{best_neg score >= t} <= floor(f n), i.e. nextafter above the
+ *   (floor(f n) + 1)-th largest impostor score, -inf when floor(f n) >= n;  DIR@FPIR=f = #{x in M : hit and best_pos score >= t(f)} / |M|,
+ *   FNIR = 1 - DIR.
+ * NOT COVERED.  More than one extreme per row (the top-K match lists, match.cosine_topk, keep K of them); a per-class second-best. */
+int pfr_class_extremes(const void* a, const float* a_scale, int Na, int a_off, const void* b, const float* b_scale, int Nb, int b_off,
+                       int dtype, int D, const int* cls_a, const int* cls_b, int both_sides, unsigned long long* best_pos,
+                       unsigned long long* best_neg, unsigned long long* worst_pos, int n_nodes, pfr_stream_t stream);
+int pfr_extremes_decode(const unsigned long long* keys, int n, int kind, float* score, int* index, pfr_stream_t stream);
+
 /* ---- k-reciprocal re-ranking of match lists (Zhong et al., "Re-ranking Person Re-identification with k-reciprocal Encoding", CVPR 2017)
  * on SPARSE rows: nothing N x N is built.  The set is N items with unit-norm fp32 rows emb32 [N][D].
  * Inputs

@@ -18,6 +18,7 @@
 // launch wrote it).  The border key is (order-preserving uint32 of the score, 0xffffffff - core index): its maximum is "highest score,
 // then smallest index" whatever the order of arrival.
 #include "pfr_pairtile.h"
+#include "pfr_scorekey.h"     // db_score_key: the order-preserving uint32 of a score (shared with pfr_extremes.hip)
 #include "pfr_unionfind.h"
 
 #define DB_LDS (2 * RC_T * RC_ROWB + 2 * RC_T * 4)   // 33 792 bytes: under the default limit
@@ -40,12 +41,6 @@ struct DbscanParams {
   int ntm, ntn, nsn;
   long long nsuper;
 };
-
-// score -> uint32 with the order of the floats (-0 canonicalised to +0 first; a NaN never gets here: it does not qualify)
-__device__ __forceinline__ unsigned int db_score_key(float s) {
-  const unsigned int u = __float_as_uint(s + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u ^ 0x80000000u);
-}
 
 template <typename T, bool LINK>
 __global__ __launch_bounds__(256, 2) void dbscan_pass_kernel(const DbscanParams p) {   // (2 workgroups per CU: at most 256 registers)

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import metrics as M
-from ..match import recall_at_k, pair_similarity, pair_histogram, positive_ranks, cluster, dbscan
+from ..match import recall_at_k, pair_similarity, pair_histogram, positive_ranks, cluster, dbscan, class_extremes, label_suspects
 
 
 class Controller(nn.Module):
@@ -194,6 +194,26 @@ class Controller(nn.Module):
         out.update((f'DBSCAN noise thr={t}', st.noise) for t, st in zip(thrs, stats))
         return out
 
+    def _open_set(self, emb, classes):
+        """Opt-in (config.open_set = dict(fpir=[0.1, 0.01])): open-set identification of the set, every item searched against all the
+        others (match.class_extremes: the match GEMM with a best-mate / best-impostor epilogue on the device; engine.metrics
+        .OpenSetStats): 'OpenSet rank1', per false-positive identification rate f 'OpenSet DIR@FPIR={f}' (mated probes that come back at
+        rank 1 at or above the threshold that alarms for at most f of the searches without a mate; FNIR = 1 - DIR) and 'OpenSet
+        TH@FPIR={f}' (a similarity (cos + 1) / 2 like every TH@…), and 'OpenSet suspects', the number of items whose best impostor
+        ranks before their best mate (match.label_suspects)."""
+        cfg = self.config.get('open_set')
+        if cfg is None:
+            return {}
+        fpirs = list(dict(cfg).get('fpir', (0.1, 0.01)))
+        dt = torch.float32 if not emb.is_cuda else getattr(self.config, 'match_dtype', torch.bfloat16)
+        ex = class_extremes(emb, classes, compute_dtype=dt, weakest=False)
+        st = M.OpenSetStats(ex.pos_score, ex.pos_index, ex.neg_score, ex.neg_index)
+        out = {'OpenSet rank1': st.rank1()}
+        out.update((f'OpenSet DIR@FPIR={f}', st.dir_at_fpir(f)) for f in fpirs)
+        out.update((f'OpenSet TH@FPIR={f}', (st.threshold_at_fpir(f) + 1.0) / 2.0) for f in fpirs)
+        out['OpenSet suspects'] = int(label_suspects(ex).numel())
+        return out
+
     def _quality(self, emb, scores, labels, pair_generator):
         """Opt-in (config.quality = True): the embeddings' lengths as a quality score (match.embedding_quality; a MagFace head trains
         them): 'Quality mean norm', and 'Quality AUC', how well min(|a|, |b|) tells the high-scoring genuine pairs from the low-scoring
@@ -219,6 +239,7 @@ class Controller(nn.Module):
             metrics.update(self._retrieval(emb, classes))
             metrics.update(self._cluster(emb, classes, ps))
             metrics.update(self._dbscan(emb, classes, ps))
+            metrics.update(self._open_set(emb, classes))
             metrics.update(self._quality(emb, scores, labels, pair_generator))
             print('', *[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')
             all_metrics[name] = metrics
@@ -272,6 +293,7 @@ class Controller(nn.Module):
             metrics.update(self._retrieval(emb, classes))
             metrics.update(self._cluster(emb, classes, ps))
             metrics.update(self._dbscan(emb, classes, ps))
+            metrics.update(self._open_set(emb, classes))
             metrics.update(self._quality(emb, scores, labels, pair_generator))
             all_metrics[name] = metrics
             self.last_confmat[name] = confmat

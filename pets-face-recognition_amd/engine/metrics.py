@@ -302,6 +302,62 @@ class ClusterStats:
         return out
 
 
+class OpenSetStats:
+    """Open-set identification (NIST 1:N: FNIR@FPIR; also DIR@FAR) from the per-probe extremes of match.class_extremes: `pos_score`,
+    `pos_index` the best mate (index -1: the probe has no mate), `neg_score`, `neg_index` the best impostor (index -1: none).  Every probe
+    is searched against all the others, leave-one-out.  The rank order is (score descending, index ascending).
+      MATED probes M = {x : pos_index[x] >= 0}; x is a HIT iff its best mate ranks before its best impostor, or it has no impostor.
+      NON-MATED searches: every probe with an impostor, searched against the gallery WITHOUT its own class: its top score is neg_score[x];
+        n = their number;  fpir(t) = #{neg_score >= t} / n.
+      threshold_at_fpir(f) = the smallest float32 t with #{neg_score >= t} <= floor(f n): nextafter above the (floor(f n) + 1)-th largest
+        impostor score, -inf when floor(f n) >= n.  (f n is taken exactly, from the decimal digits of f: 0.29 * 100 is 29.)
+      dir_at_fpir(f) = #{x in M : hit and pos_score[x] >= threshold_at_fpir(f)} / |M|;  fnir_at_fpir = 1 - dir_at_fpir.
+    A ratio with a zero denominator is NaN."""
+
+    def __init__(self, pos_score, pos_index, neg_score, neg_index):
+        f32 = lambda t: torch.as_tensor(t).detach().cpu().float().reshape(-1)
+        i64 = lambda t: torch.as_tensor(t).detach().cpu().long().reshape(-1)
+        ps, pi, ns, ni = f32(pos_score), i64(pos_index), f32(neg_score), i64(neg_index)
+        if not ps.numel() == pi.numel() == ns.numel() == ni.numel():
+            raise ValueError("OpenSetStats: four vectors of one length")
+        self.mated = pi >= 0
+        has_neg = ni >= 0
+        before = (ps > ns) | ((ps == ns) & (pi < ni))
+        self.hit = self.mated & (~has_neg | before)
+        self.pos_score = ps
+        self.n_mated = int(self.mated.sum())
+        self.neg_sorted = ns[has_neg].sort(descending=True).values
+        self.n = int(self.neg_sorted.numel())
+
+    def rank1(self):
+        return int(self.hit.sum()) / self.n_mated if self.n_mated else float('nan')
+
+    def fpir(self, t):
+        return int((self.neg_sorted >= float(t)).sum()) / self.n if self.n else float('nan')
+
+    def threshold_at_fpir(self, f):
+        from fractions import Fraction
+        k = int(Fraction(repr(float(f))) * self.n // 1)
+        if k >= self.n:
+            return float('-inf')
+        return float(torch.nextafter(self.neg_sorted[max(k, 0)], torch.tensor(float('inf'))))
+
+    def dir_at_fpir(self, f):
+        if not self.n_mated:
+            return float('nan')
+        return int((self.hit & (self.pos_score >= self.threshold_at_fpir(f))).sum()) / self.n_mated
+
+    def fnir_at_fpir(self, f):
+        return 1.0 - self.dir_at_fpir(f)
+
+    def metrics(self, fpirs=(0.1, 0.01)):
+        out = {'rank1': self.rank1()}
+        for f in fpirs:
+            out[f'DIR@FPIR={f}'] = self.dir_at_fpir(f)
+            out[f'TH@FPIR={f}'] = self.threshold_at_fpir(f)
+        return out
+
+
 # ---- function forms (one sort per call)
 def roc_curve(scores, labels):
     return PairStats(scores, labels).roc()

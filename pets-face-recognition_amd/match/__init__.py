@@ -7,6 +7,7 @@ CUDA tensors run on the gfx950 kernels (normalise → MFMA GEMM per gallery chun
 optional exact fp32 re-scoring of the candidate lists); CPU tensors use plain torch (the reference's own device
 behaviour, used by the CPU plumbing config).  Ordering everywhere: score descending, ties → lower index.
 """
+import collections
 import ctypes
 
 import torch
@@ -1210,18 +1211,20 @@ def _check_chunk(who, chunk):
         raise PfrError(f"{who}: chunk={chunk} must be >= 1")
 
 
-def _block_launches(fn, a, sa, N, chunk, head, tail):
+def _block_launches(fn, a, sa, N, chunk, head, tail, block_head=None):
     """one `fn` launch per (row block, column block) of the upper triangle with node offsets — the blocks of `cluster`; `head` are the
-    arguments between b_off and the outputs (dtype, D, thr), `tail` the outputs and what follows them"""
+    arguments between b_off and the outputs (dtype, D, thr), `tail` the outputs and what follows them; `block_head(r0, c0)` (c0 None:
+    the block's own pairs) gives further arguments behind `head` that depend on the block"""
     step = N if chunk is None else int(chunk)
     sp = lambda r0: 0 if sa is None else sa[r0:].data_ptr()
+    more = (lambda r0, c0: ()) if block_head is None else block_head
     for r0 in range(0, N, step):
         nr = min(step, N - r0)
         for c0 in range(r0, N, step):
             if c0 == r0:     # the block's own pairs: symmetric mode
-                fn(a[r0:].data_ptr(), sp(r0), nr, r0, 0, 0, 0, 0, *head, *tail)
+                fn(a[r0:].data_ptr(), sp(r0), nr, r0, 0, 0, 0, 0, *head, *more(r0, None), *tail)
             else:
-                fn(a[r0:].data_ptr(), sp(r0), nr, r0, a[c0:].data_ptr(), sp(c0), min(step, N - c0), c0, *head, *tail)
+                fn(a[r0:].data_ptr(), sp(r0), nr, r0, a[c0:].data_ptr(), sp(c0), min(step, N - c0), c0, *head, *more(r0, c0), *tail)
 
 
 def _neighbor_counts_dev(a, sa, N, T, thr, chunk):
@@ -1337,6 +1340,127 @@ def dbscan(emb, threshold, min_samples=4, compute_dtype=torch.float32, normalize
     if int(status.item()) != 0:
         raise PfrError(f"{who}: the union-find gave up on a pair (status {int(status.item())}): a loop reached its iteration cap")
     return (labels.long(), deg >= mn) if return_core else labels.long()
+
+
+# ---- open-set identification: best mate / best impostor / weakest mate ---------------------------------------------------------------
+#: `class_extremes`: fp32 scores and int64 partner indices [N]; no such pair: index -1, score -inf (weak_score: +inf); weak_* None
+#: with weakest=False
+Extremes = collections.namedtuple("Extremes", "pos_score pos_index neg_score neg_index weak_score weak_index")
+
+
+def _check_classes(who, emb, classes, emb_b, classes_b):
+    if (emb_b is None) != (classes_b is None):
+        raise PfrError(f"{who}: emb_b and classes_b go together")
+    for x, c in ((emb, classes), (emb_b, classes_b)):
+        if x is None:
+            continue
+        if not torch.is_tensor(c) or c.dim() != 1 or c.shape[0] != x.shape[0] or c.is_floating_point() or c.dtype == torch.bool:
+            raise PfrError(f"{who}: classes must be an integer tensor [N]")
+        if c.numel() and (int(c.max()) >= 2 ** 31 or int(c.min()) < -2 ** 31):
+            raise PfrError(f"{who}: classes must fit int32")
+
+
+def _class_extremes_torch(emb, classes, emb_b, classes_b, normalize, weakest, chunk=2048):
+    """the contract of pfr_class_extremes on the host, dense fp32 by row chunks: mate iff the classes are equal and not negative, a NaN
+    score updates nothing, -0.0 canonicalised by s + 0.0, the highest (weakest: lowest) score and then the smallest partner index"""
+    a = _unit_rows_f32(emb, normalize)
+    sym = emb_b is None
+    b = a if sym else _unit_rows_f32(emb_b, normalize)
+    ca = classes.long()
+    cb = ca if sym else classes_b.long()
+    Na, Nb = a.shape[0], b.shape[0]
+    cols = torch.arange(Nb)
+    inf = float("inf")
+    out = [torch.full((Na,), -inf), torch.full((Na,), -1, dtype=torch.int64), torch.full((Na,), -inf), torch.full((Na,), -1, dtype=torch.int64),
+           torch.full((Na,), inf), torch.full((Na,), -1, dtype=torch.int64)]
+
+    def pick(ok, s, lowest, score, index, rows):
+        sc = torch.where(ok, -s if lowest else s, torch.full_like(s, -inf))
+        top = sc.max(dim=1, keepdim=True).values
+        first = (ok & (sc == top)).int().argmax(dim=1)          # (argmax of a 0/1 row: the first, i.e. smallest, index)
+        has = ok.any(dim=1)
+        score[rows[has]] = s[has, first[has]]
+        index[rows[has]] = first[has]
+    for r0 in range(0, Na, chunk):
+        s = a[r0:r0 + chunk] @ b.t() + 0.0
+        rows = torch.arange(r0, r0 + s.shape[0])
+        valid = ~torch.isnan(s)
+        if sym:
+            valid &= rows[:, None] != cols[None, :]
+        mate = (ca[rows][:, None] == cb[None, :]) & (ca[rows][:, None] >= 0)
+        if Nb:
+            pick(valid & mate, s, False, out[0], out[1], rows)
+            pick(valid & ~mate, s, False, out[2], out[3], rows)
+            if weakest:
+                pick(valid & mate, s, True, out[4], out[5], rows)
+    return Extremes(*out[:4], *(out[4:] if weakest else (None, None)))
+
+
+def class_extremes(emb, classes, emb_b=None, classes_b=None, compute_dtype=torch.float32, normalize=True, chunk=None, weakest=True):
+    """Per item of `emb` [N, D] the BEST MATE (the highest score against an item of the same class), the BEST IMPOSTOR (the highest score
+    against an item of any other class) and — with weakest=True — the WEAKEST MATE (the lowest same-class score), each with the partner's
+    index: what open-set identification (`open_set_metrics`), label cleaning (`label_suspects`) and hard-pair mining need, and what
+    cannot be had from truncated top-K lists.  `classes` int [N]; a NEGATIVE class is "unlabelled / distractor": no mates, an impostor to
+    everyone.  The score is that of `pairs_above` (dot product of the L2-normalised rows in `compute_dtype`); an item is never its own
+    mate; a NaN score counts for nothing; ties go to the smallest partner index, -0.0 equals +0.0.  With `emb_b`, `classes_b` the
+    result is for the rows of `emb` against the gallery `emb_b` (indices into `emb_b`).
+    → Extremes(pos_score, pos_index, neg_score, neg_index, weak_score, weak_index): fp32 / int64 [N]; no such pair: index -1 and score
+    -inf (weak_score: +inf); weak_* are None with weakest=False.
+    CUDA tensors: pfr_class_extremes, the match GEMM with a class-conditioned atomic-max epilogue (one launch, or with `chunk` one per
+    (row block, column block) as in `cluster`; with `emb_b` one per row block), then pfr_extremes_decode; nothing N x N is written.
+    CPU tensors: chunked dense fp32 matmul, same contract.  Not covered: more than one extreme per item (`cosine_topk`)."""
+    who = "class_extremes"
+    _check_pair_sets(who, emb, emb_b, compute_dtype)
+    _check_chunk(who, chunk)
+    _check_classes(who, emb, classes, emb_b, classes_b)
+    if not emb.is_cuda:
+        return _class_extremes_torch(emb, classes, emb_b, classes_b, normalize, weakest)
+    dev, sym = emb.device, emb_b is None
+    N = emb.shape[0]
+    nk = 3 if weakest else 2
+    keys = torch.zeros(nk, max(N, 1), dtype=torch.int64, device=dev)
+    Nb = N if sym else emb_b.shape[0]
+    if N and Nb and not (sym and N == 1):
+        T = dtype_id(compute_dtype)
+        a, sa = _hist_operand(emb, compute_dtype, normalize)
+        ca = classes.to(device=dev, dtype=torch.int32).contiguous()
+        tail = (keys[0].data_ptr(), keys[1].data_ptr(), keys[2].data_ptr() if weakest else 0, N, _stream())
+        if sym:
+            _block_launches(lib.pfr_class_extremes, a, sa, N, chunk, (T, a.shape[1]), tail,
+                            block_head=lambda r0, c0: (ca[r0:].data_ptr(), 0 if c0 is None else ca[c0:].data_ptr(), 1))
+        else:
+            b, sb = _hist_operand(emb_b.to(dev), compute_dtype, normalize)
+            cb = classes_b.to(device=dev, dtype=torch.int32).contiguous()
+            step = N if chunk is None else int(chunk)
+            for r0 in range(0, N, step):
+                lib.pfr_class_extremes(a[r0:].data_ptr(), 0 if sa is None else sa[r0:].data_ptr(), min(step, N - r0), r0, b.data_ptr(),
+                                       0 if sb is None else sb.data_ptr(), Nb, 0, T, a.shape[1], ca[r0:].data_ptr(), cb.data_ptr(), 0, *tail)
+    out = []
+    for k in range(nk):
+        score = torch.empty(N, dtype=torch.float32, device=dev)
+        index = torch.empty(N, dtype=torch.int32, device=dev)
+        lib.pfr_extremes_decode(keys[k].data_ptr(), N, 1 if k == 2 else 0, score.data_ptr(), index.data_ptr(), _stream())
+        out += [score, index.long()]
+    return Extremes(*out, *(() if weakest else (None, None)))
+
+
+def open_set_metrics(emb, classes, fpir=(0.1, 0.01), emb_b=None, classes_b=None, compute_dtype=torch.float32, normalize=True):
+    """Open-set identification (engine.metrics.OpenSetStats over `class_extremes`): 'rank1', and per false-positive identification rate f
+    'DIR@FPIR={f}' — the share of the probes with a mate whose best mate comes back at rank 1 at or above the threshold that raises a
+    false alarm for at most f of the searches without a mate — and 'TH@FPIR={f}', that threshold (on the score).  FNIR = 1 - DIR."""
+    from ..engine.metrics import OpenSetStats
+    ex = class_extremes(emb, classes, emb_b, classes_b, compute_dtype=compute_dtype, normalize=normalize, weakest=False)
+    return OpenSetStats(ex.pos_score, ex.pos_index, ex.neg_score, ex.neg_index).metrics(fpir)
+
+
+def label_suspects(extremes):
+    """Label suspects for dataset cleaning: → int64 indices of the items WITH a mate whose best impostor ranks before their best mate
+    (score descending, then index ascending), sorted by neg_score - pos_score descending, then by index."""
+    ps, pi = extremes.pos_score.detach().cpu().float(), extremes.pos_index.detach().cpu().long()
+    ns, ni = extremes.neg_score.detach().cpu().float(), extremes.neg_index.detach().cpu().long()
+    idx = ((pi >= 0) & (ni >= 0) & ((ns > ps) | ((ns == ps) & (ni < pi)))).nonzero(as_tuple=True)[0]
+    order = torch.sort(ns[idx] - ps[idx], descending=True, stable=True).indices
+    return idx[order]
 
 
 def cluster_metrics(labels, classes):
