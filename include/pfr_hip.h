@@ -940,6 +940,44 @@ long pfr_augment_fit_ws_bytes(long total_bytes, int N);
 int pfr_augment_fit(const unsigned char* data, const long* offsets, const int* records, const int* coeffs, int N, int canvas_h,
                     int canvas_w, unsigned char* out_u8, void* ws, pfr_stream_t stream);
 
+/* ---- landmark alignment: homography solve (host) and perspective warp (device) (csrc/pfr_align.hip) ----
+ * The reference's preprocessor/align.py: fit a homography from 3 or 4 landmarks onto base_pts, warp the frame to dsize.
+ * OpenCV is not available to this project, so bit-identity with a cv2 build cannot be tested and is NOT claimed.  The contract
+ * below is ours.  It follows OpenCV's published scheme for warpPerspective(..., INTER_LINEAR, BORDER_CONSTANT 0): inverse map in
+ * fp64, source coordinates quantised to 1/32 pixel, 15-bit integer weights.  It fixes every operation.  It is pinned two ways: a
+ * numpy restatement (tests/align_oracle.py), which the device must equal bit for bit, and Pillow's Image.transform(PERSPECTIVE,
+ * BILINEAR), an independent implementation, which must lie within a derived bound of the restatement (tests/test_align_host.py).
+ *
+ * pfr_align_solve (HOST arrays; no device work): pts fp64 [N][npts][2] = (x, y), base fp64 [npts][2] → minv fp64 [N][9], the
+ * INVERSE map (output pixel → source pixel, inverted in fp64 by the adjugate; the warp never inverts anything), and valid [N].
+ *   mode 0 `reference` (npts 3 or 4): with 3 points the centroid of the three is prepended to both point sets, each coordinate
+ *     rounded half-to-even (np.round(np.mean(...)), align.py:8-9); then the exact homography through the 4 correspondences: an 8x8
+ *     system in fp64 with partial pivoting, h33 = 1.  With exactly four correspondences the reference's RANSAC + refinement has
+ *     nothing to choose or refine, which is why the exact solve is the restatement.
+ *   mode 1 `similarity` (npts >= 2): the least-squares rotation + uniform scale + translation, the 2-D closed form with no
+ *     reflection; last row 0 0 1.
+ *   valid[n] = 0 with minv[n] all zeros when two landmarks are not more than min_distance apart (the reference's strict
+ *   `assert all(i > self.min_distance ...)`), when the system is singular (a pivot below 1e-12 x the largest entry, or the solved
+ *   map does not return the points to 1e-6 px; similarity: a degenerate spread or scale), or when any entry is non-finite.
+ *   The call still returns 0: an invalid frame is data, not an error.
+ *
+ * pfr_align_warp: data / offsets = the ragged batch exactly as pfr_augment_fit takes it, shapes int32 [N][2] = (H, W) and minv
+ * [N][9] on the device.  mask may be NULL; otherwise packed uint8 [H][W] planes, each starting on a 16-byte boundary, at
+ * mask_offsets int64 [N] (device); a zero byte drops the pixel.  out_u8 [N][out_h][out_w][3].  For output pixel (x, y) of frame n
+ * with m = minv[n], every step in IEEE double, in this order, with NO fused multiply-add:
+ *   X0 = (m0*x + m1*y) + m2, Y0 = (m3*x + m4*y) + m5, W0 = (m6*x + m7*y) + m8;  s = W0 != 0 ? 32.0 / W0 : 0.0;
+ *   fx = X0*s, fy = Y0*s; a non-finite fx or fy makes the pixel 0,0,0, and so does the all-zero matrix, pfr_align_solve's mark of
+ *   a rejected frame (by the steps above alone it would sample source pixel (0, 0) everywhere); otherwise clamp to [-2^31, 2^31-1] and round to nearest,
+ *   ties to even → integers X, Y;  ix = X >> 5 (arithmetic), ax = X & 31; the same for y.
+ *   Taps (iy, ix), (iy, ix+1), (iy+1, ix), (iy+1, ix+1) with weights (32-ax)(32-ay)*32, ax(32-ay)*32, (32-ax)ay*32, ax*ay*32 (sum
+ *   32768); a tap outside the frame, or whose mask byte is 0, contributes 0; channel = (sum w*p + 16384) >> 15.
+ * No address is formed from a coordinate that has not passed the per-tap range test; offsets are 64-bit.  One thread per output
+ * pixel, no LDS, no atomics: bit-reproducible.  gfx950 build: 22 VGPRs, no scratch.  N == 0 or an empty output returns 0 without a
+ * launch; an output side above 4096 or a null required pointer is PFR_ERR_ARG. */
+int pfr_align_solve(int mode, const double* pts, const double* base, int N, int npts, double min_distance, double* minv, int* valid);
+int pfr_align_warp(const unsigned char* data, const long* offsets, const int* shapes, const double* minv, const unsigned char* mask,
+                   const long* mask_offsets, int N, int out_h, int out_w, unsigned char* out_u8, pfr_stream_t stream);
+
 /* Linear layer with a fused activation epilogue — the Swin MLP `FeedForward` (reference models/swin.py:40-52: Linear →
  * GELU → Linear) and its autograd.  x [M][K], w [N][K] (nn.Linear layout), y / y2 [M][N], all of `dtype`.
  *   act 2: y2 = x·wT + bias (pre-activation, kept for backward), y = gelu(y2)            (forward of the first Linear)

@@ -26,6 +26,7 @@ _CTYPES = {
     "long": ctypes.c_long,
     "size_t": ctypes.c_size_t,
     "float": ctypes.c_float,
+    "double": ctypes.c_double,
     "pfr_stream_t": ctypes.c_void_p,
 }
 

@@ -33,7 +33,9 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
          noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
          ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd', sub_centers=1, augment_extra=None, margin=None,
-         margin_kwargs=None, sample_rate=None, sparse_grad=None):
+         margin_kwargs=None, sample_rate=None, sparse_grad=None, align=None):
+    # align: dict(jitter=…, estimate=…, masks=…) puts the landmark alignment (data_loading/align.py, the reference's preprocessor/align.py) in front
+    # of the head pipeline: ragged raw frames + three landmarks -> DeviceAlign(base_pts, (image_size, image_size, 3)) -> the head augmentation
     # sample_rate / sparse_grad: Partial FC in the margin head (losses/large_margin.py); None = every class is scored, as in the reference
     # augment_extra: further DeviceAugmentation keywords of the train pipeline (p_hflip, color_jitter, p_grayscale, erasing); None = the reference's pipeline
     if augment_extra and not device_augment:
@@ -47,11 +49,14 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
     # 'simple' / 'body' (ragged frames: the detector's raw crops, each with its own size)
     if pipeline not in ('head', 'simple', 'body'):
         raise ValueError(f"pipeline must be 'head', 'simple' or 'body', got {pipeline!r}")
-    if (pipeline != 'head') != bool(ragged) or (ragged and not device_augment):
+    if align is not None and not (ragged and device_augment and pipeline == 'head'):
+        raise ValueError("align reads ragged frames and hands uniform ones to the 'head' pipeline (ragged=True, device_augment=True, pipeline='head')")
+    if (pipeline != 'head') != (bool(ragged) and align is None) or (ragged and not device_augment):
         raise ValueError("the 'simple' and 'body' pipelines read ragged frames (ragged=True, device_augment=True); 'head' reads uniform ones")
     torch.manual_seed(seed)
     dataset = SyntheticRecDataset(n_train_ids + n_val_ids, photos, image_size, seed=seed, noise=noise, raw_uint8=device_augment,
-                                  noise_bank=noise_bank, **({'ragged': True} if ragged else {}))
+                                  noise_bank=noise_bank, **({'ragged': True} if ragged else {}),
+                                  **({'landmarks': True, 'masks': bool(align.get('masks'))} if align is not None else {}))
     collate = {}
     if ragged:
         from data_loading import ragged_collate
@@ -157,6 +162,14 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
     def val_dataloader():
         return DataLoader(val, _live('test_batch_size', test_bs), num_workers=0, **collate)
 
+    if align is not None:
+        from data_loading import DeviceAlign
+        base_pts, dsize = dataset.base_pts((image_size, image_size)), (image_size, image_size, 3)
+        kw = dict(estimate=align.get('estimate', 'reference'), min_distance=align.get('min_distance', 5.0))
+        ns['device_align'] = DeviceAlign(base_pts, dsize, **kw)
+        if align.get('jitter'):    # landmark jitter is a training augmentation: the validation frames are aligned on the landmarks as given
+            ns['device_train_align'] = DeviceAlign(base_pts, dsize, jitter=align['jitter'],
+                                                   generator=torch.Generator().manual_seed(seed + 7919 * (_rank() + 1)), **kw)
     if device_augment and pipeline != 'head':
         # simple_fe_dog.py:17-31 / body_dog_fe.py:18-33 on ragged batches, at this config's network input size
         from data_loading import DeviceAugmentation

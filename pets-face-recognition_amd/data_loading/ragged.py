@@ -48,10 +48,16 @@ def unpack_frames(x):
 
 
 def ragged_collate(samples):
-    """samples: dataset items whose 'x' is a uint8 [H, W, 3] tensor; every other key is collated as usual"""
+    """samples: dataset items whose 'x' is a uint8 [H, W, 3] tensor; a 'mask' (uint8 [H, W], the frame's size) is packed the same way
+    (data_loading/align.py pack_masks); every other key, the landmarks 'pts' among them, is collated as usual"""
     from torch.utils.data import default_collate
-    batch = default_collate([{k: v for k, v in s.items() if k != 'x'} for s in samples])
+    batch = default_collate([{k: v for k, v in s.items() if k not in ('x', 'mask')} for s in samples])
     batch['x'] = pack_frames([s['x'] for s in samples])
+    if 'pts' in batch:
+        batch['pts_host'] = batch['pts'].numpy().copy()      # stays on the host like 'shape_host': the solve runs there
+    if samples and 'mask' in samples[0]:
+        from .align import pack_masks
+        batch['mask'] = pack_masks([s['mask'] for s in samples])
     return batch
 
 

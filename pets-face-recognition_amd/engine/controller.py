@@ -32,6 +32,8 @@ class Controller(nn.Module):
         self.logger = None
         self.current_epoch = 0
         self.last_metrics = {}
+        self.align_rejected = 0          # frames the landmark alignment rejected so far (config.device_align)
+        self.last_align_valid = None
 
     def forward(self, *args, **kwargs):
         return self.model_loss(*args, **kwargs)
@@ -54,7 +56,21 @@ class Controller(nn.Module):
         """uint8 [N, H, W, 3] batches are raw frames: the config's device-side Compose pipeline (the reference's
         train_augmentation / val_augmentation, fe_dogs_config.py:17-32) turns them into the float NCHW batch.  A dict with 'data'
         and 'shape' is a ragged batch of raw frames (data_loading/ragged.py) and goes through the same config entries, whose fit
-        stage brings it to the network's canvas first"""
+        stage brings it to the network's canvas first.
+        `x` may be the whole batch dict: when the config defines `device_align` (data_loading/align.py; `device_train_align`, if
+        defined, in training) and the batch carries the landmarks 'pts' (and optionally 'mask'), a ragged batch['x'] is aligned first
+        (the reference's preprocessor/align.py) and the uniform uint8 result continues like any uniform uint8 batch.  The frames
+        the solve rejected are counted in `align_rejected`; `last_align_valid` holds the flags of this batch (None: not aligned)."""
+        self.last_align_valid = None
+        if isinstance(x, dict) and 'x' in x:
+            batch, x = x, x['x']
+            align = self.config.get('device_align')
+            if train and self.config.get('device_train_align') is not None:
+                align = self.config.get('device_train_align')
+            if align is not None and 'pts' in batch and isinstance(x, dict) and 'data' in x and 'shape' in x:
+                x, valid = align(x, batch['pts_host'] if 'pts_host' in batch else batch['pts'], batch.get('mask'))
+                self.last_align_valid = valid
+                self.align_rejected += int((~valid).sum())
         if isinstance(x, dict) and 'data' in x and 'shape' in x:
             aug = self.config.get('device_train_augmentation' if train else 'device_val_augmentation')
             if aug is None:
@@ -68,16 +84,34 @@ class Controller(nn.Module):
         return aug(x)
 
     def training_step(self, batch, batch_idx=0):
-        out = self.model_loss(self._images(batch['x'], True), batch['label'])
+        x, label = self._images(batch, True), batch['label']
+        if self.last_align_valid is not None and not self.last_align_valid.all():
+            # frames whose landmarks the solve rejected come back all zero: they are DROPPED from the step, never trained on
+            keep = torch.from_numpy(self.last_align_valid).to(label.device)
+            if not bool(self.last_align_valid.any()):
+                raise ValueError("training_step: the alignment rejected every frame of the batch")
+            x, label = x[keep], label[keep]
+        out = self.model_loss(x, label)
         # a MagFace head's length regulariser (part of the loss already): kept for the Trainer's loss line
         self.last_regulariser = out.get('loss_g') if isinstance(out, dict) else None
         return out['loss']
 
     def validation_step(self, batch, batch_idx=0, dataset_idx=0):
-        return {'emb': self.model_loss(self._images(batch['x'], False)), 'label': batch['label'], 'index': batch['index']}
+        out = {'emb': self.model_loss(self._images(batch, False)), 'label': batch['label'], 'index': batch['index']}
+        if self.last_align_valid is not None:
+            # evaluation keeps every row (the pair lists index the set by position); the rejected frames are reported, 'Align rejected'
+            out['align_rejected'] = int((~self.last_align_valid).sum())
+        return out
 
     def test_step(self, batch, batch_idx=0, dataset_idx=0):
         return self.validation_step(batch, batch_idx, dataset_idx)
+
+    @staticmethod
+    def _align_rejected(outputs_i):
+        """{'Align rejected': n} when the set went through device_align, {} otherwise"""
+        if not any('align_rejected' in o for o in outputs_i):
+            return {}
+        return {'Align rejected': sum(o.get('align_rejected', 0) for o in outputs_i)}
 
     # ------------------------------------------------------------------ evaluation
     @staticmethod
@@ -241,6 +275,7 @@ class Controller(nn.Module):
             metrics.update(self._dbscan(emb, classes, ps))
             metrics.update(self._open_set(emb, classes))
             metrics.update(self._quality(emb, scores, labels, pair_generator))
+            metrics.update(self._align_rejected(outputs[i]))
             print('', *[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')
             all_metrics[name] = metrics
         self.last_metrics = all_metrics
@@ -295,6 +330,7 @@ class Controller(nn.Module):
             metrics.update(self._dbscan(emb, classes, ps))
             metrics.update(self._open_set(emb, classes))
             metrics.update(self._quality(emb, scores, labels, pair_generator))
+            metrics.update(self._align_rejected(outputs[i]))
             all_metrics[name] = metrics
             self.last_confmat[name] = confmat
             print(*[f'{name} {k}\t{v}' for k, v in metrics.items()], sep='\n')

@@ -225,7 +225,7 @@ class Trainer:
             for bi, batch in enumerate(controller.train_dataloader()):
                 if self.limit_train_batches is not None and bi >= self.limit_train_batches:
                     break
-                yield controller._images(_to_device(batch, device)['x'], True)
+                yield controller._images(_to_device(batch, device), True)      # the batch itself: a device_align config needs its 'pts'
         update_bn(images(), controller.model_loss)
         if self.ddp is not None:
             self.ddp.sync_buffers()   # each rank saw its own shard: every rank keeps rank 0's statistics
