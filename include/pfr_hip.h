@@ -606,6 +606,16 @@ int pfr_pair_curve(const float* scores, const int* labels, int P, void* workspac
 int pfr_pair_hist(const void* a, const float* a_scale, const int* a_cls, int Na, const void* b, const float* b_scale, const int* b_cls,
                   int Nb, int dtype, int D, float lo, float inv_w, int bins, unsigned long long* hist, pfr_stream_t stream);
 
+/* pfr_pair_tile_coords (host only, no device needed): the tile queue of csrc/pfr_tilewalk.h, which pfr_rank_count, pfr_pairs_above and
+ *   pfr_class_extremes walk (pfr_pair_hist, pfr_card_max_scores, pfr_neighbor_count and pfr_dbscan_link walk the same order with
+ *   private copies of the arithmetic, which this entry does not run).  The Na x Nb score matrix is cut into 128 x 128 tiles and those
+ *   into super-tiles of 16 x 16 tiles; slot t of the queue is tile t % 256 (row-major) of super-tile t / 256 (row-major; sym != 0,
+ *   Na == Nb: the super-tiles of the upper triangle only).  For the slots t0 .. t0 + n - 1 coords [n][2] int32 receives the tile row
+ *   and column, or -1, -1 for a slot that holds no tile (past the last tile row / column, or below the diagonal in symmetric mode).
+ *   Every tile (symmetric: every tile with column >= row) is in exactly one slot.  The queue has 256 * (super-tile count) slots; slots
+ *   outside it, Na or Nb < 1 and a symmetric Na != Nb return PFR_ERR_ARG. */
+int pfr_pair_tile_coords(long t0, int n, int Na, int Nb, int sym, int* coords);
+
 /* ---- exact retrieval ranks (mAP / CMC / mINP): the match GEMM with a RANK-COUNTING epilogue.  The rank of a positive is the number of
  * items that precede it, so it is counted where the MFMA leaves the scores; nothing Na x Nb is written and nothing is sorted.
  *   Scores.  a [Na][D], b [Nb][D], a_scale, b_scale, dtype, D: the operands, layouts and D multiples of pfr_pair_hist, and its score

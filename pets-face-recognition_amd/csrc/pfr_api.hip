@@ -1,5 +1,6 @@
 // pfr_api.hip — C-ABI housekeeping: thread-local error string, version, device probe.
 #include "pfr_common.h"
+#include "pfr_tilewalk.h"
 #include <stdarg.h>
 #include <string.h>
 
@@ -58,4 +59,23 @@ extern "C" int pfr_get_tuning(const char* key, int* value) {
     if (!strcmp(kKnobs[k].name, key)) { *value = g_pfr_knob[k]; return PFR_OK; }
   pfr_set_error("pfr_get_tuning: unknown key %s", key);
   return PFR_ERR_ARG;
+}
+
+// The tile queue of the pair entry points on the host (no device work): for the queue indices t0 .. t0 + n - 1 of a walk over Na x Nb
+// rows, coords[2 k] / coords[2 k + 1] = the tile row and column of slot t0 + k, or -1 / -1 for a slot that holds no tile.
+extern "C" int pfr_pair_tile_coords(long t0, int n, int Na, int Nb, int sym, int* coords) {
+  const char* who = "pfr_pair_tile_coords";
+  PFR_CHECK_ARG(Na >= 1 && Nb >= 1 && (!sym || Na == Nb), "%s: Na=%d, Nb=%d must be >= 1 (and equal in symmetric mode)", who, Na, Nb);
+  const TileWalk w = tw_from_rows(Na, Nb, sym != 0);
+  const long long total = w.nsuper * (RC_SUPER * RC_SUPER);
+  PFR_CHECK_ARG(t0 >= 0 && n >= 0 && (long long)t0 + n <= total, "%s: slots [%ld, %ld + %d) are not inside the queue of %lld", who, t0, t0, n,
+                total);
+  PFR_CHECK_ARG(n == 0 || coords, "%s: null pointer", who);
+  for (int k = 0; k < n; ++k) {
+    int tm, tn;
+    const bool tile = tw_tile((long long)t0 + k, w.ntm, w.ntn, w.nsn, sym != 0, tm, tn);
+    coords[2 * k] = tile ? tm : -1;
+    coords[2 * k + 1] = tile ? tn : -1;
+  }
+  return PFR_OK;
 }

@@ -2,13 +2,12 @@
 // of the qualifying pairs and / or a lock-free union-find on a parent array), the same union over an explicit edge list (pfr_cc_union)
 // and the flatten pass that turns the forest into canonical labels (pfr_cc_flatten); contract in include/pfr_hip.h.
 //
-// Schedule (pfr_pairhist.hip's): persistent workgroups (2 per CU) walk a queue of 128 x 128 tiles in super-tiles of 16 x 16 tiles;
-// symmetric mode enumerates the super-tiles of the upper triangle only and skips the tiles below the diagonal.  The tile product is
-// rc_tile_gemm / rc_score of pfr_pairtile.h — the code pfr_pair_scores_gather runs — so a score has the gather's bits.
+// Schedule and tile product: the tile queue of pfr_tilewalk.h (2 persistent workgroups per CU) and rc_tile_gemm / rc_score of
+// pfr_pairtile.h — the code pfr_pair_scores_gather runs — so a score has the gather's bits.
 //
 // Epilogue, per wave (its 64 x 64 part of the tile = 64 accumulator registers per lane):
-//   1. every lane builds the 64-bit mask of its qualifying registers (valid element and s >= thr); ONE wave vote; nothing qualifies
-//      (almost every tile of a realistic threshold): the wave is done.
+//   1. every lane builds the 64-bit mask of its qualifying registers (valid element, RC_VALID of pfr_pairtile.h, and s >= thr); ONE wave
+//      vote; nothing qualifies (almost every tile of a realistic threshold): the wave is done.
 //   2. edges: the lanes' population counts, an inclusive wave scan, ONE agent-scope add of the wave's total to *count by the last lane
 //      (reserve per wave, never per lane); every lane then writes its own pairs at base + its exclusive prefix + 0, 1, ...
 //      while the position is below cap.
@@ -18,16 +17,8 @@
 #include "pfr_pairtile.h"
 #include "pfr_unionfind.h"
 
-#define CL_LDS (2 * RC_T * RC_ROWB + 2 * RC_T * 4)   // 33 792 bytes: under the default limit
-
 struct ClusterParams {
-  const char* a;
-  const char* b;
-  const float* a_scale;
-  const float* b_scale;
-  int Na, Nb, sym;
-  int a_off, b_off;
-  int rowb;                 // bytes per operand row
+  PairOperands o;
   float thr;
   int* edge_i;
   int* edge_j;
@@ -37,68 +28,32 @@ struct ClusterParams {
   int* parent;
   int n_nodes, budget;
   int* status;
-  int ntm, ntn, nsn;
-  long long nsuper;
 };
 
 template <typename T>
 __global__ __launch_bounds__(256, 2) void pairs_above_kernel(const ClusterParams p) {   // (2 workgroups per CU: at most 256 registers)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ldsA = smem;                                  // [128][128 B]
-  char* ldsB = smem + RC_T * RC_ROWB;                 // [128][128 B]
-  float* scA = reinterpret_cast<float*>(smem + 2 * RC_T * RC_ROWB);
-  float* scB = scA + RC_T;
+  char *ldsA, *ldsB;
+  float *scA, *scB;
+  rc_carve(smem, ldsA, ldsB, scA, scB);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wp = wave >> 1, wq = wave & 1;
-  const int lc = tid & 7, lr = tid >> 3;
-  const int nk = p.rowb / RC_ROWB;
-  const long long total = p.nsuper * (RC_SUPER * RC_SUPER);
+  const int nk = p.o.rowb / RC_ROWB;
+  const long long total = p.o.nsuper * (RC_SUPER * RC_SUPER);
   for (long long t = blockIdx.x; t < total; t += gridDim.x) {
-    const long long su = t / (RC_SUPER * RC_SUPER);
-    const int l = (int)(t % (RC_SUPER * RC_SUPER));
-    int sm, sn;
-    if (p.sym) {
-      // super-tile su of the upper triangle, row-major: row r starts at r * ns - r (r - 1) / 2
-      const double ns2 = 2.0 * p.nsn + 1.0;
-      int r = (int)((ns2 - sqrt(ns2 * ns2 - 8.0 * (double)su)) * 0.5);
-      r = r < 0 ? 0 : (r > p.nsn - 1 ? p.nsn - 1 : r);
-      while (r > 0 && (long long)r * p.nsn - (long long)r * (r - 1) / 2 > su) --r;
-      while ((long long)(r + 1) * p.nsn - (long long)(r + 1) * r / 2 <= su) ++r;
-      sm = r;
-      sn = r + (int)(su - ((long long)r * p.nsn - (long long)r * (r - 1) / 2));
-    } else {
-      sm = (int)(su / p.nsn);
-      sn = (int)(su % p.nsn);
-    }
-    const int tm = sm * RC_SUPER + l / RC_SUPER, tn = sn * RC_SUPER + l % RC_SUPER;
-    if (tm >= p.ntm || tn >= p.ntn || (p.sym && tn < tm)) continue;   // (block-uniform)
+    int tm, tn;
+    if (!tw_tile(t, p.o.ntm, p.o.ntn, p.o.nsn, p.o.sym, tm, tn)) continue;   // (block-uniform)
     const int row0 = tm * RC_T, col0 = tn * RC_T;
-
-    // operand rows of a ragged last tile are clamped to the last valid row (their scores are masked below)
     const char* ga[4];
     const char* gb[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int ra = min(row0 + lr + 32 * u, p.Na - 1), rb = min(col0 + lr + 32 * u, p.Nb - 1);
-      ga[u] = p.a + (size_t)ra * p.rowb + lc * 16;
-      gb[u] = p.b + (size_t)rb * p.rowb + lc * 16;
-    }
+    rc_operand_rows(p.o.a, p.o.b, p.o.rowb, row0, col0, p.o.Na, p.o.Nb, tid, ga, gb);
     f32x16 acc[2][2];
-    rc_tile_gemm<T>(ga, gb, nk, ldsA, ldsB, tid, true, acc, [&] {
-      if constexpr (sizeof(T) == 1) {
-        if (tid < RC_T) {
-          const int ra = min(row0 + tid, p.Na - 1), rb = min(col0 + tid, p.Nb - 1);
-          scA[tid] = p.a_scale[ra];
-          scB[tid] = p.b_scale[rb];
-        }
-      }
-    });
-    // (the staged scales are behind the second barrier of the first k-step; the next tile's first barrier keeps them until every wave
-    //  has left this epilogue)
+    rc_tile_gemm<T>(ga, gb, nk, ldsA, ldsB, tid, true, acc,
+                    [&] { rc_stage_scales<T>(p.o.a_scale, p.o.b_scale, row0, col0, p.o.Na, p.o.Nb, tid, scA, scB); });
 
     // ---- 1. the lanes' qualifying masks: bit (j * 2 + i) * 16 + r <-> acc[i][j][r]
-    const bool diag = p.sym && tm == tn;
-    const bool full = !diag && row0 + RC_T <= p.Na && col0 + RC_T <= p.Nb;   // no element of the tile is masked
+    const bool diag = rc_tile_diag(p.o.sym, tm, tn);
+    const bool full = rc_tile_full(diag, row0, col0, p.o.Na, p.o.Nb);
     unsigned long long mask = 0ull;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -115,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void pairs_above_kernel(const ClusterParams
           float sa = 0.f;
           if constexpr (sizeof(T) == 1) sa = scA[rl];
           const float s = rc_score<T>(acc[i][j][r], sa, sb);
-          const bool ok = full || (gi < p.Na && gj < p.Nb && (!diag || gi < gj));
+          const bool ok = RC_VALID(full, diag, gi, gj, p.o.Na, p.o.Nb);
           if (ok && s >= p.thr) mask |= 1ull << ((j * 2 + i) * 16 + r);
         }
       }
@@ -143,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void pairs_above_kernel(const ClusterParams
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int cl = wq * 64 + j * 32 + (lane & 31);
-        const int v = p.b_off + col0 + cl;
+        const int v = p.o.b_off + col0 + cl;
         float sb = 0.f;
         if constexpr (sizeof(T) == 1) sb = scB[cl];
 #pragma unroll
@@ -152,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void pairs_above_kernel(const ClusterParams
           for (int r = 0; r < 16; ++r) {
             if (!((mask >> ((j * 2 + i) * 16 + r)) & 1ull)) continue;
             const int rl = wp * 64 + i * 32 + acc_row(r, lane);
-            const int u = p.a_off + row0 + rl;
+            const int u = p.o.a_off + row0 + rl;
             if (p.edge_i) {
               if (pos < p.cap) {
                 p.edge_i[pos] = u;
@@ -198,42 +153,23 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(int* parent, int n_node
 extern "C" int pfr_pairs_above(const void* a, const float* a_scale, int Na, int a_off, const void* b, const float* b_scale, int Nb,
                                int b_off, int dtype, int D, float thr, int* edge_i, int* edge_j, float* edge_s, long cap,
                                unsigned long long* count, int* parent, int n_nodes, int* status, hipStream_t stream) {
-  int esz = 0;
-  if (int rc = rc_check_operands("pfr_pairs_above", dtype, D, &esz)) return rc;
-  const bool sym = b == nullptr;
-  if (sym) { b = a; b_scale = a_scale; Nb = Na; b_off = a_off; }
-  PFR_CHECK_ARG(Na >= 0 && Nb >= 0, "pfr_pairs_above: negative row count");
-  PFR_CHECK_ARG(a_off >= 0 && b_off >= 0, "pfr_pairs_above: negative offset");
-  PFR_CHECK_ARG(a_off <= INT_MAX - Na && b_off <= INT_MAX - Nb, "pfr_pairs_above: offset + rows pass 2^31 - 1");
-  PFR_CHECK_ARG(edge_i || parent, "pfr_pairs_above: neither an edge list nor a parent array");
-  PFR_CHECK_ARG(!edge_i || (edge_j && count && cap >= 0), "pfr_pairs_above: an edge list needs edge_j, count and cap >= 0");
-  PFR_CHECK_ARG(edge_i || (!edge_j && !edge_s), "pfr_pairs_above: edge_j / edge_s without edge_i");
-  PFR_CHECK_ARG(!parent || (status && n_nodes >= 0), "pfr_pairs_above: a parent array needs status and n_nodes >= 0");
-  if (Na == 0 || Nb == 0 || (sym && Na == 1)) return PFR_OK;   // no pair
-  PFR_CHECK_ARG(a && b, "pfr_pairs_above: null pointer");
-  PFR_CHECK_ARG(dtype != PFR_I8 || (a_scale && b_scale), "pfr_pairs_above: int8 rows need their scales");
-  PFR_CHECK_ARG(pfr_all_dev({a, b, a_scale, b_scale, edge_i, edge_j, edge_s, count, parent, status}),
-                "pfr_pairs_above: every pointer must be device memory");
-
+  const char* who = "pfr_pairs_above";
   ClusterParams p = {};
-  p.a = static_cast<const char*>(a); p.b = static_cast<const char*>(b);
-  p.a_scale = a_scale; p.b_scale = b_scale;
-  p.Na = Na; p.Nb = Nb; p.sym = sym ? 1 : 0;
-  p.a_off = a_off; p.b_off = b_off;
-  p.rowb = D * esz;
+  if (int rc = rc_operands(who, a, a_scale, Na, a_off, b, b_scale, Nb, b_off, dtype, D, &p.o)) return rc;
+  PFR_CHECK_ARG(p.o.Na >= 0 && p.o.Nb >= 0, "%s: negative row count", who);
+  PFR_CHECK_ARG(p.o.a_off >= 0 && p.o.b_off >= 0, "%s: negative offset", who);
+  PFR_CHECK_ARG(p.o.a_off <= INT_MAX - p.o.Na && p.o.b_off <= INT_MAX - p.o.Nb, "%s: offset + rows pass 2^31 - 1", who);
+  PFR_CHECK_ARG(edge_i || parent, "%s: neither an edge list nor a parent array", who);
+  PFR_CHECK_ARG(!edge_i || (edge_j && count && cap >= 0), "%s: an edge list needs edge_j, count and cap >= 0", who);
+  PFR_CHECK_ARG(edge_i || (!edge_j && !edge_s), "%s: edge_j / edge_s without edge_i", who);
+  PFR_CHECK_ARG(!parent || (status && n_nodes >= 0), "%s: a parent array needs status and n_nodes >= 0", who);
+  unsigned grid = 0;
+  if (int rc = rc_ready(who, &p.o, dtype, {edge_i, edge_j, edge_s, count, parent, status}, true, 2, &grid)) return rc;
+  if (grid == 0) return PFR_OK;   // no pair
   p.thr = thr;
   p.edge_i = edge_i; p.edge_j = edge_j; p.edge_s = edge_s; p.cap = edge_i ? (unsigned long long)cap : 0ull; p.count = count;
   p.parent = parent; p.n_nodes = parent ? n_nodes : 0; p.budget = uf_budget(p.n_nodes); p.status = status;
-  p.ntm = (Na + RC_T - 1) / RC_T; p.ntn = (Nb + RC_T - 1) / RC_T;
-  p.nsn = (p.ntn + RC_SUPER - 1) / RC_SUPER;
-  const int nsm = (p.ntm + RC_SUPER - 1) / RC_SUPER;
-  p.nsuper = sym ? (long long)p.nsn * (p.nsn + 1) / 2 : (long long)nsm * p.nsn;
-  const long long ntiles = sym ? (long long)p.ntn * (p.ntn + 1) / 2 : (long long)p.ntm * p.ntn;
-  const long long wgs = 2LL * num_cus();
-  const unsigned grid = (unsigned)(ntiles < wgs ? ntiles : wgs);
-  if (dtype == PFR_F32) hipLaunchKernelGGL(pairs_above_kernel<float>, dim3(grid), dim3(256), CL_LDS, stream, p);
-  else if (dtype == PFR_BF16) hipLaunchKernelGGL(pairs_above_kernel<bf16_t>, dim3(grid), dim3(256), CL_LDS, stream, p);
-  else hipLaunchKernelGGL(pairs_above_kernel<int8_t>, dim3(grid), dim3(256), CL_LDS, stream, p);
+  RC_LAUNCH(dtype, grid, RC_LDS_BASE, stream, p, pairs_above_kernel);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }

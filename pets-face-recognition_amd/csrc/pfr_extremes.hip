@@ -2,11 +2,11 @@
 // (highest other-class score) and the WEAKEST MATE (lowest same-class score), each with its partner, as 64-bit atomic-max keys
 // (pfr_class_extremes), and their decoding (pfr_extremes_decode); contract in include/pfr_hip.h.  Nothing N x N is written.
 //
-// Schedule and tile product are dbscan_pass_kernel's (pfr_dbscan.hip): persistent workgroups (2 per CU) walk the 128 x 128 tiles in
-// super-tiles of 16 x 16, upper triangle only in symmetric mode; rc_tile_gemm / rc_score of pfr_pairtile.h, so a score has the bits of
-// pfr_pair_scores_gather.  Next to the int8 scales the tile stages, per row and per column, the class id (a negative class becomes a
-// value no other side can equal) and the FILTER value: the score of the node's current best_neg key, read once per tile with an
-// agent-scope relaxed load (-inf while the key is 0).  Keys only grow, so a stale value only lets too much through.
+// Schedule and tile product: the tile queue of pfr_tilewalk.h (2 persistent workgroups per CU) and rc_tile_gemm / rc_score of
+// pfr_pairtile.h, so a score has the bits of pfr_pair_scores_gather.  Next to the int8 scales the tile stages, per row and per column,
+// the class id (a negative class becomes a value no other side can equal) and the FILTER value: the score of the node's current
+// best_neg key, read once per tile with an agent-scope relaxed load (-inf while the key is 0).  Keys only grow, so a stale value only
+// lets too much through.
 //
 // Epilogue, per wave (its 64 x 64 part of the tile):
 //   1. Two lane masks (bit (j * 2 + i) * 16 + r <-> acc[i][j][r]): mN, the scores that reach the filter value of their row or of their
@@ -24,26 +24,18 @@
 #include "pfr_scorekey.h"
 
 #define EX_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#define EX_LDS (2 * RC_T * RC_ROWB + 6 * RC_T * 4)   // operands, scales, classes, filter values: 35 840 bytes, under the default limit
+#define EX_LDS (RC_LDS_BASE + 4 * RC_T * 4)   // operands, scales, classes, filter values: 35 840 bytes, under the default limit
 
 typedef unsigned long long ex_u64;
 
 struct ExtremesParams {
-  const char* a;
-  const char* b;
-  const float* a_scale;
-  const float* b_scale;
-  int Na, Nb, sym;
-  int a_off, b_off;
-  int rowb;                 // bytes per operand row
+  PairOperands o;
   const int* cls_a;
   const int* cls_b;
   int cols;                 // the column side has outputs (symmetric mode or both_sides)
   ex_u64* best_pos;
   ex_u64* best_neg;
   ex_u64* worst_pos;        // may be null
-  int ntm, ntn, nsn;
-  long long nsuper;
 };
 
 // the filter value of a node: the score its best_neg key holds now (-inf: no key yet, or a key that holds no number)
@@ -65,58 +57,32 @@ __device__ __forceinline__ ex_u64 ex_half_max(ex_u64 k) {
 template <typename T>
 __global__ __launch_bounds__(256, 2) void class_extremes_kernel(const ExtremesParams p) {   // (2 workgroups per CU: at most 256 registers)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ldsA = smem;                                  // [128][128 B]
-  char* ldsB = smem + RC_T * RC_ROWB;                 // [128][128 B]
-  float* scA = reinterpret_cast<float*>(smem + 2 * RC_T * RC_ROWB);
-  float* scB = scA + RC_T;
-  int* clsA = reinterpret_cast<int*>(scB + RC_T);
+  char *ldsA, *ldsB;
+  float *scA, *scB;
+  int* clsA = reinterpret_cast<int*>(rc_carve(smem, ldsA, ldsB, scA, scB));
   int* clsB = clsA + RC_T;
   float* tnA = reinterpret_cast<float*>(clsB + RC_T);
   float* tnB = tnA + RC_T;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wp = wave >> 1, wq = wave & 1;
-  const int lc = tid & 7, lr = tid >> 3;
-  const int nk = p.rowb / RC_ROWB;
+  const int nk = p.o.rowb / RC_ROWB;
   const bool worst = p.worst_pos != nullptr;
-  const long long total = p.nsuper * (RC_SUPER * RC_SUPER);
+  const long long total = p.o.nsuper * (RC_SUPER * RC_SUPER);
   for (long long t = blockIdx.x; t < total; t += gridDim.x) {
-    const long long su = t / (RC_SUPER * RC_SUPER);
-    const int l = (int)(t % (RC_SUPER * RC_SUPER));
-    int sm, sn;
-    if (p.sym) {
-      // super-tile su of the upper triangle, row-major: row r starts at r * ns - r (r - 1) / 2
-      const double ns2 = 2.0 * p.nsn + 1.0;
-      int r = (int)((ns2 - sqrt(ns2 * ns2 - 8.0 * (double)su)) * 0.5);
-      r = r < 0 ? 0 : (r > p.nsn - 1 ? p.nsn - 1 : r);
-      while (r > 0 && (long long)r * p.nsn - (long long)r * (r - 1) / 2 > su) --r;
-      while ((long long)(r + 1) * p.nsn - (long long)(r + 1) * r / 2 <= su) ++r;
-      sm = r;
-      sn = r + (int)(su - ((long long)r * p.nsn - (long long)r * (r - 1) / 2));
-    } else {
-      sm = (int)(su / p.nsn);
-      sn = (int)(su % p.nsn);
-    }
-    const int tm = sm * RC_SUPER + l / RC_SUPER, tn = sn * RC_SUPER + l % RC_SUPER;
-    if (tm >= p.ntm || tn >= p.ntn || (p.sym && tn < tm)) continue;   // (block-uniform)
+    int tm, tn;
+    if (!tw_tile(t, p.o.ntm, p.o.ntn, p.o.nsn, p.o.sym, tm, tn)) continue;   // (block-uniform)
     const int row0 = tm * RC_T, col0 = tn * RC_T;
-
-    // operand rows of a ragged last tile are clamped to the last valid row (their scores are masked below)
     const char* ga[4];
     const char* gb[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int ra = min(row0 + lr + 32 * u, p.Na - 1), rb = min(col0 + lr + 32 * u, p.Nb - 1);
-      ga[u] = p.a + (size_t)ra * p.rowb + lc * 16;
-      gb[u] = p.b + (size_t)rb * p.rowb + lc * 16;
-    }
+    rc_operand_rows(p.o.a, p.o.b, p.o.rowb, row0, col0, p.o.Na, p.o.Nb, tid, ga, gb);
     // what this thread stages: threads 0..127 the tile's rows, threads 128..255 its columns (clamped like the operands: every index is
     // inside its set); scA | scB, clsA | clsB and tnA | tnB are contiguous, so the slot is [tid] of the first.  Plain values, captured by
     // value: a capture by reference of the parameter block would put it on the stack.
     const bool st_rows = tid < RC_T;
-    const int st_r = st_rows ? min(row0 + tid, p.Na - 1) : min(col0 + tid - RC_T, p.Nb - 1);
+    const int st_r = st_rows ? min(row0 + tid, p.o.Na - 1) : min(col0 + tid - RC_T, p.o.Nb - 1);
     const int* st_cls = st_rows ? p.cls_a : p.cls_b;
-    const float* st_scale = st_rows ? p.a_scale : p.b_scale;
-    const ex_u64* st_key = p.best_neg + ((st_rows ? p.a_off : p.b_off) + st_r);
+    const float* st_scale = st_rows ? p.o.a_scale : p.o.b_scale;
+    const ex_u64* st_key = p.best_neg + ((st_rows ? p.o.a_off : p.o.b_off) + st_r);
     const bool st_filter = st_rows || p.cols != 0;    // (no output on the column side: nothing reaches its filter value)
     const int st_neg = st_rows ? INT_MIN : INT_MIN + 1;   // a distractor row equals no column, a distractor column no row
     f32x16 acc[2][2];
@@ -130,8 +96,8 @@ __global__ __launch_bounds__(256, 2) void class_extremes_kernel(const ExtremesPa
     //  has left this epilogue)
 
     // ---- 1. the lanes' masks: bit (j * 2 + i) * 16 + r <-> acc[i][j][r]
-    const bool diag = p.sym && tm == tn;
-    const bool full = !diag && row0 + RC_T <= p.Na && col0 + RC_T <= p.Nb;   // no element of the tile is masked
+    const bool diag = rc_tile_diag(p.o.sym, tm, tn);
+    const bool full = rc_tile_full(diag, row0, col0, p.o.Na, p.o.Nb);
     const int cl0 = wq * 64 + (lane & 31), cl1 = cl0 + 32;
     const int cb0 = clsB[cl0], cb1 = clsB[cl1];
     const float tc0 = tnB[cl0], tc1 = tnB[cl1];
@@ -165,19 +131,7 @@ __global__ __launch_bounds__(256, 2) void class_extremes_kernel(const ExtremesPa
       }
     }
     if (!full) {   // (block-uniform) a ragged or diagonal tile: drop what is outside the sets, the diagonal and the lower triangle
-      ex_u64 ok = 0ull;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int gj = col0 + (j ? cl1 : cl0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int gi = row0 + wp * 64 + i * 32 + acc_row(r, lane);
-            if (gi < p.Na && gj < p.Nb && (!diag || gi < gj)) ok |= 1ull << ((j * 2 + i) * 16 + r);
-          }
-        }
-      }
+      const ex_u64 ok = rc_valid_mask(false, diag, row0, col0, p.o.Na, p.o.Nb, wp, wq, lane);
       mN &= ok;
       mM &= ok;
     }
@@ -187,7 +141,7 @@ __global__ __launch_bounds__(256, 2) void class_extremes_kernel(const ExtremesPa
     // column l; cX[j] is the lane's running maximum for its column of half j.
     ex_u64 rP = 0ull, rN = 0ull, rW = 0ull;
     ex_u64 cP[2] = {0ull, 0ull}, cN[2] = {0ull, 0ull}, cW[2] = {0ull, 0ull};
-    const int ubase = p.a_off + row0 + wp * 64, vbase = p.b_off + col0 + wq * 64;
+    const int ubase = p.o.a_off + row0 + wp * 64, vbase = p.o.b_off + col0 + wq * 64;
     // (the lane id behind an empty statement the compiler may not move: what step 2 derives from it — 64 lane comparisons, the row
     //  offsets — is otherwise computed once before the tile loop and kept in registers across the GEMM, which spilled)
     int ln = lane;
@@ -291,40 +245,24 @@ extern "C" int pfr_class_extremes(const void* a, const float* a_scale, int Na, i
                                   unsigned long long* best_pos, unsigned long long* best_neg, unsigned long long* worst_pos, int n_nodes,
                                   hipStream_t stream) {
   const char* who = "pfr_class_extremes";
-  int esz = 0;
-  if (int rc = rc_check_operands(who, dtype, D, &esz)) return rc;
-  const bool sym = b == nullptr;
-  if (sym) { b = a; b_scale = a_scale; Nb = Na; b_off = a_off; cls_b = cls_a; }
-  const bool cols = sym || both_sides != 0;
-  PFR_CHECK_ARG(Na >= 0 && Nb >= 0 && n_nodes >= 0, "%s: negative size", who);
-  PFR_CHECK_ARG(a_off >= 0 && b_off >= 0, "%s: negative offset", who);
-  PFR_CHECK_ARG((long long)a_off + Na <= (long long)n_nodes, "%s: a_off + Na passes n_nodes=%d", who, n_nodes);
-  PFR_CHECK_ARG(!cols || (long long)b_off + Nb <= (long long)n_nodes, "%s: b_off + Nb passes n_nodes=%d", who, n_nodes);
-  PFR_CHECK_ARG((long long)b_off + Nb <= (long long)INT_MAX, "%s: b_off + Nb passes 2^31 - 1", who);
-  if (Na == 0 || Nb == 0 || (sym && Na == 1)) return PFR_OK;   // no pair
-  PFR_CHECK_ARG(a && b && cls_a && cls_b && best_pos && best_neg, "%s: null pointer", who);
-  PFR_CHECK_ARG(dtype != PFR_I8 || (a_scale && b_scale), "%s: int8 rows need their scales", who);
-  PFR_CHECK_ARG(pfr_all_dev({a, b, a_scale, b_scale, cls_a, cls_b, best_pos, best_neg, worst_pos}),
-                "%s: every pointer must be device memory", who);
   ExtremesParams p{};
-  p.a = static_cast<const char*>(a); p.b = static_cast<const char*>(b);
-  p.a_scale = a_scale; p.b_scale = b_scale;
-  p.Na = Na; p.Nb = Nb; p.sym = sym ? 1 : 0;
-  p.a_off = a_off; p.b_off = b_off;
-  p.rowb = D * esz;
+  PairOperands& o = p.o;
+  if (int rc = rc_operands(who, a, a_scale, Na, a_off, b, b_scale, Nb, b_off, dtype, D, &o)) return rc;
+  if (o.sym) cls_b = cls_a;
+  const bool cols = o.sym || both_sides != 0;
+  PFR_CHECK_ARG(o.Na >= 0 && o.Nb >= 0 && n_nodes >= 0, "%s: negative size", who);
+  PFR_CHECK_ARG(o.a_off >= 0 && o.b_off >= 0, "%s: negative offset", who);
+  PFR_CHECK_ARG((long long)o.a_off + o.Na <= (long long)n_nodes, "%s: a_off + Na passes n_nodes=%d", who, n_nodes);
+  PFR_CHECK_ARG(!cols || (long long)o.b_off + o.Nb <= (long long)n_nodes, "%s: b_off + Nb passes n_nodes=%d", who, n_nodes);
+  PFR_CHECK_ARG((long long)o.b_off + o.Nb <= (long long)INT_MAX, "%s: b_off + Nb passes 2^31 - 1", who);
+  unsigned grid = 0;
+  if (int rc = rc_ready(who, &o, dtype, {cls_a, cls_b, best_pos, best_neg, worst_pos}, cls_a && cls_b && best_pos && best_neg, 2, &grid))
+    return rc;
+  if (grid == 0) return PFR_OK;   // no pair
   p.cls_a = cls_a; p.cls_b = cls_b;
   p.cols = cols ? 1 : 0;
   p.best_pos = best_pos; p.best_neg = best_neg; p.worst_pos = worst_pos;
-  p.ntm = (Na + RC_T - 1) / RC_T; p.ntn = (Nb + RC_T - 1) / RC_T;
-  p.nsn = (p.ntn + RC_SUPER - 1) / RC_SUPER;
-  const int nsm = (p.ntm + RC_SUPER - 1) / RC_SUPER;
-  p.nsuper = sym ? (long long)p.nsn * (p.nsn + 1) / 2 : (long long)nsm * p.nsn;
-  const long long ntiles = sym ? (long long)p.ntn * (p.ntn + 1) / 2 : (long long)p.ntm * p.ntn;
-  const long long wgs = 2LL * num_cus();
-  const unsigned grid = (unsigned)(ntiles < wgs ? ntiles : wgs);
-  if (dtype == PFR_F32) hipLaunchKernelGGL((class_extremes_kernel<float>), dim3(grid), dim3(256), EX_LDS, stream, p);
-  else if (dtype == PFR_BF16) hipLaunchKernelGGL((class_extremes_kernel<bf16_t>), dim3(grid), dim3(256), EX_LDS, stream, p);
-  else hipLaunchKernelGGL((class_extremes_kernel<int8_t>), dim3(grid), dim3(256), EX_LDS, stream, p);
+  RC_LAUNCH(dtype, grid, EX_LDS, stream, p, class_extremes_kernel);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }

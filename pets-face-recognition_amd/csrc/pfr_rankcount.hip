@@ -3,9 +3,8 @@
 // (how many items precede it), so nothing Na x Nb is written and nothing is sorted: every score is compared, where the MFMA left it,
 // against the few thresholds of its row.
 //
-// Schedule (pfr_pairhist.hip's): persistent workgroups walk a queue of 128 x 128 tiles in super-tiles of 16 x 16 tiles; a tile is
-// 256 threads = 2 x 2 waves of 64 x 64, 128-byte k-steps staged global -> registers -> swizzled LDS, the next k-step's loads in flight
-// under the MFMAs.  Ranks are per row, so every (row, column) tile is visited: there is no triangle to skip.
+// Schedule and tile product: the tile queue of pfr_tilewalk.h and rc_tile_gemm / rc_score of pfr_pairtile.h.  Ranks are per row, so
+// every (row, column) tile is visited, also of a set against itself: there is no triangle to skip.
 //
 // Count epilogue.  Staged per tile: the column ids, the rows' excluded id, threshold count and (int8) scales, the rows' thresholds
 // (value, id) themselves, and tmin = the smallest non-NaN threshold value of each row.  An accumulator register holds 2 rows x 32
@@ -23,17 +22,13 @@
 // Gather: tile (row tile, k) multiplies the 128 rows of a with the 128 GATHERED rows b[col[row][k]] and keeps the diagonal.  Both
 // kernels call rc_tile_gemm — same staging, same k-steps, same MFMA sequence — and rc_score; an accumulator element's value depends on
 // its two operand rows and the k order only, not on where in a tile it sits, so the two entry points give the same bits.
-#include "pfr_igemm.h"
 #include "pfr_pairtile.h"
 
 #define RC_MAX_THR 64       // thresholds per row of one launch
-#define RC_FIXED_LDS (2 * RC_T * RC_ROWB + 6 * RC_T * 4)
+#define RC_FIXED_LDS (RC_LDS_BASE + 4 * RC_T * 4)
 
 struct RankCountParams {
-  const char* a;
-  const char* b;
-  const float* a_scale;
-  const float* b_scale;
+  PairOperands o;           // (sym = 0: the whole rectangle)
   const int* b_id;
   const int* excl;          // or nullptr
   const float* thr_val;
@@ -42,24 +37,18 @@ struct RankCountParams {
   unsigned int* cnt;
   const int* col;           // gather
   float* out;               // gather
-  int Na, Nb, ld;
-  int rowb;                 // bytes per operand row
-  int ntm, ntn, nsn;
-  long long nsuper;
+  int ld;
 };
-
 
 template <typename T>
 __global__ __launch_bounds__(256) void rank_count_kernel(const RankCountParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ldsA = smem;                                  // [128][128 B]
-  char* ldsB = smem + RC_T * RC_ROWB;                 // [128][128 B]
-  int* idB = reinterpret_cast<int*>(smem + 2 * RC_T * RC_ROWB);
+  char *ldsA, *ldsB;
+  float *scA, *scB;
+  int* idB = reinterpret_cast<int*>(rc_carve(smem, ldsA, ldsB, scA, scB));
   int* exA = idB + RC_T;
   int* cntA = exA + RC_T;
-  float* scA = reinterpret_cast<float*>(cntA + RC_T);
-  float* scB = scA + RC_T;
-  float* tmin = scB + RC_T;
+  float* tmin = reinterpret_cast<float*>(cntA + RC_T);
   float* thrV = tmin + RC_T;                          // [128][ld]
   int* thrI = reinterpret_cast<int*>(thrV + RC_T * p.ld);
   unsigned int* c = reinterpret_cast<unsigned int*>(thrI + RC_T * p.ld);
@@ -69,38 +58,27 @@ __global__ __launch_bounds__(256) void rank_count_kernel(const RankCountParams p
   for (int s = tid; s < slots; s += 256) c[s] = 0;
   // (the first tile's barriers order this against the first LDS atomic)
 
-  const int lc = tid & 7, lr = tid >> 3;
-  const int nk = p.rowb / RC_ROWB;
+  const int nk = p.o.rowb / RC_ROWB;
   const bool has_excl = p.excl != nullptr;
-  const long long total = p.nsuper * (RC_SUPER * RC_SUPER);
+  const long long total = p.o.nsuper * (RC_SUPER * RC_SUPER);
   for (long long t = blockIdx.x; t < total; t += gridDim.x) {
-    const long long su = t / (RC_SUPER * RC_SUPER);
-    const int l = (int)(t % (RC_SUPER * RC_SUPER));
-    const int sm = (int)(su / p.nsn), sn = (int)(su % p.nsn);
-    const int tm = sm * RC_SUPER + l / RC_SUPER, tn = sn * RC_SUPER + l % RC_SUPER;
-    if (tm >= p.ntm || tn >= p.ntn) continue;   // (block-uniform)
+    int tm, tn;
+    if (!tw_tile(t, p.o.ntm, p.o.ntn, p.o.nsn, 0, tm, tn)) continue;   // (block-uniform)
     const int row0 = tm * RC_T, col0 = tn * RC_T;
-
-    // operand rows of a ragged last tile are clamped to the last valid row (their scores are masked below)
     const char* ga[4];
     const char* gb[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int ra = min(row0 + lr + 32 * u, p.Na - 1), rb = min(col0 + lr + 32 * u, p.Nb - 1);
-      ga[u] = p.a + (size_t)ra * p.rowb + lc * 16;
-      gb[u] = p.b + (size_t)rb * p.rowb + lc * 16;
-    }
+    rc_operand_rows(p.o.a, p.o.b, p.o.rowb, row0, col0, p.o.Na, p.o.Nb, tid, ga, gb);
     f32x16 acc[2][2];
     rc_tile_gemm<T>(ga, gb, nk, ldsA, ldsB, tid, true, acc, [&] {
       if (tid < RC_T) {
-        const int ra = min(row0 + tid, p.Na - 1), rb = min(col0 + tid, p.Nb - 1);
+        const int ra = min(row0 + tid, p.o.Na - 1), rb = min(col0 + tid, p.o.Nb - 1);
         idB[tid] = p.b_id[rb];
         exA[tid] = has_excl ? p.excl[ra] : 0;
-        cntA[tid] = row0 + tid < p.Na ? min(max(p.thr_cnt[ra], 0), ld) : 0;   // a row past the end has no thresholds
-        if constexpr (sizeof(T) == 1) { scA[tid] = p.a_scale[ra]; scB[tid] = p.b_scale[rb]; }
+        cntA[tid] = row0 + tid < p.o.Na ? min(max(p.thr_cnt[ra], 0), ld) : 0;   // a row past the end has no thresholds
       }
+      rc_stage_scales<T>(p.o.a_scale, p.o.b_scale, row0, col0, p.o.Na, p.o.Nb, tid, scA, scB);
       // the rows' thresholds: [128][ld] of the tile is one contiguous range of thr_val / thr_id, cut at the last valid row
-      const int nvalid = min(RC_T, p.Na - row0) * ld;
+      const int nvalid = min(RC_T, p.o.Na - row0) * ld;
       const size_t g0 = (size_t)row0 * ld;
       for (int s = tid; s < nvalid; s += 256) {
         thrV[s] = p.thr_val[g0 + s];
@@ -117,12 +95,12 @@ __global__ __launch_bounds__(256) void rank_count_kernel(const RankCountParams p
     __syncthreads();
 
     // ---- rank-count epilogue
-    const bool full = row0 + RC_T <= p.Na && col0 + RC_T <= p.Nb;   // no element of the tile is masked by the edges
+    const bool full = rc_tile_full(false, row0, col0, p.o.Na, p.o.Nb);   // no element of the tile is masked by the edges
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int cl = wq * 64 + j * 32 + (lane & 31);
       const int idj = idB[cl];
-      const bool colok = full || col0 + cl < p.Nb;
+      const bool colok = full || col0 + cl < p.o.Nb;
       float sb = 0.f;
       if constexpr (sizeof(T) == 1) sb = scB[cl];
 #pragma unroll
@@ -167,17 +145,15 @@ __global__ __launch_bounds__(256) void rank_count_kernel(const RankCountParams p
 template <typename T>
 __global__ __launch_bounds__(256) void pair_gather_kernel(const RankCountParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ldsA = smem;
-  char* ldsB = smem + RC_T * RC_ROWB;
-  int* colS = reinterpret_cast<int*>(smem + 2 * RC_T * RC_ROWB);
-  float* scA = reinterpret_cast<float*>(colS + RC_T);
-  float* scB = scA + RC_T;
+  char *ldsA, *ldsB;
+  float *scA, *scB;
+  int* colS = reinterpret_cast<int*>(rc_carve(smem, ldsA, ldsB, scA, scB));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wp = wave >> 1, wq = wave & 1;
   const int lc = tid & 7, lr = tid >> 3;
-  const int nk = p.rowb / RC_ROWB;
+  const int nk = p.o.rowb / RC_ROWB;
   const int ld = p.ld;
-  const long long total = (long long)p.ntm * ld;
+  const long long total = (long long)p.o.ntm * ld;
   for (long long t = blockIdx.x; t < total; t += gridDim.x) {
     const int tm = (int)(t / ld), k = (int)(t % ld);
     const int row0 = tm * RC_T;
@@ -188,23 +164,23 @@ __global__ __launch_bounds__(256) void pair_gather_kernel(const RankCountParams 
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int gi = row0 + lr + 32 * u;
-      const int ra = min(gi, p.Na - 1);
-      int cj = gi < p.Na ? p.col[(size_t)ra * ld + k] : -1;
-      if (cj < 0 || cj >= p.Nb) cj = -1;
+      const int ra = min(gi, p.o.Na - 1);
+      int cj = gi < p.o.Na ? p.col[(size_t)ra * ld + k] : -1;
+      if (cj < 0 || cj >= p.o.Nb) cj = -1;
       any |= cj >= 0;
-      ga[u] = p.a + (size_t)ra * p.rowb + lc * 16;
-      gb[u] = p.b + (size_t)max(cj, 0) * p.rowb + lc * 16;
+      ga[u] = p.o.a + (size_t)ra * p.o.rowb + lc * 16;
+      gb[u] = p.o.b + (size_t)max(cj, 0) * p.o.rowb + lc * 16;
     }
     if (!__syncthreads_or(any)) continue;   // (block-uniform) nothing to gather in this tile
     f32x16 acc[2][2];
     rc_tile_gemm<T>(ga, gb, nk, ldsA, ldsB, tid, wp == wq, acc, [&] {
       if (tid < RC_T) {
         const int gi = row0 + tid;
-        const int ra = min(gi, p.Na - 1);
-        int cj = gi < p.Na ? p.col[(size_t)ra * ld + k] : -1;
-        if (cj < 0 || cj >= p.Nb) cj = -1;
+        const int ra = min(gi, p.o.Na - 1);
+        int cj = gi < p.o.Na ? p.col[(size_t)ra * ld + k] : -1;
+        if (cj < 0 || cj >= p.o.Nb) cj = -1;
         colS[tid] = cj;
-        if constexpr (sizeof(T) == 1) { scA[tid] = p.a_scale[ra]; scB[tid] = p.b_scale[max(cj, 0)]; }
+        if constexpr (sizeof(T) == 1) { scA[tid] = p.o.a_scale[ra]; scB[tid] = p.o.b_scale[max(cj, 0)]; }
       }
     });
     // (the staged columns and scales are behind the second barrier of the first k-step)
@@ -230,67 +206,47 @@ static std::atomic<unsigned long long> g_rc_lds_done{0};
 
 extern "C" int pfr_rank_count_max_thr(void) { return RC_MAX_THR; }
 
-
 extern "C" int pfr_rank_count(const void* a, const float* a_scale, int Na, const void* b, const float* b_scale, const int* b_id, int Nb,
                               int dtype, int D, const int* excl, const float* thr_val, const int* thr_id, const int* thr_cnt, int ld,
                               unsigned int* cnt, hipStream_t stream) {
-  int esz = 0;
-  if (int rc = rc_check_operands("pfr_rank_count", dtype, D, &esz)) return rc;
-  PFR_CHECK_ARG(Na >= 0 && (b == nullptr || Nb >= 0), "pfr_rank_count: negative row count");
-  PFR_CHECK_ARG(ld >= 0 && ld <= RC_MAX_THR, "pfr_rank_count: ld=%d thresholds per row, a launch takes at most %d", ld, RC_MAX_THR);
-  if (b == nullptr) { b = a; b_scale = a_scale; Nb = Na; }
-  if (Na == 0 || Nb == 0 || ld == 0) return PFR_OK;   // nothing to add
-  PFR_CHECK_ARG(a && b && b_id && thr_val && thr_id && thr_cnt && cnt, "pfr_rank_count: null pointer");
-  PFR_CHECK_ARG(dtype != PFR_I8 || (a_scale && b_scale), "pfr_rank_count: int8 rows need their scales");
-  PFR_CHECK_ARG(pfr_all_dev({a, b, a_scale, b_scale, b_id, excl, thr_val, thr_id, thr_cnt, cnt}),
-                "pfr_rank_count: every pointer must be device memory");
-
+  const char* who = "pfr_rank_count";
   RankCountParams p = {};
-  p.a = static_cast<const char*>(a); p.b = static_cast<const char*>(b);
-  p.a_scale = a_scale; p.b_scale = b_scale; p.b_id = b_id; p.excl = excl;
-  p.thr_val = thr_val; p.thr_id = thr_id; p.thr_cnt = thr_cnt; p.cnt = cnt;
-  p.Na = Na; p.Nb = Nb; p.ld = ld;
-  p.rowb = D * esz;
-  p.ntm = (Na + RC_T - 1) / RC_T; p.ntn = (Nb + RC_T - 1) / RC_T;
-  p.nsn = (p.ntn + RC_SUPER - 1) / RC_SUPER;
-  p.nsuper = (long long)((p.ntm + RC_SUPER - 1) / RC_SUPER) * p.nsn;
+  if (int rc = rc_operands(who, a, a_scale, Na, 0, b, b_scale, Nb, 0, dtype, D, &p.o)) return rc;
+  p.o.sym = 0;   // a set against itself is still the whole rectangle
+  PFR_CHECK_ARG(p.o.Na >= 0 && p.o.Nb >= 0, "%s: negative row count", who);
+  PFR_CHECK_ARG(ld >= 0 && ld <= RC_MAX_THR, "%s: ld=%d thresholds per row, a launch takes at most %d", who, ld, RC_MAX_THR);
+  if (ld == 0) return PFR_OK;   // nothing to add
   const int lds = RC_FIXED_LDS + RC_T * ld * 12;
-  const long long ntiles = (long long)p.ntm * p.ntn;
-  const long long wgs = (long long)(2 * lds <= 160 * 1024 ? 2 : 1) * num_cus();
-  const unsigned grid = (unsigned)(ntiles < wgs ? ntiles : wgs);
+  unsigned grid = 0;
+  if (int rc = rc_ready(who, &p.o, dtype, {b_id, excl, thr_val, thr_id, thr_cnt, cnt}, b_id && thr_val && thr_id && thr_cnt && cnt,
+                        2 * lds <= 160 * 1024 ? 2 : 1, &grid))
+    return rc;
+  if (grid == 0) return PFR_OK;
+  p.b_id = b_id; p.excl = excl;
+  p.thr_val = thr_val; p.thr_id = thr_id; p.thr_cnt = thr_cnt; p.cnt = cnt;
+  p.ld = ld;
   PFR_MAX_LDS_ONCE(g_rc_lds_done, RC_FIXED_LDS + RC_T * RC_MAX_THR * 12, (const void*)rank_count_kernel<float>,
                    (const void*)rank_count_kernel<bf16_t>, (const void*)rank_count_kernel<int8_t>);
-  if (dtype == PFR_F32) hipLaunchKernelGGL(rank_count_kernel<float>, dim3(grid), dim3(256), lds, stream, p);
-  else if (dtype == PFR_BF16) hipLaunchKernelGGL(rank_count_kernel<bf16_t>, dim3(grid), dim3(256), lds, stream, p);
-  else hipLaunchKernelGGL(rank_count_kernel<int8_t>, dim3(grid), dim3(256), lds, stream, p);
+  RC_LAUNCH(dtype, grid, lds, stream, p, rank_count_kernel);
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }
 
 extern "C" int pfr_pair_scores_gather(const void* a, const float* a_scale, int Na, const void* b, const float* b_scale, int Nb, int dtype,
                                       int D, const int* col, int ld, float* out, hipStream_t stream) {
-  int esz = 0;
-  if (int rc = rc_check_operands("pfr_pair_scores_gather", dtype, D, &esz)) return rc;
-  PFR_CHECK_ARG(Na >= 0 && (b == nullptr || Nb >= 0) && ld >= 0, "pfr_pair_scores_gather: negative size");
-  if (b == nullptr) { b = a; b_scale = a_scale; Nb = Na; }
-  if (Na == 0 || Nb == 0 || ld == 0) return PFR_OK;
-  PFR_CHECK_ARG(a && b && col && out, "pfr_pair_scores_gather: null pointer");
-  PFR_CHECK_ARG(dtype != PFR_I8 || (a_scale && b_scale), "pfr_pair_scores_gather: int8 rows need their scales");
-  PFR_CHECK_ARG(pfr_all_dev({a, b, a_scale, b_scale, col, out}), "pfr_pair_scores_gather: every pointer must be device memory");
-
+  const char* who = "pfr_pair_scores_gather";
   RankCountParams p = {};
-  p.a = static_cast<const char*>(a); p.b = static_cast<const char*>(b);
-  p.a_scale = a_scale; p.b_scale = b_scale; p.col = col; p.out = out;
-  p.Na = Na; p.Nb = Nb; p.ld = ld;
-  p.rowb = D * esz;
-  p.ntm = (Na + RC_T - 1) / RC_T;
-  const int lds = 2 * RC_T * RC_ROWB + 3 * RC_T * 4;   // 34 304 bytes: under the default limit
-  const long long ntiles = (long long)p.ntm * ld;
-  const long long wgs = 2LL * num_cus();
-  const unsigned grid = (unsigned)(ntiles < wgs ? ntiles : wgs);
-  if (dtype == PFR_F32) hipLaunchKernelGGL(pair_gather_kernel<float>, dim3(grid), dim3(256), lds, stream, p);
-  else if (dtype == PFR_BF16) hipLaunchKernelGGL(pair_gather_kernel<bf16_t>, dim3(grid), dim3(256), lds, stream, p);
-  else hipLaunchKernelGGL(pair_gather_kernel<int8_t>, dim3(grid), dim3(256), lds, stream, p);
+  if (int rc = rc_operands(who, a, a_scale, Na, 0, b, b_scale, Nb, 0, dtype, D, &p.o)) return rc;
+  p.o.sym = 0;
+  PFR_CHECK_ARG(p.o.Na >= 0 && p.o.Nb >= 0 && ld >= 0, "%s: negative size", who);
+  if (ld == 0) return PFR_OK;
+  unsigned grid = 0;
+  if (int rc = rc_ready(who, &p.o, dtype, {col, out}, col && out, 2, &grid)) return rc;
+  if (grid == 0) return PFR_OK;
+  p.col = col; p.out = out;
+  p.ld = ld;
+  grid = tw_grid((long long)p.o.ntm * ld, 2, num_cus());   // one tile per (row tile, list position)
+  RC_LAUNCH(dtype, grid, RC_LDS_BASE + RC_T * 4, stream, p, pair_gather_kernel);   // 34 304 bytes: under the default limit
   PFR_CHECK_LAUNCH();
   return PFR_OK;
 }

@@ -193,9 +193,10 @@ def test_gemm_with_fused_gelu_epilogues(dtype):
         pre, dy = pre.bfloat16().float(), dy.bfloat16().float()
     wt = w.t().contiguous()                                # [K][N]: rows = outputs of the gradient GEMM
     out = torch.empty(M, K, dtype=dtype, device=DEV)
-    pd = pre.to(DEV, dtype)
-    lib.pfr_gemm_act(dy.to(DEV, dtype).data_ptr(), wt.to(DEV, dtype).data_ptr(), out.data_ptr(), dtype_id(dtype), M, N, K, 0, 3,
-                     pd.data_ptr(), st)
+    # (named, so that they live until the launch is done: a temporary is freed as soon as its data_ptr() is taken, and the allocator may
+    #  hand its block to the next one — wt's copy then overwrites dy's, depending on what the tests before this one left in the cache)
+    pd, dyd, wtd = pre.to(DEV, dtype), dy.to(DEV, dtype), wt.to(DEV, dtype)
+    lib.pfr_gemm_act(dyd.data_ptr(), wtd.data_ptr(), out.data_ptr(), dtype_id(dtype), M, N, K, 0, 3, pd.data_ptr(), st)
     torch.cuda.synchronize()
     pr = pre.clone().requires_grad_(True)
     F.gelu(pr).backward(dy @ w)
