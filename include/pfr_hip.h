@@ -420,6 +420,35 @@ int pfr_magface_loss(const float* loss_rows, const float* row_stats, const float
 int pfr_l2norm_bwd_radial(const void* x, int in_dtype, const float* inv_norm, const float* dxn, const float* dnorm, void* dx,
                           int out_dtype, int rows, int D, int accumulate, pfr_stream_t stream);
 
+/* ---- pair losses on the Gram matrix of the batch (csrc/pfr_pairloss.hip; not in the reference) ------------------------------
+ * Embeddings e [B][D], labels y [B] (int64 of any sign, only compared for equality).  ê_i = e_i / max(|e_i|, eps) is what
+ * pfr_l2norm_fwd wrote (`xn`, fp32 or bf16 = the compute dtype; int8 is not supported), s_ij = ê_i . ê_j with fp32 accumulation,
+ * P(i) = {j != i : y_j = y_i}, N(i) = {j : y_j != y_i}; the diagonal belongs to neither set and has gradient 0.
+ *   kind 0 'supcon' (Khosla et al. 2020, L_out), p0 = temperature tau (> 0), p1 unused.  Anchor i is valid when P(i) is not empty;
+ *     l_i = log sum_{a != i} exp(s_ia / tau) - (1 / |P(i)|) sum_{p in P(i)} s_ip / tau,
+ *     d l_i / d s_ia = (softmax_a - [a in P(i)] / |P(i)|) / tau for a != i.
+ *   kind 1 'circle' (Sun et al. 2020, per anchor as pytorch-metric-learning does), p0 = m, p1 = gamma.  O_p = 1 + m, O_n = -m, D_p = 1 - m,
+ *     D_n = m, alpha_p = max(0, O_p - s_p), alpha_n = max(0, s_n - O_n), both constants in the gradient.  Anchor i is valid when P(i) and
+ *     N(i) are both non-empty;  z_i = LSE_{n in N(i)} gamma alpha_n (s_n - D_n) + LSE_{p in P(i)} (-gamma alpha_p (s_p - D_p)),
+ *     l_i = softplus(z_i),  d l_i / d s_n = sigma(z_i) softmax_n gamma alpha_n,  d l_i / d s_p = -sigma(z_i) softmax_p gamma alpha_p.
+ *   loss = (1 / A) sum over the valid anchors of l_i, A = their number; A = 0: loss = 0.0 exactly and an all-zero gradient.  Invalid
+ *   anchors give no loss and no gradient; a log-sum-exp over an empty set never becomes a NaN; every log-sum-exp is max-subtracted
+ *   (gamma = 256 works).  With W_ij = (1 / A) d l_i / d s_ij the gradient in normalised space is dê_r = sum_j (W_rj + W_jr) ê_j;
+ *   pfr_l2norm_bwd takes it to e.  No floating-point atomics, the scalar is summed in a fixed order: the same bits every call.
+ * pfr_pair_loss_fwd: one launch.  stats [B][4] fp32 = {lse_all, 1 / |P|, 1, valid} (supcon) or {lse_p, lse_n, sigma(z), valid}
+ *   (circle), all 0 for an invalid anchor; ell [B] = l_i (0 where invalid); out [3] = {loss, 1 / A (0 when A = 0), A}.
+ *   counter: ONE int32 of device memory that is 0 before the first launch and that the kernel leaves at 0 (the ticket of the
+ *   last-workgroup reduction); launches that share it must be ordered on one stream.
+ * pfr_pair_loss_bwd: one launch.  dxn [B][D] fp32 = grad_scale * (*grad_scale_dev or 1) * dê, every element written (plain stores).
+ *   xnT [D][ldt] is ê transposed in the same dtype (pfr_l2norm_fwd's xnT), ldt a multiple of 32 >= B, columns B .. ldt-1 zero.  In bf16
+ *   W_rj + W_jr is rounded to bf16 for the second product (fp32 accumulation); in fp32 nothing is rounded.
+ * D is a multiple of 8, 8 <= D <= 1024; any B >= 1; ragged last tiles are masked. */
+int pfr_pair_loss_fwd(const void* xn, int dtype, const int64_t* label, int B, int D, int kind, float p0, float p1, float* stats,
+                      float* ell, float* out, int* counter, pfr_stream_t stream);
+int pfr_pair_loss_bwd(const void* xn, const void* xnT, int dtype, int ldt, const int64_t* label, int B, int D, int kind, float p0,
+                      float p1, const float* stats, const float* out, float grad_scale, const float* grad_scale_dev, float* dxn,
+                      pfr_stream_t stream);
+
 /* ---- optimiser steps over flat fp32 master buffers (configs/dog_fe/fe_dogs_config.py:123-133; body_dog_fe.py:121-131) */
 int pfr_sgd_step(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
                  float weight_decay, float grad_scale, int first_step, pfr_stream_t stream);

@@ -576,6 +576,68 @@ def l2norm_bwd_radial(x, inv, dxn, dnorm, out_dtype, out=None, accumulate=False)
     return out
 
 
+# ------------------------------------------------------------------------------------------------ pair losses
+PAIR_KINDS = {"supcon": 0, "circle": 1}
+_PAIR_TICKETS = {}
+
+
+def pair_params(kind, tau=0.1, m=0.25, gamma=64.0):
+    """-> (kind id, p0, p1) of pfr_pair_loss_fwd / _bwd: supcon (tau, 0), circle (m, gamma)"""
+    if kind not in PAIR_KINDS:
+        raise ValueError(f"pair loss kind must be one of {sorted(PAIR_KINDS)}, got {kind!r}")
+    return (0, float(tau), 0.0) if kind == "supcon" else (1, float(m), float(gamma))
+
+
+def _pair_ticket(device):
+    """the zeroed int32 the forward's last-workgroup reduction counts on and leaves at 0: one per (device, stream)"""
+    key = (device.index, _stream())
+    t = _PAIR_TICKETS.get(key)
+    if t is None:
+        t = _PAIR_TICKETS[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return t
+
+
+def _pair_chk(xn, label):
+    _chk(xn, "pair_loss: xn"); _chk(label, "pair_loss: label")
+    if xn.dim() != 2 or xn.dtype not in (torch.float32, torch.bfloat16):
+        raise PfrError(f"pair_loss: xn must be a [B, D] fp32 or bf16 tensor (int8 is not supported), got {xn.dtype} {tuple(xn.shape)}")
+    if label.dtype != torch.int64 or label.shape != (xn.shape[0],):
+        raise PfrError(f"pair_loss: label must be int64 [{xn.shape[0]}], got {label.dtype} {tuple(label.shape)}")
+
+
+def pair_loss_fwd(xn, label, kind, **params):
+    """normalised rows xn [B, D] (l2norm_fwd) -> (out fp32 [3] = {loss, 1 / A, A}, stats fp32 [B, 4], ell fp32 [B]); one launch"""
+    _pair_chk(xn, label)
+    B, D = xn.shape
+    k, p0, p1 = pair_params(kind, **params)
+    out = torch.empty(3, dtype=torch.float32, device=xn.device)
+    stats = torch.empty((B, 4), dtype=torch.float32, device=xn.device)
+    ell = torch.empty(B, dtype=torch.float32, device=xn.device)
+    lib.pfr_pair_loss_fwd(_p(xn), dtype_id(xn.dtype), _p(label), B, D, k, p0, p1, _p(stats), _p(ell), _p(out), _p(_pair_ticket(xn.device)),
+                          _stream())
+    return out, stats, ell
+
+
+def pair_loss_bwd(xn, xnT, label, stats, out, kind, grad_scale=1.0, grad_scale_dev=None, dxn=None, **params):
+    """-> dxn fp32 [B, D] = grad_scale * (*grad_scale_dev) * d loss / d xn; xnT [D, ldt] is l2norm_fwd's transposed copy, ldt a multiple
+    of 32 >= B with zero pad columns; one launch"""
+    _pair_chk(xn, label)
+    B, D = xn.shape
+    k, p0, p1 = pair_params(kind, **params)
+    _chk(xnT, "pair_loss_bwd: xnT")
+    if xnT.dtype != xn.dtype or xnT.dim() != 2 or xnT.shape[0] != D:
+        raise PfrError(f"pair_loss_bwd: xnT must be {xn.dtype} [{D}, ldt], got {xnT.dtype} {tuple(xnT.shape)}")
+    _chk_f32(stats, (B, 4), xn.device, "pair_loss_bwd: stats")
+    _chk_f32(out, (3,), xn.device, "pair_loss_bwd: out")
+    if grad_scale_dev is not None:
+        _chk_f32(grad_scale_dev, grad_scale_dev.shape, xn.device, "pair_loss_bwd: grad_scale_dev")
+    if dxn is None:
+        dxn = torch.empty((B, D), dtype=torch.float32, device=xn.device)
+    lib.pfr_pair_loss_bwd(_p(xn), _p(xnT), dtype_id(xn.dtype), xnT.shape[1], _p(label), B, D, k, p0, p1, _p(stats), _p(out), float(grad_scale),
+                          _p(grad_scale_dev), _p(dxn), _stream())
+    return dxn
+
+
 # ------------------------------------------------------------------------------------------------ optimisers
 def sgd_step(p, g, mom, shadow, lr, momentum, weight_decay, grad_scale=1.0, first_step=False):
     lib.pfr_sgd_step(_p(p), _p(g), _p(mom), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),

@@ -11,7 +11,7 @@ from torch.utils.data import DataLoader
 
 import models
 from data_loading import SyntheticRecDataset, RecSubset, PairGenerator
-from losses import SoftmaxBasedMetricLearning
+from losses import SoftmaxBasedMetricLearning, PairMetricLearning
 
 
 
@@ -33,7 +33,13 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
          fused_optimizer=True, compute_dtype=None, limit_train_batches=None, workers=0, n_pairs=200, device_augment=False, noise=0.15,
          noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
          ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd', sub_centers=1, augment_extra=None, margin=None,
-         margin_kwargs=None, sample_rate=None, sparse_grad=None, align=None):
+         margin_kwargs=None, sample_rate=None, sparse_grad=None, align=None, pair_loss=None, pk=None, centre_free=False):
+    # pair_loss: dict(kind='supcon' | 'circle', weight=1.0, **params) adds a pair loss on the batch's Gram matrix (losses/pair.py) to the head's
+    # loss; with centre_free=True there is no class head at all and the pair loss is the criterion (losses.PairMetricLearning)
+    # pk: (P, K) draws the train batches as P identities x K photos (data_loading.PKBatchSampler; train_bs is then P * K) so that every
+    # anchor has positives; None = the reference's shuffled batches
+    if centre_free and pair_loss is None:
+        raise ValueError("centre_free=True trains on the pair loss alone: pass pair_loss=dict(kind=...)")
     # align: dict(jitter=…, estimate=…, masks=…) puts the landmark alignment (data_loading/align.py, the reference's preprocessor/align.py) in front
     # of the head pipeline: ragged raw frames + three landmarks -> DeviceAlign(base_pts, (image_size, image_size, 3)) -> the head augmentation
     # sample_rate / sparse_grad: Partial FC in the margin head (losses/large_margin.py); None = every class is scored, as in the reference
@@ -123,6 +129,10 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
             margin_args['sample_rate'] = sample_rate
         if sparse_grad is not None:
             margin_args['sparse_grad'] = sparse_grad
+        if centre_free:
+            return PairMetricLearning(model=model_, pair_loss=pair_loss, embedding_size=512)
+        if pair_loss is not None:
+            margin_args['pair_loss'] = pair_loss
         return SoftmaxBasedMetricLearning(model=model_, num_class=n_train_ids, embedding_size=512, is_focal=is_focal,
                                           loss_kwargs=loss_kwargs, arc_margin=True, sub_centers=sub_centers, **margin_args)
 
@@ -135,7 +145,7 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         base = _live('init_lr', 10 ** -2 if optimizer_kind == 'sgd' else 10 ** -3)
         d = [{'lr': base / 2, 'params': params1},
              {'lr': base, 'params': params2},
-             {'lr': base, 'params': list(model_.add_margin.parameters()), 'weight_decay': 1 * (10 ** -4)}]
+             {'lr': base, 'params': list(model_.add_margin.parameters()) if hasattr(model_, 'add_margin') else [], 'weight_decay': 1 * (10 ** -4)}]
         d = [g for g in d if len(g['params'])]   # (a backbone without an `fc` layer — Swin's embedding layer is `mlp_head` — has no second group)
         if optimizer_kind == 'adamw':
             if fused_optimizer and device != 'cpu':
@@ -151,11 +161,21 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
         sched = torch.optim.lr_scheduler.MultiStepLR(optim, milestones=[35, 45], gamma=0.1)
         return [optim], [sched]
 
+    pk_epoch = [0]
+
     def train_dataloader():
         # pinned batches for the copy stream (data_loading/prefetch.py); workers stay alive across epochs like the reference's
         # persistent_workers loaders (fe_dogs_config.py:135-143)
         # (batch size and the base rate are read from the config namespace at call time: main.py's find_max_batch_size /
         # find_optimal_init_lr write train_batch_size / init_lr there, reference main.py:79-89)
+        if pk is not None:
+            # P identities x K photos per batch; a fresh, reproducible order per epoch (the loader is built once per epoch)
+            from data_loading import PKBatchSampler
+            sampler = PKBatchSampler([labels[i] for i in train_idx], pk[0], pk[1], seed=seed + _rank())
+            sampler.set_epoch(pk_epoch[0])
+            pk_epoch[0] += 1
+            return DataLoader(train, batch_sampler=sampler, num_workers=workers, pin_memory=device != 'cpu',
+                              persistent_workers=workers > 0, prefetch_factor=4 if workers > 0 else None, **collate)
         return DataLoader(train, _live('train_batch_size', train_bs), shuffle=True, drop_last=True, num_workers=workers, pin_memory=device != 'cpu',
                           persistent_workers=workers > 0, prefetch_factor=4 if workers > 0 else None, **collate)
 

@@ -5,3 +5,4 @@ from .augment import simple_train_augmentation, simple_val_augmentation, body_tr
 from .ragged import ragged_collate, pack_frames, unpack_frames, is_ragged  # noqa: F401
 from .prefetch import DevicePrefetcher  # noqa: F401
 from .align import DeviceAlign, align_torch, pack_masks, solve as align_solve  # noqa: F401
+from .pk_sampler import PKBatchSampler  # noqa: F401

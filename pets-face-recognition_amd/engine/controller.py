@@ -94,6 +94,8 @@ class Controller(nn.Module):
         out = self.model_loss(x, label)
         # a MagFace head's length regulariser (part of the loss already): kept for the Trainer's loss line
         self.last_regulariser = out.get('loss_g') if isinstance(out, dict) else None
+        # the pair term on the batch's Gram matrix (losses/pair.py; part of the loss already, with its weight): likewise
+        self.last_pair_loss = out.get('loss_pair') if isinstance(out, dict) else None
         return out['loss']
 
     def validation_step(self, batch, batch_idx=0, dataset_idx=0):

@@ -300,6 +300,7 @@ class Trainer:
         lr_history = []
         history = []
         reg_history = []     # a MagFace head's regulariser at the steps of `history`
+        pair_history = []    # the pair term (losses/pair.py) at the steps of `history`
         gn_history = []
         first_epoch = 0
         ckpt_path = ckpt_path or self.resume_from_checkpoint
@@ -353,8 +354,12 @@ class Trainer:
                     reg = getattr(controller, 'last_regulariser', None)
                     if reg is not None:
                         reg_history.append(float(reg.detach()))
+                    pair = getattr(controller, 'last_pair_loss', None)
+                    if pair is not None:
+                        pair_history.append(float(pair.detach()))
                     if self.rank == 0:
-                        print(f'epoch {epoch} step {self.global_step} loss {lv:.5f}' + (f' loss_g {reg_history[-1]:.5f}' if reg is not None else ''))
+                        print(f'epoch {epoch} step {self.global_step} loss {lv:.5f}' + (f' loss_g {reg_history[-1]:.5f}' if reg is not None else '')
+                              + (f' loss_pair {pair_history[-1]:.5f}' if pair is not None else ''))
             if t_mark is not None and n_mark:
                 if device.type == 'cuda':
                     torch.cuda.synchronize(device)
@@ -379,6 +384,7 @@ class Trainer:
         self.lr_history = lr_history
         self.loss_history = history
         self.regulariser_history = reg_history
+        self.pair_loss_history = pair_history
         self.grad_norm_history = gn_history
         return controller
 

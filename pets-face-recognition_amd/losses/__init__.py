@@ -2,12 +2,14 @@
 signature, attribute names (`module`, `add_margin`, `focal_loss`) and forward contract
 (/root/reference/losses/__init__.py:8-46): `forward(img, label=None)` returns the embedding tensor when `label is
 None`, else `{'loss', 'emb', 'logits'}` (a Partial FC training forward adds `'classes'` and `'local_label'`, a MagFace head
-`'loss_g'`: the length regulariser that `'loss'` already contains); a list/tuple of images is embedded one by one and concatenated."""
+`'loss_g'`: the length regulariser that `'loss'` already contains; `pair_loss=` adds `'loss_pair'`, the pair term that `'loss'`
+already contains with its weight); a list/tuple of images is embedded one by one and concatenated."""
 import torch
 import torch.nn as nn
 
 from .large_margin import ArcMarginProduct, AddMarginProduct, AdaFaceProduct, CurricularFaceProduct, MagFaceProduct, _MarginHead
 from .losses import FocalLoss, describe_criterion
+from .pair import PairLoss, build_pair_loss
 
 
 _ADAPTIVE_HEADS = {"adaface": AdaFaceProduct, "curricular": CurricularFaceProduct, "magface": MagFaceProduct}
@@ -15,8 +17,12 @@ _ADAPTIVE_HEADS = {"adaface": AdaFaceProduct, "curricular": CurricularFaceProduc
 
 class SoftmaxBasedMetricLearning(nn.Module):
     def __init__(self, model, num_class, embedding_size=512, s=64.0, m=0.5, is_focal=False, loss_kwargs=None,
-                 arc_margin=False, easy_margin=False, sub_centers=1, margin=None, margin_kwargs=None, sample_rate=1.0, sparse_grad=False):
+                 arc_margin=False, easy_margin=False, sub_centers=1, margin=None, margin_kwargs=None, sample_rate=1.0, sparse_grad=False, pair_loss=None):
         super().__init__()
+        # pair_loss (not in the reference): dict(kind='supcon' | 'circle', weight=1.0, **params) adds weight * PairLoss(kind, **params) on
+        # the pairs of the batch (losses/pair.py) to the head's loss; the pair term alone is returned detached as 'loss_pair'.  None: no
+        # such module exists and every returned value is what it was.
+        self.pair_loss, self.pair_weight = (None, 0.0) if pair_loss is None else build_pair_loss(pair_loss)
         # sample_rate / sparse_grad (not in the reference): Partial FC, see losses/large_margin.py; a sampled training forward returns
         # `logits` [B, S] over the classes `classes` with the targets `local_label`.  Passed on only when set, so that the defaults build
         # exactly the head they did.
@@ -94,6 +100,15 @@ class SoftmaxBasedMetricLearning(nn.Module):
             tensor = self.module(img)
         if label is None:
             return tensor
+        out = self._head_forward(tensor, label)
+        if self.pair_loss is not None:
+            head = self.add_margin
+            lp = self.pair_loss(tensor, label, compute_dtype=getattr(head, "compute_dtype", None) or getattr(self.module, "compute_dtype", None))
+            out['loss'] = out['loss'] + self.pair_weight * lp
+            out['loss_pair'] = lp.detach()
+        return out
+
+    def _head_forward(self, tensor, label):
         crit = self._fusable(tensor)
         head = self.add_margin
         partial = head._partial(label) if isinstance(head, _MarginHead) else None
@@ -125,6 +140,32 @@ class SoftmaxBasedMetricLearning(nn.Module):
             loss, logits = MarginCEFunction.apply(tensor, head.weight, label, head.hip_mode(), head.s, head.m, crit,
                                                   resolve_dtype(dt), self.return_logits, crit.alpha, head.sub_centers, head._count())
         return {'loss': loss, 'emb': tensor, 'logits': logits if self.return_logits else None}
+
+
+class PairMetricLearning(nn.Module):
+    """Backbone + a pair loss on the batch (losses/pair.py) and NO class head: the centre-free training mode, for identities that are
+    too many, too few-shot or open-ended for a centre each.  Same forward contract as SoftmaxBasedMetricLearning: `forward(img,
+    label=None)` returns the embedding when `label is None`, else `{'loss', 'emb', 'logits': None, 'loss_pair'}` with
+    loss = weight * pair loss and 'loss_pair' the unweighted term, detached.  pair_loss: dict(kind=..., weight=1.0, **params).
+    Batches want several items per identity (data_loading.PKBatchSampler): an anchor without a positive contributes nothing."""
+
+    def __init__(self, model, pair_loss, embedding_size=512):
+        super().__init__()
+        self.module = model
+        self.embedding_size = embedding_size
+        self.pair_loss, self.pair_weight = build_pair_loss(pair_loss)
+
+    def forward(self, img, label=None, **__):
+        if isinstance(img, (list, tuple)):
+            tensor = torch.cat([self.module(i) for i in img], dim=0)
+        else:
+            tensor = self.module(img)
+        if label is None:
+            return tensor
+        if tensor.dim() != 2 or tensor.shape[1] != self.embedding_size:
+            raise ValueError(f"PairMetricLearning: the backbone returned {tuple(tensor.shape)}, expected [B, {self.embedding_size}]")
+        lp = self.pair_loss(tensor, label, compute_dtype=getattr(self.module, "compute_dtype", None))
+        return {'loss': self.pair_weight * lp, 'emb': tensor, 'logits': None, 'loss_pair': lp.detach()}
 
 
 class DummyWrapper(nn.Module):
