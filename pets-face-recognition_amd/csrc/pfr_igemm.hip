@@ -793,6 +793,7 @@ __global__ __launch_bounds__(NW * 64, (KCH_ == 4 && NW == 4 && NST_ == 2 && size
 #pragma unroll
         for (int e = 0; e < KPO; ++e) { float cdf, pdf; gelu_cdf_pdf(f[e], cdf, pdf); f[e] *= cdf; }
         v = Chunk<TO>::pack(f);
+        if (p.stats_part) Chunk<TO>::unpack(v, f);   // pfr_gemm_act_colstats: statistics of the activation as stored too
       } else if (p.act == 3) {  // GELU backward fused into the data-gradient GEMM: dz = dh ∘ gelu'(z)
         float z[KPO];
         Chunk<TO>::unpack(pre ? pb[i] : ld16(reinterpret_cast<const char*>(p.y2) + ((size_t)m * p.ldy + co) * sizeof(TO)), z);
@@ -803,6 +804,7 @@ __global__ __launch_bounds__(NW * 64, (KCH_ == 4 && NW == 4 && NST_ == 2 && size
           f[e] *= cdf + z[e] * pdf;
         }
         v = Chunk<TO>::pack(f);
+        if (p.stats_part) Chunk<TO>::unpack(v, f);   // pfr_gemm_act_colstats: statistics of the activation as stored too
       }
     }
     if (p.stats_part) {

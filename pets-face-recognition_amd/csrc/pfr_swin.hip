@@ -602,8 +602,14 @@ extern "C" int pfr_layernorm_bwd_dxsum(const void* dy, const void* x, const floa
     if (ln_geom(C, kp, &g)) {
       const size_t shb = (size_t)13 * C * sizeof(float);
       const bool small = (double)rows * C * (dtype == PFR_BF16 ? 2 : 4) < 1.5e9;   // 32-bit buffer offsets
+      // 13 * C * 4 bytes pass the 64 KiB a launch gets by default at C > 1260 (bf16 rows of 3 or 4 chunks per lane, up to 106 496 bytes at
+      // C = 2048; fp32 ends at C = 1024 = 53 248 bytes): those launches were refused.  Only the instances that need it raise their limit.
 #define PFR_LNB(TT, K, GG)                                                                                              \
   if (g.cpl == K && g.G == GG) {                                                                                        \
+    if (shb > (size_t)64 * 1024) {                                                                                      \
+      static std::atomic<unsigned long long> attr{0};                                                                   \
+      PFR_MAX_LDS_ONCE(attr, 13 * 2048 * (int)sizeof(float), (const void*)layernorm_bwd3_kernel<TT, K, GG>, (const void*)layernorm_bwd2_kernel<TT, K, GG>); \
+    }                                                                                                                   \
     if (small) hipLaunchKernelGGL((layernorm_bwd3_kernel<TT, K, GG>), dim3(nb), dim3(256), shb, st, (const TT*)dy, (const TT*)x, mean, rstd, gamma, (const TT*)dres, (TT*)dx, part, dxsum_part, rows, C, g.cpr); \
     else hipLaunchKernelGGL((layernorm_bwd2_kernel<TT, K, GG>), dim3(nb), dim3(256), shb, st, (const TT*)dy, (const TT*)x, mean, rstd, gamma, (const TT*)dres, (TT*)dx, part, dxsum_part, rows, C, g.cpr); \
   }
