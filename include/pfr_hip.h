@@ -50,6 +50,8 @@ int pfr_device_arch(char* buf, int buflen);
  *   "slin" (1) streaming Linear kernel for K = 96 j (Swin): 0 off, 1 for M >= 65536 rows, 2 whenever eligible;
  *   "attn_mfma" (1) window attention on MFMA;  "match_order" (1) L2-blocked tile order of the persistent filter GEMM of the gallery match.
  *   "ln_rb" (4) LayerNorm forward, rows in flight per lane group for C <= 512: 4, 6 or 8.
+ *   "pair_mem_order" (1) grid order of pfr_pair_mem_loss_fwd / _bwd: 0 anchor block fast, 1 the anchor blocks of one partner range on one XCD
+ *   (the same bits either way; profiles/pair_memory.txt).
  * Results do not depend on the knobs (same accumulation order per kernel family; alternatives are pinned bit-for-bit or to the oracle by the
  * tests); statistics-partial granularity follows pfr_conv2d_mtile.  pfr_get_tuning reads a knob back. */
 int pfr_set_tuning(const char* key, int value);
@@ -448,6 +450,45 @@ int pfr_pair_loss_fwd(const void* xn, int dtype, const int64_t* label, int B, in
 int pfr_pair_loss_bwd(const void* xn, const void* xnT, int dtype, int ldt, const int64_t* label, int B, int D, int kind, float p0,
                       float p1, const float* stats, const float* out, float grad_scale, const float* grad_scale_dev, float* dxn,
                       pfr_stream_t stream);
+
+/* ---- pair losses with a cross-batch memory (csrc/pfr_pairmem.hip; Wang et al., CVPR 2020; not in the reference) --------------
+ * The batch is that of pfr_pair_loss_fwd: ê [B][D] as pfr_l2norm_fwd wrote it, labels y [B].  The memory is a ring of past rows:
+ * mem [M][D] in the same compute dtype (fp32 or bf16), labels mem_label [M] int64 and `count` in [0, M] live slots, which are always the
+ * slots 0 .. count-1 (the ring fills from 0 and wraps only once it is full).  The partners of anchor i are the batch items j != i and
+ * the live slots k:  P(i) = {j != i : y_j = y_i} u {k < count : ym_k = y_i},  N(i) = {j : y_j != y_i} u {k < count : ym_k != y_i}.
+ * Logits, l_i, validity (supcon: P not empty; circle: P and N not empty) and loss = (1 / A) sum over the valid BATCH anchors of l_i
+ * (A = 0: 0.0 exactly) are the formulas of pfr_pair_loss_fwd over these larger sets.  Memory items are never anchors and nothing flows
+ * to them: with W_ij = (1 / A) d l_i / d s_ij,  dê_r = sum_{j in batch} (W_rj + W_jr) ê_j + sum_{k < count} W_rk m_k.
+ *   Rows of mem at slots >= count may hold anything (NaN included): the kernels zero them in the operand, not only in the weight.  The
+ *   transposed copy memT [D][ldm] has ldm a multiple of 32 >= M and the CALLER keeps it zero at columns >= count (pfr_pair_mem_push
+ *   writes only live columns into a buffer that starts as zeros), as xnT's pad columns are.
+ *   No floating-point atomics; every reduction has a fixed order: the same bits every call, whichever workgroup finishes last.
+ *   D, dtype and the parameters are limited as for pfr_pair_loss_fwd; M is a multiple of 32 with 32 <= M < 2^24.  B <= M is what the
+ *   push needs (a batch has to fit into the ring) and what the Python module enforces; the two loss kernels take any B.
+ * The partner list is cut into tiles of 32: ceil(B / 32) batch tiles, then ceil(count / 32) memory tiles (a tile never holds both), and
+ * the tile list into S contiguous splits, split s = tiles [s nt / S, (s + 1) nt / S); the grid is (anchor blocks of 32) x S.
+ * pfr_pair_mem_splits: host arithmetic only.  -> the S that splits = 0 stands for: min(256 / anchor blocks, ceil(tiles / 4),
+ *   64 MiB / (B D 4 bytes)), at least 1.  It sizes the workspace `ws` of both calls: forward S B 8 floats (partial states), backward
+ *   S B D floats (slabs; the 64 MiB cap is the stated budget).  An explicit S needs a workspace of that S.
+ * pfr_pair_mem_loss_fwd: one launch.  splits = 0: auto; an explicit S in [1, 4096] is honoured, also beyond the number of tiles (an
+ *   empty split contributes the empty state (-inf, 0)).  S = 1: ws may be NULL.  Each workgroup writes the partial state of its 32
+ *   anchors; the last workgroup (the integer ticket `counter`, as in pfr_pair_loss_fwd) merges the splits in split order and sums the
+ *   scalar in a fixed order.  stats, ell, out: as pfr_pair_loss_fwd.
+ * pfr_pair_mem_loss_bwd: dxn [B][D] fp32 = grad_scale * (*grad_scale_dev or 1) * dê, every element written with plain stores.  One
+ *   launch when S = 1 (ws may be NULL); S > 1: every split writes a slab and a second small kernel on the same stream sums the slabs in
+ *   split order.  In bf16 G (W_rj + W_jr, or W_rk) is rounded to bf16 for the second product (fp32 accumulation).
+ * pfr_pair_mem_push: copies the B rows of xn to the slots (head + r) mod M: rows into mem, columns into memT, labels into mem_label.
+ *   The caller advances head = (head + B) mod M and count = min(count + B, M).  It must run after the backward that reads the old ring. */
+int pfr_pair_mem_splits(int B, int count, int D);
+int pfr_pair_mem_loss_fwd(const void* xn, int dtype, const int64_t* label, int B, int D, const void* mem, const int64_t* mem_label, int M,
+                          int count, int kind, float p0, float p1, int splits, float* ws, float* stats, float* ell, float* out,
+                          int* counter, pfr_stream_t stream);
+int pfr_pair_mem_loss_bwd(const void* xn, const void* xnT, int dtype, int ldt, const int64_t* label, int B, int D, const void* mem,
+                          const void* memT, int ldm, const int64_t* mem_label, int M, int count, int kind, float p0, float p1,
+                          const float* stats, const float* out, float grad_scale, const float* grad_scale_dev, int splits, float* ws,
+                          float* dxn, pfr_stream_t stream);
+int pfr_pair_mem_push(const void* xn, const int64_t* label, int B, int D, int dtype, void* mem, void* memT, int ldm, int64_t* mem_label,
+                      int M, int head, pfr_stream_t stream);
 
 /* ---- optimiser steps over flat fp32 master buffers (configs/dog_fe/fe_dogs_config.py:123-133; body_dog_fe.py:121-131) */
 int pfr_sgd_step(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,

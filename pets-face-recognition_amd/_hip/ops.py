@@ -638,6 +638,78 @@ def pair_loss_bwd(xn, xnT, label, stats, out, kind, grad_scale=1.0, grad_scale_d
     return dxn
 
 
+# ------------------------------------------------------------------------------------------------ pair losses with a cross-batch memory
+def _pair_mem_chk(xn, label, mem, mem_label, count, who):
+    _pair_chk(xn, label)
+    _chk(mem, f"{who}: mem"); _chk(mem_label, f"{who}: mem_label")
+    D = xn.shape[1]
+    if mem.dim() != 2 or mem.dtype != xn.dtype or mem.shape[1] != D or mem.device != xn.device:
+        raise PfrError(f"{who}: mem must be {xn.dtype} [M, {D}] on {xn.device}, got {mem.dtype} {tuple(mem.shape)} on {mem.device}")
+    M = mem.shape[0]
+    if mem_label.dtype != torch.int64 or mem_label.shape != (M,):
+        raise PfrError(f"{who}: mem_label must be int64 [{M}], got {mem_label.dtype} {tuple(mem_label.shape)}")
+    if not 0 <= int(count) <= M:
+        raise PfrError(f"{who}: need 0 <= count <= M = {M}, got {count}")
+    return M
+
+
+def pair_mem_splits(B, count, D):
+    """the number of partner-range splits that splits=0 stands for (host arithmetic); the workspaces hold [S, B, 8] (forward) and [S, B, D]
+    (backward) floats"""
+    return lib.pfr_pair_mem_splits(int(B), int(count), int(D))
+
+
+def pair_mem_loss_fwd(xn, label, mem, mem_label, count, kind, splits=0, **params):
+    """pair_loss_fwd with the live slots 0 .. count-1 of the ring (mem [M, D], mem_label [M]) as further partners -> (out, stats, ell);
+    one launch.  splits: 0 = pair_mem_splits, or an explicit number of partner-range splits (the tests)"""
+    M = _pair_mem_chk(xn, label, mem, mem_label, count, "pair_mem_loss_fwd")
+    B, D = xn.shape
+    k, p0, p1 = pair_params(kind, **params)
+    S = int(splits) or pair_mem_splits(B, count, D)
+    ws = torch.empty((S, B, 8), dtype=torch.float32, device=xn.device) if S > 1 else None
+    out = torch.empty(3, dtype=torch.float32, device=xn.device)
+    stats = torch.empty((B, 4), dtype=torch.float32, device=xn.device)
+    ell = torch.empty(B, dtype=torch.float32, device=xn.device)
+    lib.pfr_pair_mem_loss_fwd(_p(xn), dtype_id(xn.dtype), _p(label), B, D, _p(mem), _p(mem_label), M, int(count), k, p0, p1, S, _p(ws),
+                              _p(stats), _p(ell), _p(out), _p(_pair_ticket(xn.device)), _stream())
+    return out, stats, ell
+
+
+def pair_mem_loss_bwd(xn, xnT, label, mem, memT, mem_label, count, stats, out, kind, grad_scale=1.0, grad_scale_dev=None, dxn=None, splits=0,
+                      **params):
+    """-> dxn fp32 [B, D]; memT [D, ldm] is the ring transposed, ldm a multiple of 32 >= M and zero at columns >= count (pair_mem_push keeps
+    it so).  Nothing flows to the ring.  One launch, plus the slab sum when there is more than one split"""
+    M = _pair_mem_chk(xn, label, mem, mem_label, count, "pair_mem_loss_bwd")
+    B, D = xn.shape
+    k, p0, p1 = pair_params(kind, **params)
+    _chk(xnT, "pair_mem_loss_bwd: xnT"); _chk(memT, "pair_mem_loss_bwd: memT")
+    if xnT.dtype != xn.dtype or xnT.dim() != 2 or xnT.shape[0] != D:
+        raise PfrError(f"pair_mem_loss_bwd: xnT must be {xn.dtype} [{D}, ldt], got {xnT.dtype} {tuple(xnT.shape)}")
+    if memT.dtype != xn.dtype or memT.dim() != 2 or memT.shape[0] != D:
+        raise PfrError(f"pair_mem_loss_bwd: memT must be {xn.dtype} [{D}, ldm], got {memT.dtype} {tuple(memT.shape)}")
+    _chk_f32(stats, (B, 4), xn.device, "pair_mem_loss_bwd: stats")
+    _chk_f32(out, (3,), xn.device, "pair_mem_loss_bwd: out")
+    if grad_scale_dev is not None:
+        _chk_f32(grad_scale_dev, grad_scale_dev.shape, xn.device, "pair_mem_loss_bwd: grad_scale_dev")
+    if dxn is None:
+        dxn = torch.empty((B, D), dtype=torch.float32, device=xn.device)
+    S = int(splits) or pair_mem_splits(B, count, D)
+    ws = torch.empty((S, B, D), dtype=torch.float32, device=xn.device) if S > 1 else None
+    lib.pfr_pair_mem_loss_bwd(_p(xn), _p(xnT), dtype_id(xn.dtype), xnT.shape[1], _p(label), B, D, _p(mem), _p(memT), memT.shape[1], _p(mem_label),
+                              M, int(count), k, p0, p1, _p(stats), _p(out), float(grad_scale), _p(grad_scale_dev), S, _p(ws), _p(dxn), _stream())
+    return dxn
+
+
+def pair_mem_push(xn, label, mem, memT, mem_label, head):
+    """rows, transposed columns and labels of the batch into the ring slots (head + r) mod M; the caller keeps head and count"""
+    M = _pair_mem_chk(xn, label, mem, mem_label, 0, "pair_mem_push")
+    B, D = xn.shape
+    _chk(memT, "pair_mem_push: memT")
+    if memT.dtype != xn.dtype or memT.dim() != 2 or memT.shape[0] != D:
+        raise PfrError(f"pair_mem_push: memT must be {xn.dtype} [{D}, ldm], got {memT.dtype} {tuple(memT.shape)}")
+    lib.pfr_pair_mem_push(_p(xn), _p(label), B, D, dtype_id(xn.dtype), _p(mem), _p(memT), memT.shape[1], _p(mem_label), M, int(head), _stream())
+
+
 # ------------------------------------------------------------------------------------------------ optimisers
 def sgd_step(p, g, mom, shadow, lr, momentum, weight_decay, grad_scale=1.0, first_step=False):
     lib.pfr_sgd_step(_p(p), _p(g), _p(mom), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),

@@ -59,6 +59,7 @@ enum PfrKnob {
   KNOB_SSTEM,         // halo-staged stem convolution (pfr_sstem.hip: 4x4 over 16 channels -> 64): 1 on (default), 0 = the tile kernel
   KNOB_IGEMM_DMA,     // -DPFR_IGEMM_SPREAD experiment builds only: DMA issue schedule of the 128-byte-k-step tile kernels (IgemmParams::dma_sched)
   KNOB_IGEMM_KROT,    // tile kernel: workgroup t starts its k-loop at k-step (t * krot) % nk (0 = every workgroup at k-step 0; summation order changes)
+  KNOB_PAIR_MEM_ORDER, // pair losses with a cross-batch memory: 0 = anchor block fast in the grid, 1 = the anchor blocks of one partner range on one XCD
   KNOB_COUNT
 };
 extern int g_pfr_knob[KNOB_COUNT];

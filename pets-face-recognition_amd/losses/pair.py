@@ -8,11 +8,16 @@ P(i) = {j != i : y_j = y_i}, N(i) = {j : y_j != y_i}; the diagonal is in neither
            l_i = softplus(LSE_n gamma alpha_n (s_n - m) + LSE_p (-gamma alpha_p (s_p - 1 + m)))
   loss = mean of l_i over the valid anchors; no valid anchor: 0.0 exactly, with a zero gradient.
 Rank-local: the pairs are those of this process's batch, there is no all-gather.  No mining (batch-hard triplet, multi-similarity), no
-cross-batch memory, no label that means "ignore".
+momentum encoder, no label that means "ignore".
+
+Cross-batch memory (Wang et al., CVPR 2020; `PairLoss(kind, memory=M)`): a ring of the normalised embeddings and labels of the last M items.
+Every anchor of the batch also pairs with the live slots k < count of the ring: P(i) and N(i) grow by {k : ym_k = y_i} and {k : ym_k != y_i},
+the formulas and the validity rules stay, the loss is still the mean over the valid anchors of the BATCH, and nothing flows to the ring
+(include/pfr_hip.h at pfr_pair_mem_loss_fwd).  The ring is rank-local and not checkpointed: a resumed run starts with an empty one.
 
 CUDA tensors run `PairLossFunction`: pfr_l2norm_fwd, ONE forward launch (csrc/pfr_pairloss.hip), then one backward launch and
-pfr_l2norm_bwd.  CPU tensors run `pair_loss_torch`, the same contract in torch ops in the tensor's own dtype; in float64 it is the oracle
-of the device tests."""
+pfr_l2norm_bwd; with a memory `PairMemLossFunction` (csrc/pfr_pairmem.hip).  CPU tensors run `pair_loss_torch` / `pair_loss_mem_torch`,
+the same contract in torch ops in the tensor's own dtype; in float64 they are the oracles of the device tests."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -79,6 +84,50 @@ def pair_loss_torch(emb, label, kind, normalize=True, eps=1e-12, alpha_emb=None,
     return (loss, rows, valid) if return_rows else loss
 
 
+def pair_loss_mem_from_scores(s_batch, s_mem, label, mem_label, kind, s_alpha=None, **params):
+    """pair_loss_from_scores with a memory: s_batch [B, B] are the scores inside the batch, s_mem [B, n] those against the n live slots of
+    the ring (labels mem_label [n]; n may be 0).  -> (loss, l [B] with 0 at invalid anchors (detached), valid [B] bool, logits [B, B + n]).
+    Only the batch items are anchors.  s_alpha: (batch, memory) scores Circle's alpha are taken from (None: the scores, detached)."""
+    p = _params(kind, params)
+    B, n = s_batch.shape[0], s_mem.shape[1]
+    s = torch.cat([s_batch, s_mem], 1)
+    same = label[:, None] == torch.cat([label, mem_label.to(label.device)])[None, :]
+    eye = torch.cat([torch.eye(B, dtype=torch.bool, device=s.device), torch.zeros(B, n, dtype=torch.bool, device=s.device)], 1)
+    pos, neg = same & ~eye, ~same
+    valid = pos.any(1) if kind == "supcon" else pos.any(1) & neg.any(1)
+    idx = valid.nonzero().squeeze(1)
+    if kind == "supcon":
+        x = s / p["tau"]
+    else:
+        m, gamma = p["m"], p["gamma"]
+        sa = (s if s_alpha is None else torch.cat(list(s_alpha), 1)).detach()
+        x = torch.where(same, -gamma * (1 + m - sa).clamp_min(0) * (s - (1 - m)), gamma * (sa + m).clamp_min(0) * (s - m))
+    rows = s.new_zeros(B)
+    if idx.numel() == 0:
+        return (s * 0).sum(), rows, valid, x        # 0.0 exactly, and a zero gradient
+    ninf = float("-inf")
+    if kind == "supcon":
+        xv = x[idx]
+        ell = torch.logsumexp(xv.masked_fill(eye[idx], ninf), 1) - (xv * pos[idx]).sum(1) / pos[idx].sum(1)
+    else:
+        z = torch.logsumexp(x[idx].masked_fill(~neg[idx], ninf), 1) + torch.logsumexp(x[idx].masked_fill(~pos[idx], ninf), 1)
+        ell = -F.logsigmoid(-z)
+    return ell.sum() / idx.numel(), rows.index_put((idx,), ell.detach()), valid, x
+
+
+def pair_loss_mem_torch(emb, label, mem, mem_label, kind, normalize=True, eps=1e-12, alpha_emb=None, return_rows=False, **params):
+    """pair_loss_torch with a memory: mem [n, D] are the live rows of the ring as they were stored (already normalised; used detached),
+    mem_label [n] their labels.  normalize / alpha_emb / return_rows as in pair_loss_torch."""
+    xn = F.normalize(emb, dim=1, eps=eps) if normalize else emb
+    mem = mem.detach().to(xn.dtype)
+    sa = None
+    if alpha_emb is not None:
+        an = F.normalize(alpha_emb, dim=1, eps=eps) if normalize else alpha_emb
+        sa = (an @ an.t(), an @ mem.t())
+    loss, rows, valid, _ = pair_loss_mem_from_scores(xn @ xn.t(), xn @ mem.t(), label, mem_label, kind, s_alpha=sa, **params)
+    return (loss, rows, valid) if return_rows else loss
+
+
 class PairLossFunction(torch.autograd.Function):
     """(emb [B, D] CUDA, label int64 [B]) -> scalar loss.  Forward: pfr_l2norm_fwd (ê and êᵀ in the compute dtype) + pfr_pair_loss_fwd;
     backward: pfr_pair_loss_bwd (dê, fp32) + pfr_l2norm_bwd.  There is no fallback: a shape the kernels refuse is an error."""
@@ -103,32 +152,162 @@ class PairLossFunction(torch.autograd.Function):
         return demb.to(emb.dtype), None, None, None, None
 
 
+class PairMemLossFunction(torch.autograd.Function):
+    """PairLossFunction against the ring of `owner` (a PairLoss with memory > 0): pfr_l2norm_fwd + pfr_pair_mem_loss_fwd; backward:
+    pfr_pair_mem_loss_bwd + pfr_l2norm_bwd.  `count` live slots are used (0 during the warm-up).  keep: leave ê and the labels with the
+    owner as the rows its next training call pushes.  The backward refuses a ring that has been pushed to since this forward."""
+
+    @staticmethod
+    def forward(ctx, emb, label, owner, count, T, keep):
+        from .._hip import ops
+        emb = emb.contiguous()
+        label = label.contiguous()
+        B, D = emb.shape
+        xn, xnT, inv = ops.l2norm_fwd(emb, T, want_t=True, ldt=(B + 31) // 32 * 32)
+        owner._ensure(xn)
+        out, stats, _ = ops.pair_mem_loss_fwd(xn, label, owner.mem, owner.mem_label, count, owner.kind, **owner.params)
+        ctx.save_for_backward(emb, label, xn, xnT, inv, stats, out)
+        ctx.owner, ctx.count, ctx.generation = owner, count, owner.generation
+        if keep:
+            owner._pending = (xn, label)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        from .._hip import ops
+        emb, label, xn, xnT, inv, stats, out = ctx.saved_tensors
+        o = ctx.owner
+        o._guard(ctx.generation)
+        dxn = ops.pair_mem_loss_bwd(xn, xnT, label, o.mem, o.memT, o.mem_label, ctx.count, stats, out, o.kind,
+                                    grad_scale_dev=g.float().contiguous(), **o.params)
+        demb = ops.l2norm_bwd(emb, inv, dxn, torch.float32)
+        return demb.to(emb.dtype), None, None, None, None, None
+
+
+class _RingGuard(torch.autograd.Function):
+    """identity whose backward refuses a ring that has been pushed to since the forward (the CPU path of the generation guard)"""
+
+    @staticmethod
+    def forward(ctx, loss, owner):
+        ctx.owner, ctx.generation = owner, owner.generation
+        return loss.view_as(loss)
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.owner._guard(ctx.generation)
+        return g, None
+
+
 class PairLoss(nn.Module):
     """PairLoss(kind, **params): forward(emb [B, D], label [B]) -> scalar.  kind 'supcon' (tau=0.1) or 'circle' (m=0.25, gamma=64).
     compute_dtype (fp32 / bf16; None = the default of the HIP engines, as the margin heads resolve it) is the dtype of ê on the device:
-    in bf16 the scores come from the bf16-rounded ê with fp32 accumulation.  int8 is not supported."""
+    in bf16 the scores come from the bf16-rounded ê with fp32 accumulation.  int8 is not supported.
 
-    def __init__(self, kind="supcon", compute_dtype=None, **params):
+    memory=M > 0 (a multiple of 32, B <= M): cross-batch memory.  The ring is `mem` [M, D], `memT` [D, M] and `mem_label` [M], non-persistent
+    buffers allocated at the first batch in that batch's compute dtype (CPU: the tensor's dtype); a later change of dtype or D is an error.
+    `head` and `count` are host integers.  The ring is not part of the state dict: a resumed run starts with an empty ring.
+      * the push is deferred: a training-mode forward first pushes the PREVIOUS call's ê and labels, then computes the loss against the
+        ring, so the backward reads the ring its forward saw.  Every push raises `generation`; a backward that finds a newer generation
+        than its forward's (two forwards before the first backward) raises.
+      * no push in eval mode or under torch.no_grad(): those calls read the ring and leave it alone.
+      * memory_warmup=W: the first W training calls fill the ring but their loss uses no slot (early features drift).
+      * rank-local: every process has its own ring."""
+
+    def __init__(self, kind="supcon", memory=0, memory_warmup=0, compute_dtype=None, **params):
         super().__init__()
         self.kind = kind
         self.params = _params(kind, params)
         self.compute_dtype = compute_dtype
+        self.memory, self.memory_warmup = int(memory), int(memory_warmup)
+        if self.memory < 0 or self.memory % 32 or self.memory >= 1 << 24:
+            raise ValueError(f"pair loss: memory must be 0 or a multiple of 32 below 2^24, got {memory}")
+        if self.memory_warmup < 0 or (self.memory_warmup and not self.memory):
+            raise ValueError(f"pair loss: memory_warmup needs memory > 0 and a count of calls >= 0, got {memory_warmup}")
+        if self.memory:
+            for name in ("mem", "memT", "mem_label"):
+                self.register_buffer(name, None, persistent=False)
+            self.reset_memory()
 
     def extra_repr(self):
-        return f"kind={self.kind!r}, " + ", ".join(f"{k}={v:g}" for k, v in self.params.items())
+        mem = f", memory={self.memory}, memory_warmup={self.memory_warmup}" if self.memory else ""
+        return f"kind={self.kind!r}, " + ", ".join(f"{k}={v:g}" for k, v in self.params.items()) + mem
+
+    # ---------------------------------------------------------------------------------------------- the ring
+    def reset_memory(self):
+        """empty the ring (the buffers are allocated again at the next batch)"""
+        self.mem = self.memT = self.mem_label = None
+        self.head = self.count = self.generation = self.train_calls = 0
+        self._pending = None
+
+    def _ensure(self, xn):
+        if xn.shape[0] > self.memory:
+            raise ValueError(f"pair loss: the batch ({xn.shape[0]}) is larger than the memory ({self.memory})")
+        if self.mem is None:
+            M, D = self.memory, xn.shape[1]
+            self.mem = torch.zeros(M, D, dtype=xn.dtype, device=xn.device)
+            self.memT = torch.zeros(D, M, dtype=xn.dtype, device=xn.device)      # zero beyond `count`: the kernels rely on it
+            self.mem_label = torch.zeros(M, dtype=torch.int64, device=xn.device)
+        elif self.mem.dtype != xn.dtype or self.mem.shape[1] != xn.shape[1] or self.mem.device != xn.device:
+            raise ValueError(f"pair loss: the memory holds {self.mem.dtype} rows of length {self.mem.shape[1]} on {self.mem.device}, "
+                             f"got {xn.dtype} rows of length {xn.shape[1]} on {xn.device} (reset_memory() starts a new ring)")
+
+    def push(self, xn, label):
+        """the normalised rows xn [B, D] and their labels into the slots (head + r) mod M, now"""
+        xn, label = xn.detach().contiguous(), label.detach().contiguous()
+        self._ensure(xn)
+        B, M = xn.shape[0], self.memory
+        if xn.is_cuda:
+            from .._hip import ops
+            ops.pair_mem_push(xn, label, self.mem, self.memT, self.mem_label, self.head)
+        else:
+            idx = (self.head + torch.arange(B)) % M
+            self.mem[idx] = xn
+            self.memT[:, idx] = xn.t()
+            self.mem_label[idx] = label
+        self.head = (self.head + B) % M
+        self.count = min(self.count + B, M)
+        self.generation += 1
+
+    def _guard(self, generation):
+        if generation != self.generation:
+            raise RuntimeError(f"pair loss memory: the ring was pushed to (generation {self.generation}) after the forward of this backward "
+                               f"(generation {generation}): run each backward before the next training-mode forward")
+
+    def _forward_memory(self, emb, label, T):
+        keep = self.training and torch.is_grad_enabled()
+        if keep:
+            if self._pending is not None:
+                self.push(*self._pending)
+                self._pending = None
+            self.train_calls += 1
+        # the warm-up covers the training calls 1 .. memory_warmup; a call that does not train reads the ring once those are done
+        warm = self.train_calls <= self.memory_warmup if keep else self.train_calls < self.memory_warmup
+        count = 0 if warm else self.count
+        if emb.is_cuda:
+            return PairMemLossFunction.apply(emb, label, self, count, T, keep)
+        xn = F.normalize(emb, dim=1, eps=1e-12)
+        self._ensure(xn)
+        loss = pair_loss_mem_torch(xn, label, self.mem[:count], self.mem_label[:count], self.kind, normalize=False, **self.params)
+        if keep:
+            self._pending = (xn.detach(), label)
+        return _RingGuard.apply(loss, self)
 
     def forward(self, emb, label, compute_dtype=None):
         if not emb.is_cuda:
+            if self.memory:
+                return self._forward_memory(emb, label, emb.dtype)
             return pair_loss_torch(emb, label, self.kind, **self.params)
         from ._head_hip import resolve_dtype
         T = resolve_dtype(self.compute_dtype or compute_dtype)
         if T not in (torch.float32, torch.bfloat16):
             raise ValueError(f"pair loss: the compute dtype is fp32 or bf16, got {T}")
+        if self.memory:
+            return self._forward_memory(emb, label, T)
         return PairLossFunction.apply(emb, label, self.kind, T, self.params)
 
 
 def build_pair_loss(spec):
-    """dict(kind=..., weight=1.0, compute_dtype=None, **params) -> (PairLoss, weight)"""
+    """dict(kind=..., weight=1.0, memory=0, memory_warmup=0, compute_dtype=None, **params) -> (PairLoss, weight)"""
     spec = dict(spec)
     if "kind" not in spec:
         raise ValueError("pair_loss needs a 'kind' ('supcon' or 'circle')")
