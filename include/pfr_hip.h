@@ -490,6 +490,53 @@ int pfr_pair_mem_loss_bwd(const void* xn, const void* xnT, int dtype, int ldt, c
 int pfr_pair_mem_push(const void* xn, const int64_t* label, int B, int D, int dtype, void* mem, void* memT, int ldm, int64_t* mem_label,
                       int M, int head, pfr_stream_t stream);
 
+/* ---- mined pair losses: batch-hard triplet and Multi-Similarity (csrc/pfr_pairmine.hip; not in the reference) ----------------
+ * Operands, sets and reduction are those of pfr_pair_mem_loss_fwd: ê [B][D] as pfr_l2norm_fwd wrote it (fp32 or bf16), int64 labels, an
+ * optional ring mem [M][D] / mem_label [M] with `count` live slots (mem = NULL, M = 0, count = 0: the batch alone), P(i) and N(i) over
+ * the batch (diagonal excluded) plus the live slots.  Memory items are never anchors and nothing flows to them.  Anchor i is valid when
+ * P(i) and N(i) are both non-empty; loss = (1 / A) sum over the valid batch anchors of l_i; A = 0: 0.0 exactly and an all-zero gradient.
+ * Partners are numbered j for batch item j and B + k for slot k.
+ *   Extremes (both kinds): s_p*(i) = min over P(i) of s_ij, s_n*(i) = max over N(i) of s_ij, each with its partner number.  Ties go to
+ *   the smallest partner number, -0.0 = +0.0, and a pair whose score is a NaN counts for nothing: it is in neither set (the conventions
+ *   of pfr_class_extremes).  These values, and every decision taken from them (which pair is the hardest, which pairs the miner keeps,
+ *   whether the hinge is active), are CONSTANTS in the gradient.
+ *   kind 2 'batch_hard' (Hermans et al. 2017, on cosine scores): params = {m >= 0, gamma >= 0, -, -}.  z_i = s_n* - s_p* + m;
+ *     gamma = 0: l_i = max(0, z_i), active iff z_i > 0;  gamma > 0: l_i = softplus(gamma z_i) / gamma.  f_i = d l_i / d z_i;
+ *     W_{i,n*} = +f_i / A, W_{i,p*} = -f_i / A, every other W is 0.
+ *   kind 3 'multi_similarity' (Wang et al., CVPR 2019): params = {alpha > 0, beta > 0, base lambda, epsilon >= 0} (pytorch-metric-learning:
+ *     2, 50, 0.5, 0.1).  Mining: negative n is kept iff s_in + epsilon > s_p*(i), positive p iff s_ip - epsilon < s_n*(i) (each sum rounded
+ *     once in fp32).  L_p = log(1 + sum_{kept p} exp(-alpha (s_ip - lambda))), L_n = log(1 + sum_{kept n} exp(beta (s_in - lambda))),
+ *     l_i = L_p / alpha + L_n / beta;  d l_i / d s_ip = -exp(-alpha (s_ip - lambda) - L_p),  d l_i / d s_in = exp(beta (s_in - lambda) - L_n)
+ *     for kept pairs, 0 for the others.  Each log(1 + sum) is an online max-subtracted log-sum-exp that contains the element 0 (finite at
+ *     beta = 256); an empty kept set gives 0.  Deviation from the published code, stated: the mean runs over the VALID anchors (this
+ *     project's rule), not over the batch size with anchors skipped.
+ *   The partner list, its tiles, the splits and pfr_pair_mined_splits (= pfr_pair_mem_splits; workspaces: forward S B 8 floats, backward
+ *   S B D floats, multi_similarity only) are those of pfr_pair_mem_loss_fwd.  No floating-point atomics; the same bits every call,
+ *   whichever workgroup finishes last.  Extremes, partner numbers, validity, kept counts and all of batch_hard do not depend on S at all
+ *   (the merge of extremes is a total order); L_p, L_n and the multi_similarity gradient may differ between different S in the last
+ *   bits, as the existing memory kernels' log-sum-exps and slab sums do.  D, dtype, M as there; any B >= 1; ragged tiles are masked; rows
+ *   of mem at slots >= count may hold NaN and are zeroed in the operand.
+ * pfr_pair_mined_fwd: params points to FOUR host floats, read during the call.  Launch 1, the extremes: the transposed 32 x 32 score tile,
+ *   per-lane (min positive, its number, max negative, its number, |P|, |N|), merged over the waves in wave order and over the splits by the
+ *   last workgroup (the integer ticket `counter`, contract of pfr_pair_loss_fwd); batch_hard ends here.  multi_similarity: launch 2 on the
+ *   same stream scores the tiles again and accumulates the two gated log-sum-exps.
+ *   stats [B][8] fp32: {s_p*, s_n*, number of p* (int32 bits), number of n* (int32 bits), L_p | z_i, L_n | f_i, kept pairs | 0, valid};
+ *   an invalid anchor has the whole row 0 and both numbers -1.  ell [B] = l_i (0 where invalid); out [3] = {loss, 1 / A, A}.
+ * pfr_pair_mined_bwd: dxn [B][D] fp32 = grad_scale * (*grad_scale_dev or 1) * dê, every element written with plain stores.
+ *   multi_similarity: the dense form of pfr_pair_mem_loss_bwd (G_ij = W_ij + W_ji from the two stats rows and the recomputed score, the
+ *   same pmn_keep decision as the forward; slabs and the ordered slab sum when S > 1; bf16 rounds G once).  batch_hard: sparse, no GEMM,
+ *   xnT / memT / ws unused (may be NULL): row r = (f_r / A) (p[n*_r] - p[p*_r]) plus, for the anchors i in index order, +(f_i / A) ê_i
+ *   where n*_i = r and -(f_i / A) ê_i where p*_i = r, fp32 throughout.  A stats row whose partner numbers are outside [0, B + count)
+ *   contributes nothing: no address is formed from it. */
+int pfr_pair_mined_splits(int B, int count, int D);
+int pfr_pair_mined_fwd(const void* xn, int dtype, const int64_t* label, int B, int D, const void* mem, const int64_t* mem_label, int M,
+                       int count, int kind, const float* params, int splits, float* ws, float* stats, float* ell, float* out,
+                       int* counter, pfr_stream_t stream);
+int pfr_pair_mined_bwd(const void* xn, const void* xnT, int dtype, int ldt, const int64_t* label, int B, int D, const void* mem,
+                       const void* memT, int ldm, const int64_t* mem_label, int M, int count, int kind, const float* params,
+                       const float* stats, const float* out, float grad_scale, const float* grad_scale_dev, int splits, float* ws,
+                       float* dxn, pfr_stream_t stream);
+
 /* ---- optimiser steps over flat fp32 master buffers (configs/dog_fe/fe_dogs_config.py:123-133; body_dog_fe.py:121-131) */
 int pfr_sgd_step(float* p, const float* g, float* mom, void* shadow, int shadow_dtype, size_t n, float lr, float momentum,
                  float weight_decay, float grad_scale, int first_step, pfr_stream_t stream);

@@ -710,6 +710,80 @@ def pair_mem_push(xn, label, mem, memT, mem_label, head):
     lib.pfr_pair_mem_push(_p(xn), _p(label), B, D, dtype_id(xn.dtype), _p(mem), _p(memT), memT.shape[1], _p(mem_label), M, int(head), _stream())
 
 
+# ------------------------------------------------------------------------------------------------ mined pair losses
+PAIR_MINED_KINDS = {"batch_hard": 2, "multi_similarity": 3}
+
+
+def pair_mined_params(kind, m=0.3, gamma=0.0, alpha=2.0, beta=50.0, base=0.5, epsilon=0.1):
+    """-> (kind id, the four host floats of pfr_pair_mined_fwd / _bwd): batch_hard (m, gamma, 0, 0), multi_similarity (alpha, beta,
+    base, epsilon)"""
+    import ctypes
+    if kind not in PAIR_MINED_KINDS:
+        raise ValueError(f"mined pair loss kind must be one of {sorted(PAIR_MINED_KINDS)}, got {kind!r}")
+    vals = (m, gamma, 0.0, 0.0) if kind == "batch_hard" else (alpha, beta, base, epsilon)
+    return PAIR_MINED_KINDS[kind], (ctypes.c_float * 4)(*[float(v) for v in vals])
+
+
+def _pair_mined_chk(xn, label, mem, mem_label, count, who):
+    """-> M; mem = None: the batch alone (M = count = 0)"""
+    if mem is None:
+        _pair_chk(xn, label)
+        if mem_label is not None or int(count) != 0:
+            raise PfrError(f"{who}: without a ring (mem=None) there is no mem_label and count is 0, got count={count}")
+        return 0
+    return _pair_mem_chk(xn, label, mem, mem_label, count, who)
+
+
+def pair_mined_splits(B, count, D):
+    """the number of partner-range splits that splits=0 stands for (host arithmetic; = pair_mem_splits); the workspaces hold [S, B, 8]
+    (forward) and [S, B, D] (backward of multi_similarity) floats"""
+    return lib.pfr_pair_mined_splits(int(B), int(count), int(D))
+
+
+def pair_mined_fwd(xn, label, kind, mem=None, mem_label=None, count=0, splits=0, **params):
+    """normalised rows xn [B, D] (l2norm_fwd), optionally the live slots 0 .. count-1 of a ring -> (out fp32 [3] = {loss, 1 / A, A},
+    stats fp32 [B, 8], ell fp32 [B]).  stats[:, 2:4] hold partner numbers as int32 bits (stats.view(torch.int32)).  batch_hard: one
+    launch; multi_similarity: two (the extremes, then the gated log-sum-exps)"""
+    M = _pair_mined_chk(xn, label, mem, mem_label, count, "pair_mined_fwd")
+    B, D = xn.shape
+    k, p4 = pair_mined_params(kind, **params)
+    S = int(splits) or pair_mined_splits(B, count, D)
+    ws = torch.empty((S, B, 8), dtype=torch.float32, device=xn.device) if S > 1 else None
+    out = torch.empty(3, dtype=torch.float32, device=xn.device)
+    stats = torch.empty((B, 8), dtype=torch.float32, device=xn.device)
+    ell = torch.empty(B, dtype=torch.float32, device=xn.device)
+    lib.pfr_pair_mined_fwd(_p(xn), dtype_id(xn.dtype), _p(label), B, D, _p(mem), _p(mem_label), M, int(count), k, p4, S, _p(ws), _p(stats),
+                           _p(ell), _p(out), _p(_pair_ticket(xn.device)), _stream())
+    return out, stats, ell
+
+
+def pair_mined_bwd(xn, xnT, label, stats, out, kind, mem=None, memT=None, mem_label=None, count=0, grad_scale=1.0, grad_scale_dev=None,
+                   dxn=None, splits=0, **params):
+    """-> dxn fp32 [B, D] = grad_scale * (*grad_scale_dev) * d loss / d xn.  multi_similarity: xnT [D, ldt] and memT [D, ldm] as for
+    pair_mem_loss_bwd, one launch plus the slab sum when there is more than one split.  batch_hard: one sparse launch (xnT and memT are
+    not read).  Nothing flows to the ring"""
+    M = _pair_mined_chk(xn, label, mem, mem_label, count, "pair_mined_bwd")
+    B, D = xn.shape
+    k, p4 = pair_mined_params(kind, **params)
+    _chk(xnT, "pair_mined_bwd: xnT"); _chk(memT, "pair_mined_bwd: memT")
+    if xnT is None or xnT.dtype != xn.dtype or xnT.dim() != 2 or xnT.shape[0] != D:
+        raise PfrError(f"pair_mined_bwd: xnT must be {xn.dtype} [{D}, ldt]")
+    if (mem is None) != (memT is None) or (memT is not None and (memT.dtype != xn.dtype or memT.dim() != 2 or memT.shape[0] != D)):
+        raise PfrError(f"pair_mined_bwd: memT must be {xn.dtype} [{D}, ldm] when there is a ring, and None without one")
+    _chk_f32(stats, (B, 8), xn.device, "pair_mined_bwd: stats")
+    _chk_f32(out, (3,), xn.device, "pair_mined_bwd: out")
+    if grad_scale_dev is not None:
+        _chk_f32(grad_scale_dev, grad_scale_dev.shape, xn.device, "pair_mined_bwd: grad_scale_dev")
+    if dxn is None:
+        dxn = torch.empty((B, D), dtype=torch.float32, device=xn.device)
+    S = int(splits) or pair_mined_splits(B, count, D)
+    ws = torch.empty((S, B, D), dtype=torch.float32, device=xn.device) if S > 1 and kind == "multi_similarity" else None
+    lib.pfr_pair_mined_bwd(_p(xn), _p(xnT), dtype_id(xn.dtype), xnT.shape[1], _p(label), B, D, _p(mem), _p(memT),
+                           0 if memT is None else memT.shape[1], _p(mem_label), M, int(count), k, p4, _p(stats), _p(out), float(grad_scale),
+                           _p(grad_scale_dev), S, _p(ws), _p(dxn), _stream())
+    return dxn
+
+
 # ------------------------------------------------------------------------------------------------ optimisers
 def sgd_step(p, g, mom, shadow, lr, momentum, weight_decay, grad_scale=1.0, first_step=False):
     lib.pfr_sgd_step(_p(p), _p(g), _p(mom), _p(shadow), PFR_F32 if shadow is None else dtype_id(shadow.dtype), p.numel(),

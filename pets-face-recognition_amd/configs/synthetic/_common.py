@@ -34,7 +34,7 @@ def make(ns, arch, n_train_ids, n_val_ids, photos, image_size, train_bs, test_bs
          noise_bank=0, limit_val_batches=None, gradient_clip_val=None, gradient_clip_algorithm=None, loss_kwargs=None, is_focal=True,
          ragged=False, pipeline='head', trainer_extra=None, model_kwargs=None, optimizer_kind='sgd', sub_centers=1, augment_extra=None, margin=None,
          margin_kwargs=None, sample_rate=None, sparse_grad=None, align=None, pair_loss=None, pk=None, centre_free=False):
-    # pair_loss: dict(kind='supcon' | 'circle', weight=1.0, **params) adds a pair loss on the batch's Gram matrix (losses/pair.py) to the head's
+    # pair_loss: dict(kind='supcon' | 'circle' | 'batch_hard' | 'multi_similarity', weight=1.0, **params) adds a pair loss on the batch's Gram matrix (losses/pair.py) to the head's
     # loss; with centre_free=True there is no class head at all and the pair loss is the criterion (losses.PairMetricLearning)
     # pk: (P, K) draws the train batches as P identities x K photos (data_loading.PKBatchSampler; train_bs is then P * K) so that every
     # anchor has positives; None = the reference's shuffled batches

@@ -6,7 +6,7 @@ set -e
 cd "$(dirname "$0")"
 ARCH=gfx950
 FLAGS="--offload-arch=$ARCH -O3 -std=c++17 -fPIC -Wno-unused-result -ffp-contract=fast ${PFR_EXTRA_FLAGS}"
-SOURCES="pfr_api pfr_comm pfr_plan pfr_igemm pfr_igemm_p pfr_sconv pfr_sconv3 pfr_sstem pfr_slin pfr_wgrad pfr_wgrad9 pfr_elementwise pfr_bnfree pfr_head pfr_pairloss pfr_pairmem pfr_pfc pfr_match pfr_pairhist pfr_rankcount pfr_cardmax pfr_cluster pfr_dbscan pfr_extremes pfr_rerank pfr_swin pfr_mha pfr_dwconv pfr_dwconv3 pfr_dwconvk pfr_se pfr_augment pfr_augment_fit pfr_augment_color pfr_prelu pfr_align"
+SOURCES="pfr_api pfr_comm pfr_plan pfr_igemm pfr_igemm_p pfr_sconv pfr_sconv3 pfr_sstem pfr_slin pfr_wgrad pfr_wgrad9 pfr_elementwise pfr_bnfree pfr_head pfr_pairloss pfr_pairmem pfr_pairmine pfr_pfc pfr_match pfr_pairhist pfr_rankcount pfr_cardmax pfr_cluster pfr_dbscan pfr_extremes pfr_rerank pfr_swin pfr_mha pfr_dwconv pfr_dwconv3 pfr_dwconvk pfr_se pfr_augment pfr_augment_fit pfr_augment_color pfr_prelu pfr_align"
 HEADERS="pfr_common.h pfr_augment_dev.h pfr_mma.h pfr_igemm.h pfr_pairtile.h pfr_pairloss.h pfr_tilewalk.h pfr_scorekey.h pfr_unionfind.h ../../include/pfr_hip.h pfr_thunks_gen.inc"
 # Variant builds for A/B runs: PFR_BUILD_TAG=nt PFR_EXTRA_FLAGS="-DPFR_LN_NT=1" build.sh  ->  build_nt/*.o, libpfr_hip_nt.so (load it with
 # PFR_LIB_PATH=...).  The flags of the last build are recorded next to the objects: a change of flags rebuilds everything (the objects'

@@ -19,7 +19,7 @@ class SoftmaxBasedMetricLearning(nn.Module):
     def __init__(self, model, num_class, embedding_size=512, s=64.0, m=0.5, is_focal=False, loss_kwargs=None,
                  arc_margin=False, easy_margin=False, sub_centers=1, margin=None, margin_kwargs=None, sample_rate=1.0, sparse_grad=False, pair_loss=None):
         super().__init__()
-        # pair_loss (not in the reference): dict(kind='supcon' | 'circle', weight=1.0, **params) adds weight * PairLoss(kind, **params) on
+        # pair_loss (not in the reference): dict(kind='supcon' | 'circle' | 'batch_hard' | 'multi_similarity', weight=1.0, **params) adds weight * PairLoss(kind, **params) on
         # the pairs of the batch (losses/pair.py) to the head's loss; the pair term alone is returned detached as 'loss_pair'.  None: no
         # such module exists and every returned value is what it was.
         self.pair_loss, self.pair_weight = (None, 0.0) if pair_loss is None else build_pair_loss(pair_loss)

@@ -7,8 +7,18 @@ P(i) = {j != i : y_j = y_i}, N(i) = {j : y_j != y_i}; the diagonal is in neither
   circle   valid when P(i) and N(i) are not empty;  alpha_p = max(0, 1 + m - s_p), alpha_n = max(0, s_n + m), constants in the gradient;
            l_i = softplus(LSE_n gamma alpha_n (s_n - m) + LSE_p (-gamma alpha_p (s_p - 1 + m)))
   loss = mean of l_i over the valid anchors; no valid anchor: 0.0 exactly, with a zero gradient.
-Rank-local: the pairs are those of this process's batch, there is no all-gather.  No mining (batch-hard triplet, multi-similarity), no
-momentum encoder, no label that means "ignore".
+Rank-local: the pairs are those of this process's batch, there is no all-gather.  No momentum encoder, no label that means "ignore".
+
+Mined kinds (include/pfr_hip.h at pfr_pair_mined_fwd; DESIGN.md "Mined pair losses"; csrc/pfr_pairmine.hip), valid when P(i) and N(i) are
+not empty.  s_p*(i) = min over P(i), s_n*(i) = max over N(i), ties to the smallest partner number (batch item j is number j, ring slot k
+is B + k), -0.0 = +0.0, a NaN score is in neither set:
+  batch_hard        (Hermans et al. 2017, on cosine scores) z_i = s_n* - s_p* + m;  gamma = 0: l_i = max(0, z_i);  gamma > 0:
+                    l_i = softplus(gamma z_i) / gamma
+  multi_similarity  (Wang et al., CVPR 2019) negative n kept iff s_in + epsilon > s_p*, positive p kept iff s_ip - epsilon < s_n*;
+                    l_i = log(1 + sum_{kept p} exp(-alpha (s_ip - base))) / alpha + log(1 + sum_{kept n} exp(beta (s_in - base))) / beta
+Two stated deviations: the mean runs over the VALID anchors (the published Multi-Similarity code divides by the batch size), and the
+selection (which pair is the hardest, which pairs are kept, whether the hinge is active) is a CONSTANT in the gradient.  Not covered: an
+all-gather of partners across ranks, Euclidean-distance triplets, semi-hard mining.
 
 Cross-batch memory (Wang et al., CVPR 2020; `PairLoss(kind, memory=M)`): a ring of the normalised embeddings and labels of the last M items.
 Every anchor of the batch also pairs with the live slots k < count of the ring: P(i) and N(i) grow by {k : ym_k = y_i} and {k : ym_k != y_i},
@@ -16,14 +26,16 @@ the formulas and the validity rules stay, the loss is still the mean over the va
 (include/pfr_hip.h at pfr_pair_mem_loss_fwd).  The ring is rank-local and not checkpointed: a resumed run starts with an empty one.
 
 CUDA tensors run `PairLossFunction`: pfr_l2norm_fwd, ONE forward launch (csrc/pfr_pairloss.hip), then one backward launch and
-pfr_l2norm_bwd; with a memory `PairMemLossFunction` (csrc/pfr_pairmem.hip).  CPU tensors run `pair_loss_torch` / `pair_loss_mem_torch`,
+pfr_l2norm_bwd; with a memory `PairMemLossFunction` (csrc/pfr_pairmem.hip); the mined kinds `PairMinedLossFunction`, with or without a memory.  CPU tensors run `pair_loss_torch` / `pair_loss_mem_torch`,
 the same contract in torch ops in the tensor's own dtype; in float64 they are the oracles of the device tests."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-KINDS = ("supcon", "circle")
-_DEFAULTS = {"supcon": dict(tau=0.1), "circle": dict(m=0.25, gamma=64.0)}
+KINDS = ("supcon", "circle", "batch_hard", "multi_similarity")
+MINED_KINDS = ("batch_hard", "multi_similarity")
+_DEFAULTS = {"supcon": dict(tau=0.1), "circle": dict(m=0.25, gamma=64.0), "batch_hard": dict(m=0.3, gamma=0.0),
+             "multi_similarity": dict(alpha=2.0, beta=50.0, base=0.5, epsilon=0.1)}
 
 
 def _params(kind, params):
@@ -37,7 +49,70 @@ def _params(kind, params):
         raise ValueError(f"supcon needs a temperature > 0, got {p['tau']}")
     if kind == "circle" and not (p["gamma"] > 0 and 0 <= p["m"] < 1):
         raise ValueError(f"circle needs gamma > 0 and 0 <= m < 1, got m={p['m']} gamma={p['gamma']}")
+    if kind == "batch_hard" and not (p["m"] >= 0 and p["gamma"] >= 0):
+        raise ValueError(f"batch_hard needs a margin >= 0 and gamma >= 0, got m={p['m']} gamma={p['gamma']}")
+    if kind == "multi_similarity" and not (p["alpha"] > 0 and p["beta"] > 0 and p["epsilon"] >= 0 and p["base"] == p["base"]):
+        raise ValueError(f"multi_similarity needs alpha > 0, beta > 0 and epsilon >= 0, got {p}")
     return p
+
+
+def pair_mined_parts(s, pos, neg, kind, **params):
+    """The mined kinds from the score matrix s [B, n] on (column j = partner number j) and the boolean sets pos / neg [B, n] -> dict:
+    sp, sn (the extremes, detached, 0 where invalid), ip, inn (their partner numbers, -1 where invalid), valid, keep [B, n] (the pairs
+    with a weight: p* and n* for batch_hard, the miner's choice for multi_similarity), x [B, n] (multi_similarity: the logits, part of the
+    graph), a, b (batch_hard: z_i, f_i; multi_similarity: L_p, L_n; 0 where invalid, detached), rows (l_i, part of the graph)."""
+    p = _params(kind, params)
+    B, n = s.shape
+    sd = s.detach()
+    ok = ~torch.isnan(sd)                                           # a NaN score is in neither set
+    pos, neg = pos & ok, neg & ok
+    valid = pos.any(1) & neg.any(1)
+    num = torch.arange(n, device=s.device).expand(B, n)
+    inf = float("inf")
+
+    def extreme(mask, sign):
+        v = (sign * sd).masked_fill(~mask, inf).min(1).values       # min of s (sign = 1) or of -s
+        at = mask & ((sign * sd) == v[:, None])                     # == : -0.0 ties with +0.0
+        i = torch.where(at, num, n).min(1).values                   # the smallest partner number among the ties
+        return i
+
+    ip, inn = extreme(pos, 1.0), extreme(neg, -1.0)
+    ipc, inc = ip.clamp_max(n - 1)[:, None], inn.clamp_max(n - 1)[:, None]
+    zero = sd.new_zeros(B)
+    sp = torch.where(valid, sd.gather(1, ipc).squeeze(1), zero)
+    sn = torch.where(valid, sd.gather(1, inc).squeeze(1), zero)
+    minus = torch.full_like(ip, -1)
+    out = dict(sp=sp, sn=sn, ip=torch.where(valid, ip, minus), inn=torch.where(valid, inn, minus), valid=valid)
+    if kind == "batch_hard":
+        z = s.gather(1, inc).squeeze(1) - s.gather(1, ipc).squeeze(1) + p["m"]
+        z = torch.where(valid, z, zero)
+        g = p["gamma"]
+        # the hinge is active iff z > 0 (clamp_min's backward would also pass the gradient at z = 0 exactly)
+        rows = torch.where(z.detach() > 0, z, z * 0) if g == 0 else -F.logsigmoid(-g * z) / g
+        f = (z.detach() > 0).to(s.dtype) if g == 0 else torch.sigmoid(g * z.detach())
+        keep = (num == ipc) | (num == inc)
+        out.update(x=s, a=z.detach(), b=torch.where(valid, f, zero), keep=keep & valid[:, None])
+    else:
+        al, be, lam, eps = p["alpha"], p["beta"], p["base"], p["epsilon"]
+        keep = ((neg & (sd + eps > sp[:, None])) | (pos & (sd - eps < sn[:, None]))) & valid[:, None]
+        x = torch.where(pos, -al * (s - lam), be * (s - lam))
+        ninf = float("-inf")
+        z0 = s.new_zeros(B, 1)                                      # the element 0 of log(1 + sum)
+        Lp = torch.logsumexp(torch.cat([z0, x.masked_fill(~(keep & pos), ninf)], 1), 1)
+        Ln = torch.logsumexp(torch.cat([z0, x.masked_fill(~(keep & neg), ninf)], 1), 1)
+        rows = Lp / al + Ln / be
+        out.update(x=x, a=torch.where(valid, Lp.detach(), zero), b=torch.where(valid, Ln.detach(), zero), keep=keep)
+    out["rows"] = torch.where(valid, rows, zero)
+    return out
+
+
+def _mined_from_scores(s, pos, neg, kind, params):
+    """-> (loss, l (detached), valid, logits) of the mined kinds, the return of pair_loss_from_scores"""
+    r = pair_mined_parts(s, pos, neg, kind, **params)
+    A = int(r["valid"].sum())
+    if A == 0:
+        return (s * 0).sum(), s.new_zeros(s.shape[0]), r["valid"], r["x"]        # 0.0 exactly, and a zero gradient
+    return r["rows"].sum() / A, r["rows"].detach(), r["valid"], r["x"]
 
 
 def pair_loss_from_scores(s, label, kind, s_alpha=None, **params):
@@ -49,6 +124,8 @@ def pair_loss_from_scores(s, label, kind, s_alpha=None, **params):
     same = label[:, None] == label[None, :]
     eye = torch.eye(B, dtype=torch.bool, device=s.device)
     pos, neg = same & ~eye, ~same
+    if kind in MINED_KINDS:
+        return _mined_from_scores(s, pos, neg, kind, params)
     valid = pos.any(1) if kind == "supcon" else pos.any(1) & neg.any(1)
     idx = valid.nonzero().squeeze(1)
     if kind == "supcon":
@@ -94,6 +171,8 @@ def pair_loss_mem_from_scores(s_batch, s_mem, label, mem_label, kind, s_alpha=No
     same = label[:, None] == torch.cat([label, mem_label.to(label.device)])[None, :]
     eye = torch.cat([torch.eye(B, dtype=torch.bool, device=s.device), torch.zeros(B, n, dtype=torch.bool, device=s.device)], 1)
     pos, neg = same & ~eye, ~same
+    if kind in MINED_KINDS:
+        return _mined_from_scores(s, pos, neg, kind, params)
     valid = pos.any(1) if kind == "supcon" else pos.any(1) & neg.any(1)
     idx = valid.nonzero().squeeze(1)
     if kind == "supcon":
@@ -184,6 +263,45 @@ class PairMemLossFunction(torch.autograd.Function):
         return demb.to(emb.dtype), None, None, None, None, None
 
 
+class PairMinedLossFunction(torch.autograd.Function):
+    """The mined kinds on the device: pfr_l2norm_fwd + pfr_pair_mined_fwd; backward: pfr_pair_mined_bwd + pfr_l2norm_bwd.  owner = None:
+    the batch alone.  owner = a PairLoss with memory > 0: against its ring, with the `count`, `keep` and generation rules of
+    PairMemLossFunction."""
+
+    @staticmethod
+    def forward(ctx, emb, label, kind, params, T, owner, count, keep):
+        from .._hip import ops
+        emb = emb.contiguous()
+        label = label.contiguous()
+        B = emb.shape[0]
+        xn, xnT, inv = ops.l2norm_fwd(emb, T, want_t=True, ldt=(B + 31) // 32 * 32)
+        ring = {}
+        if owner is not None:
+            owner._ensure(xn)
+            ring = dict(mem=owner.mem, mem_label=owner.mem_label, count=count)
+        out, stats, _ = ops.pair_mined_fwd(xn, label, kind, **ring, **params)
+        ctx.save_for_backward(emb, label, xn, xnT, inv, stats, out)
+        ctx.kind, ctx.params, ctx.owner, ctx.count = kind, params, owner, count
+        if owner is not None:
+            ctx.generation = owner.generation
+            if keep:
+                owner._pending = (xn, label)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        from .._hip import ops
+        emb, label, xn, xnT, inv, stats, out = ctx.saved_tensors
+        o = ctx.owner
+        ring = {}
+        if o is not None:
+            o._guard(ctx.generation)
+            ring = dict(mem=o.mem, memT=o.memT, mem_label=o.mem_label, count=ctx.count)
+        dxn = ops.pair_mined_bwd(xn, xnT, label, stats, out, ctx.kind, grad_scale_dev=g.float().contiguous(), **ring, **ctx.params)
+        demb = ops.l2norm_bwd(emb, inv, dxn, torch.float32)
+        return demb.to(emb.dtype), None, None, None, None, None, None, None
+
+
 class _RingGuard(torch.autograd.Function):
     """identity whose backward refuses a ring that has been pushed to since the forward (the CPU path of the generation guard)"""
 
@@ -199,7 +317,9 @@ class _RingGuard(torch.autograd.Function):
 
 
 class PairLoss(nn.Module):
-    """PairLoss(kind, **params): forward(emb [B, D], label [B]) -> scalar.  kind 'supcon' (tau=0.1) or 'circle' (m=0.25, gamma=64).
+    """PairLoss(kind, **params): forward(emb [B, D], label [B]) -> scalar.  kind 'supcon' (tau=0.1), 'circle' (m=0.25, gamma=64),
+    'batch_hard' (m=0.3, gamma=0: the hinge; gamma > 0: softplus(gamma z) / gamma) or 'multi_similarity' (alpha=2, beta=50, base=0.5,
+    epsilon=0.1).
     compute_dtype (fp32 / bf16; None = the default of the HIP engines, as the margin heads resolve it) is the dtype of ê on the device:
     in bf16 the scores come from the bf16-rounded ê with fp32 accumulation.  int8 is not supported.
 
@@ -283,6 +403,8 @@ class PairLoss(nn.Module):
         # the warm-up covers the training calls 1 .. memory_warmup; a call that does not train reads the ring once those are done
         warm = self.train_calls <= self.memory_warmup if keep else self.train_calls < self.memory_warmup
         count = 0 if warm else self.count
+        if emb.is_cuda and self.kind in MINED_KINDS:
+            return PairMinedLossFunction.apply(emb, label, self.kind, self.params, T, self, count, keep)
         if emb.is_cuda:
             return PairMemLossFunction.apply(emb, label, self, count, T, keep)
         xn = F.normalize(emb, dim=1, eps=1e-12)
@@ -303,6 +425,8 @@ class PairLoss(nn.Module):
             raise ValueError(f"pair loss: the compute dtype is fp32 or bf16, got {T}")
         if self.memory:
             return self._forward_memory(emb, label, T)
+        if self.kind in MINED_KINDS:
+            return PairMinedLossFunction.apply(emb, label, self.kind, self.params, T, None, 0, False)
         return PairLossFunction.apply(emb, label, self.kind, T, self.params)
 
 
@@ -310,6 +434,6 @@ def build_pair_loss(spec):
     """dict(kind=..., weight=1.0, memory=0, memory_warmup=0, compute_dtype=None, **params) -> (PairLoss, weight)"""
     spec = dict(spec)
     if "kind" not in spec:
-        raise ValueError("pair_loss needs a 'kind' ('supcon' or 'circle')")
+        raise ValueError(f"pair_loss needs a 'kind' (one of {list(KINDS)})")
     weight = float(spec.pop("weight", 1.0))
     return PairLoss(spec.pop("kind"), **spec), weight
